@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- HR Mpixels/s of the rasterizer hot path (forward + backward) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dmax 0.1] [--config c2|c3|c4|c5|c5s]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dmax 0.1] [--config c2|c3|c4|c5|c5s] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic Gaussians already resident in HBM:
 plan (bin) -> forward splat into a fresh [H,W,3] image -> backward to {sigmas, coords, colors}, exactly what
@@ -16,8 +16,16 @@ plan (bin) -> forward splat into a fresh [H,W,3] image -> backward to {sigmas, c
           --exchange broadcast: ONE broadcast of all [N,8] Gaussians from rank 0 and ONE reduce_scatter of
             the per-Gaussian gradients per step (the literal 8e pattern; volume grows with N).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel, measured
-live with events on the launch stream) and `cpu_baseline` (the oracle on the host cores, bounded sample).
+Rank 0 prints ONE JSON line: `metric`, `value`, `unit`, `ms_per_step` (one timed step),
+`higher_is_better`, `dtype` and the workload's `config`.  A plain run does only that: set-up, warm-up, the timed steps,
+the line.  `--full` adds everything else the bench measures, in runs of their own after the timed steps: `roofline` and
+`kernels` (per-stage device times with events on the launch stream, rocprofv3 counter passes), `cpu_baseline` (the
+oracle on the host cores, bounded sample), the other configs and exact-semantics / drop-in / published legs of config 2,
+and the multi-rank legs of `--gpus N`.
+
+--dump-outputs DIR writes what the timed path computed in its LAST step -- the image and the gradients a caller receives
+(rank 0's rows) -- as DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample of larger arrays:
+DIR/<name>_sample.npy); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -31,8 +39,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from benchlib import (CONFIGS, HBM_PEAK_GBS, PAIR_CEILING, Step, band8_leg, bound_label, pair_ceiling, copy_bandwidth, cpu_baseline, dropin_run, effective_tau, emit,  # noqa: E402
-                      exact_runs, live_counters, flush_c_stdio, published_leg, run_c5e2e, single_gpu_leg, stage_times, strong_c4_leg, window_pairs)
+from benchlib import (CONFIGS, HBM_PEAK_GBS, PAIR_CEILING, Step, band8_leg, bound_label, pair_ceiling, copy_bandwidth, cpu_baseline, dropin_run, dump_outputs,  # noqa: E402
+                      effective_tau, emit, exact_runs, live_counters, flush_c_stdio, published_leg, run_c5e2e, single_gpu_leg, stage_times, strong_c4_leg, window_pairs)
 
 
 def parse():
@@ -44,6 +52,11 @@ def parse():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--cutoff", type=float, default=0.0, help="support cutoff tau (0 = library default: adaptive ln(N/1e-5))")
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step in a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: roofline, per-kernel times and counters, CPU baseline, the other "
+                         "configs and legs (--no-cpu-baseline / --no-live-pmc / --no-extras trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not count the dominant kernel's HBM bytes live (two short child runs under rocprofv3 --pmc); "
@@ -105,7 +118,7 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world} (launch with torch.distributed.run)"
 
     if args.config == "c5e2e":
-        run_c5e2e(args, dev, rank, world)
+        run_c5e2e(args, dev, rank, world, full=args.full, dump=args.dump_outputs)
         if world > 1 or args.force_dist:
             import torch.distributed as dist
             dist.destroy_process_group()
@@ -181,103 +194,110 @@ def main():
     ms = dt / args.steps * 1e3
     mpix = step.H * step.W / (dt / args.steps) / 1e6        # whole-job HR pixels per second (all ranks)
 
-    # per-kernel device time, measured live (not part of the timed region)
-    kern = stage_times(step, dev, iters=30)
-    dom = max((k for k in kern if k != "plan"), key=lambda k: kern[k]["avg_ms"])
-    traffic, traffic_source, live = None, None, None
-    pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")   # (committed passes: the fallback when rocprofv3 is missing)
-    dom_kernel = {"forward": "k_render_fwd", "backward": "k_render_bwd"}[dom]
-    if world == 1 and rank == 0 and not args.no_live_pmc and not args.force_dist:
-        # counted NOW, on this box, for this build: three child runs of the same workload under rocprofv3 --pmc
-        extra = ["--config", args.config, "--dmax", str(args.dmax), "--cutoff", str(args.cutoff)] + (["--fwd-only"] if args.fwd_only else [])
-        try:
-            live, note = live_counters(extra)
-        except Exception as e:      # the counters must never take the line with them
-            live, note = None, repr(e)
-        if live and live.get(dom, {}).get("hbm_bytes"):
-            traffic, traffic_source = live[dom]["hbm_bytes"], note
-        else:
-            print(f"[bench] live counters unavailable ({note}); replaying profiles/pmc_latest.json", file=sys.stderr)
-    if traffic is None and os.path.exists(pmc) and args.config == "c2" and world == 1:
-        try:
-            traffic = json.load(open(pmc)).get(dom_kernel, {}).get("hbm_bytes")
-            traffic_source = ("profiles/pmc_latest.json (REPLAYED: HBM bytes per launch of this kernel from the committed rocprofv3 "
-                              "--pmc FETCH_SIZE / WRITE_SIZE passes of the same command, not counted in this run)")
-        except Exception:
-            traffic = None
-    kname = {"forward": "k_sample_fwd", "backward": "k_sample_bwd"} if getattr(step, "sampled", False) else \
-        {"forward": "k_render_fwd", "backward": "k_render_bwd"}
-    valu_busy_live = {k: v.get("valu_busy") for k, v in (live or {}).items()}
-    roofline = {"bound": "hbm", "kernel": ", ".join((live or {}).get(dom, {}).get("kernels", [])) or kname[dom],
-                "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": kern[dom]["GBps"] / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_over_algorithmic": round(traffic / kern[dom]["algorithmic_bytes"], 2) if traffic and kern[dom].get("algorithmic_bytes") else None,
-                "traffic_source": traffic_source if traffic is not None else None,
-                "binding_resource": bound_label(valu_busy_live.get(dom)),
-                "bound_note": "`bound` = the roof `frac` is measured against (HBM: SURVEY 8(d)'s algorithmic bytes / stage time / 8 TB/s); the kernel is NOT "
-                              "HBM-bound: `binding_resource` is what the live SQ counters say binds it (valu_busy = VALU issue occupancy)",
-                "valu_busy": valu_busy_live, "counters": live,
-                "note": "stage times from events on the launch stream; outputs are stored, not accumulated (no memsets)"}
-    # The binding unit is the fp32 VALU / v_exp_f32 pipe, not HBM: report pair rates and the VALU
-    # occupancy next to the HBM fraction.
-    if rank == 0:
-        try:
-            roofline["hbm_copy_GBps_measured"] = round(copy_bandwidth(dev), 1)
-            roofline["frac_of_measured_copy"] = kern[dom]["GBps"] / roofline["hbm_copy_GBps_measured"]
-        except Exception as e:
-            roofline["hbm_copy_GBps_measured"] = None
-            print(f"[bench] copy bandwidth probe failed: {e!r}", file=sys.stderr)
-        if not step.halo and not step.batched:
-            tau, _ = effective_tau(step, args.cutoff)
-            in_box, swept = window_pairs(step.sig, step.xy, step.H, step.W, step.dmax, tau, step.rows)
-            valu = {"pairs_in_dmax_box": in_box, "pairs_in_swept_window": swept,
-                    "Gpairs_per_s": {k: round(swept / (kern[k]["avg_ms"] * 1e-3) / 1e9, 1) for k in kern if k != "plan"},
-                    "note": "pairs = (Gaussian, pixel) terms; box = what gs_cuda_dmax sums, swept window = box ∩ support cutoff"}
-            # fraction of the pair-evaluation ceiling (the roof that binds): swept pairs/s over SIMDs * clock / cycles per
-            # packed trip * 128 pairs, with the instruction counts the ceiling assumes
-            valu["ceiling"] = {k: pair_ceiling(step, k) for k in kern if k in PAIR_CEILING}
-            valu["ceiling_note"] = ("1024 SIMDs x 2.4 GHz; wave64 VALU (packed fp32 included) = 4 cycles, v_exp_f32 = 8 cycles "
-                                    "(tools/valu_rate.hip); one packed trip = 128 pairs")
-            roofline["valu_frac"] = {k: swept / (kern[k]["avg_ms"] * 1e-3) / pair_ceiling(step, k)["pairs_per_s"]
-                                     for k in kern if k in PAIR_CEILING}
-            if valu_busy_live:
-                valu["valu_busy_rocprof"] = dict(valu_busy_live, source="counted live in this run (roofline.counters)")
-            elif os.path.exists(pmc) and args.config == "c2" and world == 1:
-                try:
-                    j = json.load(open(pmc))
-                    valu["valu_busy_rocprof"] = {"forward": j["k_render_fwd"].get("valu_busy"),
-                                                 "backward": j["k_render_bwd"].get("valu_busy"),
-                                                 "source": "profiles/pmc_latest.json (REPLAYED: SQ_INSTS_VALU, SQ_BUSY_CYCLES of the committed passes)"}
-                except Exception:
-                    pass
-            roofline["valu"] = valu
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, step.outputs())
+        print(f"[bench] outputs of the last timed step: {', '.join(names)} in {args.dump_outputs}", file=sys.stderr)
 
+    # everything below the headline (--full): per-kernel device times, counters, roofline, multi-rank legs
+    kern = roofline = None
     c4_strong = c4_strong_halo = c4_strong_halo_overlap = other_exchange = None
-    if (world > 1 or args.force_dist) and args.config == "c2" and not step.batched:
-        # the headline's own weak-scaled workload over the OTHER exchange, beside it in the same line (halo first, the north
-        # star's broadcast + reduce-scatter next to it), with its own rccl block
-        try:
-            other_exchange = strong_c4_leg(args, dev, rank, world, exchange="broadcast" if args.exchange == "halo" else "halo", config="c2")
-        except Exception as e:
-            other_exchange = {"error": repr(e)}
-    if (world > 1 or args.force_dist) and args.config in ("c2", "c4") and not step.batched:
-        # BASELINE config 4's own pattern -- strong-scaled 8192^2, packed broadcast + in-place reduce-scatter -- as a leg of
-        # EVERY multi-rank line, whatever exchange the headline used
-        try:
-            c4_strong = strong_c4_leg(args, dev, rank, world)
-        except Exception as e:
-            c4_strong = {"error": repr(e)}
-        # ... and the same image with a sharded producer and the nearest-neighbour halo swap (what DESIGN.md section 5 proposes
-        # for this path: 64 MB per rank and step of collectives become a few hundred KB)
-        try:
-            c4_strong_halo = strong_c4_leg(args, dev, rank, world, exchange="halo")
-        except Exception as e:
-            c4_strong_halo = {"error": repr(e)}
-        # ... and with the swap hidden behind the own Gaussians' render (two renders per band)
-        try:
-            c4_strong_halo_overlap = strong_c4_leg(args, dev, rank, world, exchange="halo", overlap=True)
-        except Exception as e:
-            c4_strong_halo_overlap = {"error": repr(e)}
+    if args.full:
+        # per-kernel device time, measured live (not part of the timed region)
+        kern = stage_times(step, dev, iters=30)
+        dom = max((k for k in kern if k != "plan"), key=lambda k: kern[k]["avg_ms"])
+        traffic, traffic_source, live = None, None, None
+        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")   # (committed passes: the fallback when rocprofv3 is missing)
+        dom_kernel = {"forward": "k_render_fwd", "backward": "k_render_bwd"}[dom]
+        if world == 1 and rank == 0 and not args.no_live_pmc and not args.force_dist:
+            # counted NOW, on this box, for this build: three child runs of the same workload under rocprofv3 --pmc
+            extra = ["--config", args.config, "--dmax", str(args.dmax), "--cutoff", str(args.cutoff)] + (["--fwd-only"] if args.fwd_only else [])
+            try:
+                live, note = live_counters(extra)
+            except Exception as e:      # the counters must never take the line with them
+                live, note = None, repr(e)
+            if live and live.get(dom, {}).get("hbm_bytes"):
+                traffic, traffic_source = live[dom]["hbm_bytes"], note
+            else:
+                print(f"[bench] live counters unavailable ({note}); replaying profiles/pmc_latest.json", file=sys.stderr)
+        if traffic is None and os.path.exists(pmc) and args.config == "c2" and world == 1:
+            try:
+                traffic = json.load(open(pmc)).get(dom_kernel, {}).get("hbm_bytes")
+                traffic_source = ("profiles/pmc_latest.json (REPLAYED: HBM bytes per launch of this kernel from the committed rocprofv3 "
+                                  "--pmc FETCH_SIZE / WRITE_SIZE passes of the same command, not counted in this run)")
+            except Exception:
+                traffic = None
+        kname = {"forward": "k_sample_fwd", "backward": "k_sample_bwd"} if getattr(step, "sampled", False) else \
+            {"forward": "k_render_fwd", "backward": "k_render_bwd"}
+        valu_busy_live = {k: v.get("valu_busy") for k, v in (live or {}).items()}
+        roofline = {"bound": "hbm", "kernel": ", ".join((live or {}).get(dom, {}).get("kernels", [])) or kname[dom],
+                    "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": kern[dom]["GBps"] / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_over_algorithmic": round(traffic / kern[dom]["algorithmic_bytes"], 2) if traffic and kern[dom].get("algorithmic_bytes") else None,
+                    "traffic_source": traffic_source if traffic is not None else None,
+                    "binding_resource": bound_label(valu_busy_live.get(dom)),
+                    "bound_note": "`bound` = the roof `frac` is measured against (HBM: SURVEY 8(d)'s algorithmic bytes / stage time / 8 TB/s); the kernel is NOT "
+                                  "HBM-bound: `binding_resource` is what the live SQ counters say binds it (valu_busy = VALU issue occupancy)",
+                    "valu_busy": valu_busy_live, "counters": live,
+                    "note": "stage times from events on the launch stream; outputs are stored, not accumulated (no memsets)"}
+        # The binding unit is the fp32 VALU / v_exp_f32 pipe, not HBM: report pair rates and the VALU
+        # occupancy next to the HBM fraction.
+        if rank == 0:
+            try:
+                roofline["hbm_copy_GBps_measured"] = round(copy_bandwidth(dev), 1)
+                roofline["frac_of_measured_copy"] = kern[dom]["GBps"] / roofline["hbm_copy_GBps_measured"]
+            except Exception as e:
+                roofline["hbm_copy_GBps_measured"] = None
+                print(f"[bench] copy bandwidth probe failed: {e!r}", file=sys.stderr)
+            if not step.halo and not step.batched:
+                tau, _ = effective_tau(step, args.cutoff)
+                in_box, swept = window_pairs(step.sig, step.xy, step.H, step.W, step.dmax, tau, step.rows)
+                valu = {"pairs_in_dmax_box": in_box, "pairs_in_swept_window": swept,
+                        "Gpairs_per_s": {k: round(swept / (kern[k]["avg_ms"] * 1e-3) / 1e9, 1) for k in kern if k != "plan"},
+                        "note": "pairs = (Gaussian, pixel) terms; box = what gs_cuda_dmax sums, swept window = box ∩ support cutoff"}
+                # fraction of the pair-evaluation ceiling (the roof that binds): swept pairs/s over SIMDs * clock / cycles per
+                # packed trip * 128 pairs, with the instruction counts the ceiling assumes
+                valu["ceiling"] = {k: pair_ceiling(step, k) for k in kern if k in PAIR_CEILING}
+                valu["ceiling_note"] = ("1024 SIMDs x 2.4 GHz; wave64 VALU (packed fp32 included) = 4 cycles, v_exp_f32 = 8 cycles "
+                                        "(tools/valu_rate.hip); one packed trip = 128 pairs")
+                roofline["valu_frac"] = {k: swept / (kern[k]["avg_ms"] * 1e-3) / pair_ceiling(step, k)["pairs_per_s"]
+                                         for k in kern if k in PAIR_CEILING}
+                if valu_busy_live:
+                    valu["valu_busy_rocprof"] = dict(valu_busy_live, source="counted live in this run (roofline.counters)")
+                elif os.path.exists(pmc) and args.config == "c2" and world == 1:
+                    try:
+                        j = json.load(open(pmc))
+                        valu["valu_busy_rocprof"] = {"forward": j["k_render_fwd"].get("valu_busy"),
+                                                     "backward": j["k_render_bwd"].get("valu_busy"),
+                                                     "source": "profiles/pmc_latest.json (REPLAYED: SQ_INSTS_VALU, SQ_BUSY_CYCLES of the committed passes)"}
+                    except Exception:
+                        pass
+                roofline["valu"] = valu
+
+        if (world > 1 or args.force_dist) and args.config == "c2" and not step.batched:
+            # the headline's own weak-scaled workload over the OTHER exchange, beside it in the same line (halo first, the north
+            # star's broadcast + reduce-scatter next to it), with its own rccl block
+            try:
+                other_exchange = strong_c4_leg(args, dev, rank, world, exchange="broadcast" if args.exchange == "halo" else "halo", config="c2")
+            except Exception as e:
+                other_exchange = {"error": repr(e)}
+        if (world > 1 or args.force_dist) and args.config in ("c2", "c4") and not step.batched:
+            # BASELINE config 4's own pattern -- strong-scaled 8192^2, packed broadcast + in-place reduce-scatter -- as a leg of
+            # EVERY multi-rank line, whatever exchange the headline used
+            try:
+                c4_strong = strong_c4_leg(args, dev, rank, world)
+            except Exception as e:
+                c4_strong = {"error": repr(e)}
+            # ... and the same image with a sharded producer and the nearest-neighbour halo swap (what DESIGN.md section 5 proposes
+            # for this path: 64 MB per rank and step of collectives become a few hundred KB)
+            try:
+                c4_strong_halo = strong_c4_leg(args, dev, rank, world, exchange="halo")
+            except Exception as e:
+                c4_strong_halo = {"error": repr(e)}
+            # ... and with the swap hidden behind the own Gaussians' render (two renders per band)
+            try:
+                c4_strong_halo_overlap = strong_c4_leg(args, dev, rank, world, exchange="halo", overlap=True)
+            except Exception as e:
+                c4_strong_halo_overlap = {"error": repr(e)}
     if world > 1:      # every rank's C-stdio output (RCCL banner) is out before rank 0 prints the line
         import torch.distributed as dist
         flush_c_stdio()
@@ -308,8 +328,9 @@ def main():
                        "forward_subtile_px": None if step.batched else step.cabi.forward_subtile_width(step.plan),   # 16 = wide forward (x5 and up)
                        "parallelism": (f"data-parallel x{world} (one batch per rank, no exchange)" if step.batched and world > 1
                                        else f"row-band x{world}" if world > 1 else "single")},
-            "roofline": roofline, "kernels": kern,
         }
+        if args.full:
+            out["roofline"], out["kernels"] = roofline, kern
         if step.dist:
             out["config"]["exchange"] = (f"halo swap with ranks g-1/g+1 ({step.ex.transport if step.halo else ''}), "
                                          f"{step.halo_records} records max per edge, capacity {step.ex.cap}"
@@ -323,7 +344,7 @@ def main():
                                      "pattern": (("2 x all_to_all_single with non-zero splits for ranks g-1/g+1 only" if step.ex.transport == "alltoall"
                                                   else "2 x batch_isend_irecv with ranks g-1/g+1") + " (forward records, backward gradients)")
                                                 if step.halo else "broadcast of ONE packed [N,8] buffer + in-place reduce_scatter_tensor of the [N,8] gradients"}
-        if world == 1 and args.config == "c2" and not args.no_extras and not args.force_dist:
+        if args.full and world == 1 and args.config == "c2" and not args.no_extras and not args.force_dist:
             out["exact"] = exact_runs(args, dev, step.H * step.W)
             out["dropin"] = dropin_run(args, dev)
             # the other scale factors the north star names (x12 forward only = BASELINE config 3, x8 fwd+bwd = config 4 on this
@@ -364,7 +385,7 @@ def main():
             out["c4_strong_halo"] = c4_strong_halo
         if c4_strong_halo_overlap is not None:
             out["c4_strong_halo_overlap"] = c4_strong_halo_overlap
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         emit(out)
     if world > 1 or args.force_dist:

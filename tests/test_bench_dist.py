@@ -27,7 +27,7 @@ def test_bench_two_ranks_functional(launcher, extra):
     the driver uses at N = 1); under `python -m torch.distributed.run ... bench.py --gpus 2` (the driver's N > 1 form)
     it must not spawn again."""
     cmd = [*launcher, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--no-cpu-baseline", *extra]
+           "--backend", "gloo", "--full", "--no-cpu-baseline", *extra]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -73,7 +73,7 @@ def test_bench_force_dist_over_rccl(exchange):
     """`bench.py --force-dist --backend nccl`: the multi-rank code path of the bench -- process group, exchange, barriers, the
     rccl blocks of the line -- on a one-rank RCCL group; the halo form and the north star's broadcast form side by side"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--backend", "nccl", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--exchange", exchange]
+           "--full", "--no-cpu-baseline", "--exchange", exchange]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

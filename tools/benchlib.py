@@ -143,6 +143,7 @@ class Step:
         self.cutoff = args.cutoff
         H = W = int(h_lr * scale)
         self.B, self.H, self.W = B, B * H * self.world, W     # H x W reported = all samples' pixels on all ranks
+        self.h_sample = H
         self.pix_rank = B * H * W
         p = torch.stack([synthetic.gs_parameters(h_lr, w_lr, seed=b + 100 * self.rank, gpp=gpp) for b in range(B)])
         self.p = p.to(dev)
@@ -285,6 +286,25 @@ class Step:
             self.do_backward()
             if self.dist:                                            # per-Gaussian grads, summed over bands, in place
                 self.shard.reduce_packed_grads_(self.gpad, self.n, "reduce_scatter")
+
+    def outputs(self):
+        """{name: tensor}: what a caller of the timed step receives from its last call -- the image (this rank's rows)
+        and the gradients, views of the step's own buffers (a captured graph replays into the same ones)"""
+        if self.batched:       # (planar [B,3,slot,W] canvas: the rows past a sample's own height are padding)
+            out = {"samples": self.out} if self.sampled else {"image": self.img[:, :, : self.h_sample]}
+            if not self.fwd_only:
+                out["grad_params"] = self.gp
+            return out
+        out = {"image": self.img}
+        if self.fwd_only:
+            return out
+        if self.halo:
+            out["grad_packed"] = self.ex.g_records[: self.ex.n]           # own Gaussians, halo gradients merged in
+        elif self.dist:
+            out["grad_packed"] = self.gpad[: self.n]                       # this rank's reduced slice, the rest zero
+        else:
+            out.update(zip(("grad_sigmas", "grad_coords", "grad_colors"), self.g))
+        return out
 
     # algorithmic bytes (SURVEY.md 8d): fwd = 32 N + 24 H W with the reference's accumulate-into contract; the
     # step stores into a fresh image (GSASR_FLAG_OVERWRITE_IMAGE), so the image is written once and never read:
@@ -475,6 +495,29 @@ def emit(out):
     flush_c_stdio()
     sys.stdout.write(json.dumps(out) + "\n")
     sys.stdout.flush()
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirpath, arrays, seed=0):
+    """Write {name: float32 tensor} as `dirpath/<name>.npy` (float32, the tensor's shape).  When the whole set is larger than
+    DUMP_BYTES, every array above an equal share of it is written as `<name>_sample.npy` instead: that many of its elements
+    at flat indices drawn from a generator seeded with `seed` (ascending; the same indices for the same shape on every run).
+    Returns the file names written."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(1, len(arrays))
+    big = sum(t.numel() for t in arrays.values()) * 4 > DUMP_BYTES
+    names = []
+    for name, t in arrays.items():
+        t = t.detach()
+        if big and t.numel() > share:
+            idx = torch.randint(0, t.numel(), (share,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(dirpath, name + ".npy"), t.float().cpu().numpy())
+        names.append(name + ".npy")
+    return names
 
 
 def wall_ms(fn, n, dev, warm=3, warm_s=0.0):
@@ -765,10 +808,12 @@ def cpu_baseline(args):
     return out
 
 
-def run_c5e2e(args, dev, rank, world, as_leg=False):
+def run_c5e2e(args, dev, rank, world, as_leg=False, full=True, dump=None):
     """BASELINE.json config 5 end to end.  One step = reference
     `optimize_parameters` (TrainTestGSASR/basicsr/models/gsasr_model.py:175-245) with this package's batched rasterizer.
-    N > 1: independent replicas (one batch per rank, no collective: the rasterizer path itself does not shard here)."""
+    N > 1: independent replicas (one batch per rank, no collective: the rasterizer path itself does not shard here).
+    full: also the rasterizer's share of the step and (unless args.no_cpu_baseline) the CPU baseline; dump: a directory for
+    the last timed step's loss and decoder output (dump_outputs)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import c5_models
     from gsasr_amd import gaussian_splatting as gsp
@@ -804,24 +849,28 @@ def run_c5e2e(args, dev, rank, world, as_leg=False):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms = dt / args.steps * 1e3
-    # the rasterizer's share: the same batched splat forward + backward alone, on the decoder's last output
-    pd = params.detach()
-    g = torch.rand(B, 3, H, W, device=dev)
-    sms = [(scale, scale)] * B
+    if dump and rank == 0:
+        names = dump_outputs(dump, {"loss": loss.reshape(1), "params": params})
+        print(f"[bench] outputs of the last timed step: {', '.join(names)} in {dump}", file=sys.stderr)
+    if full:
+        # the rasterizer's share: the same batched splat forward + backward alone, on the decoder's last output
+        pd = params.detach()
+        g = torch.rand(B, 3, H, W, device=dev)
+        sms = [(scale, scale)] * B
 
-    def raster():
-        pa = pd.requires_grad_(True)
-        gsp.generate_2D_gaussian_splatting_batch(sizes, pa, scales, sms, dmax=dmax).backward(g)
-        pa.grad = None
+        def raster():
+            pa = pd.requires_grad_(True)
+            gsp.generate_2D_gaussian_splatting_batch(sizes, pa, scales, sms, dmax=dmax).backward(g)
+            pa.grad = None
 
-    ms_raster = wall_ms(raster, 20, dev)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-    for a, b in evs:
-        a.record()
-        raster()
-        b.record()
-    torch.cuda.synchronize(dev)
-    dev_raster = sorted(a.elapsed_time(b) for a, b in evs)[len(evs) // 2]
+        ms_raster = wall_ms(raster, 20, dev)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        for a, b in evs:
+            a.record()
+            raster()
+            b.record()
+        torch.cuda.synchronize(dev)
+        dev_raster = sorted(a.elapsed_time(b) for a, b in evs)[len(evs) // 2]
     n_params = sum(p.numel() for p in list(enc.parameters()) + list(dec.parameters()))
     if rank != 0:
         return
@@ -834,11 +883,12 @@ def run_c5e2e(args, dev, rank, world, as_leg=False):
                       "parallelism": f"independent replicas x{world}" if world > 1 else "single",
                       "producers": "tools/c5_models.py: EDSR-baseline-shaped encoder (16 res blocks, 64 ch) + the Fea2GS decoder's architecture at "
                                    "the shipped EDSR-baseline configuration (channel 180, 6 heads, 12x12 windows, 144 seeds, 1 x 2 cross-attention + "
-                                   "6 x 6 self-attention layers, pixel-shuffle 2 x 2, five MLP heads), own code, random init"},
-           "rasterizer": {"ms_fwd_bwd_wall": ms_raster, "ms_fwd_bwd_device": dev_raster, "share_of_step": dev_raster / ms,
-                          "note": "generate_2D_gaussian_splatting_batch forward + backward alone on the decoder's output "
-                                  "(prologue + plan + splat, splat backward + chain rule), events on the launch stream"}}
-    if world == 1 and not args.no_cpu_baseline:
+                                   "6 x 6 self-attention layers, pixel-shuffle 2 x 2, five MLP heads), own code, random init"}}
+    if full:
+        out["rasterizer"] = {"ms_fwd_bwd_wall": ms_raster, "ms_fwd_bwd_device": dev_raster, "share_of_step": dev_raster / ms,
+                             "note": "generate_2D_gaussian_splatting_batch forward + backward alone on the decoder's output "
+                                     "(prologue + plan + splat, splat backward + chain rule), events on the launch stream"}
+    if full and world == 1 and not args.no_cpu_baseline:
         # one SAMPLE of the same step on the host cores with the oracle as the rasterizer back end
         from oracle import gs_oracle, host_ref
         cores = gs_oracle.num_threads()

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export GSASR_SPLAT_DEV=1   # the GSASR_SPLAT_* A/B switches below are read only with it
-BENCH="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extras --no-live-pmc"
+BENCH="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extras --no-live-pmc"
 sq="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_SALU"
 pass() {   # pass <name> "<counters>" <command...>: one counters-only run -> $OUT/<name>.txt
   local name=$1 ctr=$2; shift 2
@@ -60,39 +60,39 @@ for cfg in c3 c4 c2x16; do
   pass pmc_write_$cfg "WRITE_SIZE" $BENCH --config $cfg --steps 5 --warmup 2
   pass pmc_sq_$cfg "$sq" $BENCH --config $cfg --steps 5 --warmup 2
 done
-# 4. the plain bench line (with exact / dropin / cpu_baseline / the x12, x8 and 16-per-LR-pixel legs)
-cd $R && python bench.py > $OUT/bench.json 2> $OUT/bench.err
+# 4. the --full bench line (with exact / dropin / cpu_baseline / the x12, x8 and 16-per-LR-pixel legs)
+cd $R && python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/kernel_stats.txt $OUT/pmc_fetch.txt $OUT/pmc_write.txt
 tail -c 3000 $OUT/bench.json
 # 5. the other BASELINE configs and variants on this GPU (bench lines only)
-python bench.py --no-cpu-baseline --config c3 --steps 10 --warmup 3 > $OUT/bench_c3.json 2>> $OUT/bench.err
-python bench.py --no-cpu-baseline --config c4 --steps 5 --warmup 2 > $OUT/bench_c4.json 2>> $OUT/bench.err
-GSASR_SPLAT_BWD=tile python bench.py --no-cpu-baseline --config c4 --steps 5 --warmup 2 > $OUT/bench_c4_tile_bwd.json 2>> $OUT/bench.err
-GSASR_SPLAT_BWD=gaussian python bench.py --no-cpu-baseline --config c4 --steps 5 --warmup 2 > $OUT/bench_c4_gaussian_bwd.json 2>> $OUT/bench.err
-GSASR_SPLAT_BWD=tile python bench.py --no-cpu-baseline --no-extras > $OUT/bench_c2_tile_bwd.json 2>> $OUT/bench.err
-python bench.py --no-cpu-baseline --no-extras --dmax 0.5 > $OUT/bench_c2_dmax0p5.json 2>> $OUT/bench.err
-python bench.py --no-cpu-baseline --no-extras --dmax -1 > $OUT/bench_c2_unbounded.json 2>> $OUT/bench.err
-python bench.py --no-cpu-baseline --no-extras --cutoff 104 > $OUT/bench_c2_tau104.json 2>> $OUT/bench.err
-python bench.py --no-cpu-baseline --no-extras --cutoff -1 --steps 10 --warmup 3 > $OUT/bench_c2_nocull.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --config c3 --steps 10 --warmup 3 > $OUT/bench_c3.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --config c4 --steps 5 --warmup 2 > $OUT/bench_c4.json 2>> $OUT/bench.err
+GSASR_SPLAT_BWD=tile python bench.py --full --no-cpu-baseline --config c4 --steps 5 --warmup 2 > $OUT/bench_c4_tile_bwd.json 2>> $OUT/bench.err
+GSASR_SPLAT_BWD=gaussian python bench.py --full --no-cpu-baseline --config c4 --steps 5 --warmup 2 > $OUT/bench_c4_gaussian_bwd.json 2>> $OUT/bench.err
+GSASR_SPLAT_BWD=tile python bench.py --full --no-cpu-baseline --no-extras > $OUT/bench_c2_tile_bwd.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --no-extras --dmax 0.5 > $OUT/bench_c2_dmax0p5.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --no-extras --dmax -1 > $OUT/bench_c2_unbounded.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --no-extras --cutoff 104 > $OUT/bench_c2_tau104.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --no-extras --cutoff -1 --steps 10 --warmup 3 > $OUT/bench_c2_nocull.json 2>> $OUT/bench.err
 python tools/e2e_time.py > $OUT/e2e_time.txt 2>&1
 for f in $OUT/bench_c*.json; do echo $f; python -c "import json,sys; d=json.loads(open('$f').read().strip().splitlines()[-1]); print(round(d['value'],1), round(d['ms_per_step'],4), {k:round(v['avg_ms']*1e3,1) for k,v in d['kernels'].items()})"; done
 cat $OUT/e2e_time.txt | grep fused
-python bench.py --no-cpu-baseline --config c5 > $OUT/bench_c5.json 2>> $OUT/bench.err
-python bench.py --config c5e2e --steps 20 --warmup 5 > $OUT/bench_c5e2e.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --config c5 > $OUT/bench_c5.json 2>> $OUT/bench.err
+python bench.py --full --config c5e2e --steps 20 --warmup 5 > $OUT/bench_c5e2e.json 2>> $OUT/bench.err
 python tools/e2e_batch_time.py > $OUT/e2e_batch_time.txt 2>&1
 tail -c 400 $OUT/bench_c5.json; tail -2 $OUT/e2e_batch_time.txt
 # 6. the sampled-pixel path: bench line, host-API timing, per-kernel device times
-python bench.py --no-cpu-baseline --config c5s > $OUT/bench_c5s.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --config c5s > $OUT/bench_c5s.json 2>> $OUT/bench.err
 python tools/sample_time.py > $OUT/sample_time.txt 2>&1
 tail -c 600 $OUT/bench_c5s.json; cat $OUT/sample_time.txt | tail -7
 # 7. multi-rank code path self-test at world size 1 (RCCL init, band exchange with itself)
-python bench.py --no-cpu-baseline --force-dist --steps 10 --warmup 3 > $OUT/bench_force_dist.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --force-dist --steps 10 --warmup 3 > $OUT/bench_force_dist.json 2>> $OUT/bench.err
 tail -c 700 $OUT/bench_force_dist.json
 # 8. host path: the reference's calling convention and PyTorch's own floor under it; gradient error vs conditioning
 python tools/dropin_profile.py > $OUT/dropin_profile.txt 2>&1
 python tools/autograd_floor.py > $OUT/autograd_floor.txt 2>&1
 python tools/rho_conditioning.py > $OUT/rho_conditioning.txt 2>&1
-python bench.py --no-cpu-baseline --config c2x16 > $OUT/bench_c2x16.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --config c2x16 > $OUT/bench_c2x16.json 2>> $OUT/bench.err
 cat $OUT/dropin_profile.txt $OUT/autograd_floor.txt | grep -v amdgpu.ids
 
 # 9. round 5: the reference's published workload, the tile lists against the search, what-if builds, hipGraph replay against eager
@@ -104,9 +104,9 @@ done
 pass pmc_sq_published "$sq" python $R/tools/published_run.py --cutoff 0 --calls 3
 cd $R
 for cfg in c2 c2x16 c5; do
-  python bench.py --no-cpu-baseline --no-extras --no-live-pmc --no-graph --config $cfg > $OUT/bench_${cfg}_default.json 2>> $OUT/bench.err
-  GSASR_SPLAT_LISTS=0 python bench.py --no-cpu-baseline --no-extras --no-live-pmc --no-graph --config $cfg > $OUT/bench_${cfg}_search.json 2>> $OUT/bench.err
-  GSASR_SPLAT_LISTS=1 python bench.py --no-cpu-baseline --no-extras --no-live-pmc --no-graph --config $cfg > $OUT/bench_${cfg}_lists.json 2>> $OUT/bench.err
+  python bench.py --full --no-cpu-baseline --no-extras --no-live-pmc --no-graph --config $cfg > $OUT/bench_${cfg}_default.json 2>> $OUT/bench.err
+  GSASR_SPLAT_LISTS=0 python bench.py --full --no-cpu-baseline --no-extras --no-live-pmc --no-graph --config $cfg > $OUT/bench_${cfg}_search.json 2>> $OUT/bench.err
+  GSASR_SPLAT_LISTS=1 python bench.py --full --no-cpu-baseline --no-extras --no-live-pmc --no-graph --config $cfg > $OUT/bench_${cfg}_lists.json 2>> $OUT/bench.err
 done
 for f in $OUT/bench_c*_default.json $OUT/bench_c*_search.json $OUT/bench_c*_lists.json; do echo -n "$(basename $f) "; python -c "import json,sys; d=json.loads(open('$f').read().strip().splitlines()[-1]); print(round(d['value'],1), round(d['ms_per_step'],4), {k:round(v['avg_ms']*1e3,1) for k,v in d['kernels'].items()})"; done > $OUT/lists_ab.txt
 cat $OUT/lists_ab.txt
