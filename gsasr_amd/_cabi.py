@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -192,41 +193,52 @@ class _WorkspacePool:
     zeroes the per-cell counters of the OTHER parity on the side (GSASR_FLAG_COUNTERS_CLEAN / GSASR_FLAG_PARITY), so a
     workspace that comes back from a finished step is clean for the flipped parity.  Keyed by (device, stream, size):
     reuse is ordered by the stream, exactly like the caching allocator's own reuse.  Bounded: a few workspaces per
-    key, MAX_BYTES in all (least recently used keys go first -- training on ragged sizes meets many sizes)."""
+    key, MAX_BYTES in all (least recently used keys go first -- training on ragged sizes meets many sizes).  Thread-safe:
+    `Plan.__del__` gives workspaces back from whichever thread drops the last reference (the autograd engine's among them)
+    while another thread takes one for its next plan."""
     KEEP = 4                    # free workspaces kept per key (forward and backward of a few steps in flight)
     MAX_BYTES = 2 << 30
 
     def __init__(self):
         self.free = {}          # key -> [(tensor, parity)]; dict order = least recently used first
         self.bytes = 0
+        self.lock = threading.Lock()
 
     def take(self, key, nbytes, dev):
-        lst = self.free.get(key)
-        if lst:
-            ws, parity = lst.pop()
-            self.bytes -= ws.numel()
+        with self.lock:
+            lst = self.free.get(key)
             if lst:
-                self.free[key] = self.free.pop(key)     # most recently used
-            else:
-                del self.free[key]
-            return ws, parity, True
+                ws, parity = lst.pop()
+                self.bytes -= ws.numel()
+                if lst:
+                    self.free[key] = self.free.pop(key)     # most recently used
+                else:
+                    del self.free[key]
+                return ws, parity, True
         return torch.empty(nbytes, dtype=torch.uint8, device=dev), 0, False
 
     def give(self, key, ws, parity):
-        lst = self.free.pop(key, [])
-        if len(lst) < self.KEEP and ws.numel() <= self.MAX_BYTES:
-            lst.append((ws, parity))
-            self.bytes += ws.numel()
-        if lst:
-            self.free[key] = lst
-        while self.bytes > self.MAX_BYTES and self.free:
-            old = next(iter(self.free))
-            for t, _ in self.free.pop(old):
-                self.bytes -= t.numel()
+        dropped = []            # (freed outside the lock: a tensor's destructor may run arbitrary code)
+        with self.lock:
+            lst = self.free.pop(key, [])
+            if len(lst) < self.KEEP and ws.numel() <= self.MAX_BYTES:
+                lst.append((ws, parity))
+                self.bytes += ws.numel()
+            if lst:
+                self.free[key] = lst
+            while self.bytes > self.MAX_BYTES and self.free:
+                old = next(iter(self.free))
+                for t, _ in self.free.pop(old):
+                    self.bytes -= t.numel()
+                    dropped.append(t)
+        del dropped
 
     def clear(self):
-        self.free.clear()
-        self.bytes = 0
+        with self.lock:
+            dropped = list(self.free.values())
+            self.free.clear()
+            self.bytes = 0
+        del dropped
 
 
 _POOL = _WorkspacePool()

@@ -180,8 +180,9 @@ public:
 // image [3,H,W] (or [B,3,slot,W]) and back, one C call each way (prologue + plan + splat; splat backward + chain rule).  What
 // `generate_2D_gaussian_splatting_step` -- the function the reference's training loop calls per sample
 // (basicsr/models/gsasr_model.py:191-233) -- costs on the host is this node.
+// (the same set as gsasr_amd._cabi._LAYOUT_FLAGS: the two pools agree on what counts as a layout)
 constexpr unsigned LAYOUT_FLAGS = GSASR_FLAG_FORWARD_ONLY | GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_ATOMIC |
-                                  GSASR_FLAG_CHW_GRAD | GSASR_FLAG_STRIDE8;
+                                  GSASR_FLAG_BWD_HOME | GSASR_FLAG_CHW_GRAD | GSASR_FLAG_STRIDE8;
 
 class StepNode : public torch::autograd::Function<StepNode> {
 public:
@@ -305,6 +306,17 @@ void bind(int64_t plan, int64_t fwd, int64_t bwd, int64_t bytes, int64_t err)
     p_err = (err_fn)err;
 }
 
+int64_t layout_flags() { return (int64_t)LAYOUT_FLAGS; }
+
+// the pooled workspaces' keys {bytes, s, h, w, layout, batch, slot} (tests)
+std::vector<std::vector<int64_t>> pool_keys()
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    std::vector<std::vector<int64_t>> out;
+    for (const Pooled &e : g_pool) out.push_back({e.bytes, e.s, e.h, e.w, (int64_t)e.layout, e.batch, e.slot});
+    return out;
+}
+
 void clear_pool()
 {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -320,4 +332,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("bind_step", &bind_step, "hand over gsasr_step_workspace_bytes / _forward / _forward_sm / _backward");
     m.def("step_apply", &step_apply, "the fused step (prologue + plan + splat, and back) as a C++ autograd node");
     m.def("clear_pool", &clear_pool, "drop the pooled plan workspaces");
+    m.def("layout_flags", &layout_flags, "the gsasr_dims flags that make a pooled workspace's layout (its pool key)");
+    m.def("pool_keys", &pool_keys, "keys of the pooled plan workspaces: [bytes, s, h, w, layout, batch, slot] each");
 }

@@ -2,6 +2,9 @@
 // (one translation unit of libgsasr_splat.so; gsasr_splat.hip has the overview of the whole pipeline)
 #include "splat_common.h"
 
+#include <algorithm>
+#include <map>
+
 using namespace gsasr_detail;
 
 namespace gsasr_detail {
@@ -60,22 +63,50 @@ KernelChoice registered_choice(const gsasr_dims *d)
 
 // Which plans carry slots.  The slot count of a workspace follows from the flags of the dims the PLAN was made with; a
 // backward (or the gather of a step call) that derives it from its OWN flags would, when the two disagree, read slots and
-// spans the plan never wrote.  The plan therefore leaves a note {workspace -> slots per Gaussian} here and every later
-// call on that workspace lays it out from the note (a small direct-mapped table: a lost note only means the old
-// behaviour, trusting the caller's flags).
-// One 64-bit word per note, written and read atomically (no lock on the plan / forward / backward path): the workspace
-// address (256-byte aligned: bits 8..47), a 16-bit hash of the shape the plan was made for, and the slot count.  A note
-// whose shape hash differs from the caller's dims -- a freed workspace address reused for another shape without a new plan,
-// a note overwritten by a colliding workspace -- is ignored.
+// spans the plan never wrote.  The plan therefore leaves a note {workspace -> slots per Gaussian, tile lists} here and every
+// later call on that workspace lays it out from the note.  The notes are lossless: a direct-mapped table of 1024 entries
+// (one atomic load on the forward / backward path) in front of an overflow map that takes every note a colliding workspace
+// pushes out of its entry.  A call whose workspace has no note for its shape -- never planned, planned for another shape,
+// or its memory since taken over by another plan -- fails with GSASR_ERR_PLAN: the layout is never re-derived from the
+// caller's flags or the registry of the moment (a kernel choice registered, switched or cleared since the plan would move
+// slots, lists and the step scratch behind them).
+// Two 64-bit words per note: the workspace address (256-byte aligned: bits 8..47) with a 16-bit hash of the shape the plan
+// was made for and the slot / list-height byte; and the address again with the capacity of the plan's tile lists (the
+// stride of tl_entries).  The capacity follows from gsasr_dims.list_cap OR from the kernel choice registered for the shape
+// at PLAN time; a forward / backward that re-derived it from the registry would, after a tune() / reset between the plan and
+// the render, read the lists with another stride than k_bin wrote them with.
 constexpr int NOTES = 1024;
 static std::atomic<unsigned long long> g_notes[NOTES];
-// ... and a second word per note: the capacity of the plan's tile lists (the stride of tl_entries), tagged with the same shape
-// hash.  The capacity follows from gsasr_dims.list_cap OR from the kernel choice registered for the shape at PLAN time; a
-// forward / backward that re-derived it from the registry would, after a tune() / reset between the plan and the render, read
-// the lists with another stride than k_bin wrote them with.  The plan's value is frozen here instead.
 static std::atomic<unsigned long long> g_note_caps[NOTES];
+// overflow: address -> the two words, for notes pushed out of their direct-mapped entry.  Written by plans only (under
+// g_note_mu, which also orders the plans' updates of the direct table); read under it by the calls that miss the table.
+// Bounded: past NOTES_OVER_MAX entries the oldest sixteenth goes (an entry otherwise leaves only when a later plan's bytes
+// cover its address -- freed workspaces of a long run on ragged sizes); a call on a workspace whose note went that way fails
+// with GSASR_ERR_PLAN, never guesses.  It takes more than 65 000 workspaces planned since, all displaced, to reach a live one.
+struct OverNote { unsigned long long w, c, seq; };
+static std::mutex g_note_mu;
+static std::map<uintptr_t, OverNote> g_note_over;
+static unsigned long long g_note_seq = 0;
+static std::atomic<size_t> g_note_over_n{0};
+constexpr size_t NOTES_OVER_MAX = 1u << 16;
+
+static void drop_oldest_notes()
+{
+    std::vector<unsigned long long> seqs;
+    seqs.reserve(g_note_over.size());
+    for (const auto &e : g_note_over) seqs.push_back(e.second.seq);
+    auto cut = seqs.begin() + (long)(seqs.size() / 16);
+    std::nth_element(seqs.begin(), cut, seqs.end());
+    const unsigned long long limit = *cut;
+    for (auto it = g_note_over.begin(); it != g_note_over.end();)
+        it = it->second.seq < limit ? g_note_over.erase(it) : std::next(it);
+}
 
 static unsigned note_slot(const void *ws) { return (unsigned)(((uintptr_t)ws >> 8) * 2654435761u >> 22) & (NOTES - 1); }
+
+// (bits 24..63 of both words: bits 8..47 of the workspace address)
+constexpr unsigned long long ADDR_MASK = ~0xffffffull;
+static unsigned long long note_addr(const void *ws) { return ((unsigned long long)(uintptr_t)ws & 0x0000ffffffffff00ull) << 16; }
 
 static unsigned long long note_shape(const gsasr_dims *d)
 {
@@ -85,38 +116,73 @@ static unsigned long long note_shape(const gsasr_dims *d)
     return (x >> 40) & 0xffffull;
 }
 
-// (payload byte: slots per Gaussian in bits 0..4, the tile lists' tile height in bits 5..6: 0 none, 1 = 16 rows, 2 = 32)
-void note_plan(const void *ws, const gsasr_dims *d, int part_k, int tl_hlog, int tl_cap)
+// (payload byte: slots per Gaussian in bits 0..4, the tile lists' tile height in bits 5..6: 0 none, 1 = 16 rows, 2 = 32;
+// the capacity word: the capacity (<= 65536) in bits 0..23)
+void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap)
 {
+    const unsigned long long a = note_addr(ws);
+    const unsigned long long w = a | note_shape(d) << 8 | (unsigned long long)((part_k & 0x1f) | (tl_hlog ? (tl_hlog - 3) << 5 : 0));
+    const unsigned long long c = a | ((unsigned long long)(unsigned)tl_cap & 0xffffffull);
+    const unsigned i = note_slot(ws);
+    std::lock_guard<std::mutex> lk(g_note_mu);
+    const unsigned long long old = g_notes[i].load(std::memory_order_relaxed);
+    if (old != 0ull && (old & ADDR_MASK) != a) {
+        // another workspace's note leaves the table: into the overflow map FIRST, so that a reader that sees the new entry
+        // finds the old one there
+        if (g_note_over.size() >= NOTES_OVER_MAX) drop_oldest_notes();
+        g_note_over[(uintptr_t)((old >> 16) & 0x0000ffffffffff00ull)] = {old, g_note_caps[i].load(std::memory_order_relaxed), ++g_note_seq};
+    }
+    if (!g_note_over.empty()) {
+        // this plan's bytes belong to this workspace now: no other workspace starts inside them (nor at their first byte:
+        // this note lives in the table)
+        const uintptr_t lo = (uintptr_t)ws, hi = lo + (plan_bytes > 0 ? plan_bytes : 1);
+        g_note_over.erase(g_note_over.lower_bound(lo), g_note_over.lower_bound(hi));
+    }
+    g_note_over_n.store(g_note_over.size(), std::memory_order_relaxed);
     // (the capacity first: a reader that sees the new first word also sees a capacity of the same plan or a newer one of the
-    // same workspace and shape -- concurrent plans on ONE workspace are the caller's race either way)
-    g_note_caps[note_slot(ws)].store((note_shape(d) << 32) | (unsigned long long)(unsigned)tl_cap, std::memory_order_release);
-    const unsigned long long w = ((unsigned long long)(uintptr_t)ws & 0x0000ffffffffff00ull) << 16 | note_shape(d) << 8 |
-                                 (unsigned long long)((part_k & 0x1f) | (tl_hlog ? (tl_hlog - 3) << 5 : 0));
-    g_notes[note_slot(ws)].store(w, std::memory_order_release);
+    // same workspace -- concurrent plans on ONE workspace are the caller's race either way)
+    g_note_caps[i].store(c, std::memory_order_release);
+    g_notes[i].store(w, std::memory_order_release);
 }
 
-// layout of the plan in `ws`: from the note its plan left, else from these dims -- except the tile lists, which a call uses
-// only on the note's word (a lost note means the search, never a list nobody wrote)
-Layout plan_layout(const gsasr_dims *d, const void *ws)
+// layout of the plan in `ws` from the note its plan left; *noted = false (and the layout of these dims, which nothing may
+// use but for its size) when there is no note of this shape for `ws`
+Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted)
 {
     int part_k = -1, tl_hlog = -1, tl_cap = -1;
-    bool cap_lost = false;
+    bool found = false;
     if (ws) {
-        const unsigned long long w = g_notes[note_slot(ws)].load(std::memory_order_acquire);
-        const unsigned long long key = ((unsigned long long)(uintptr_t)ws & 0x0000ffffffffff00ull) << 16 | note_shape(d) << 8;
-        if ((w & ~0xffull) == key) {
+        const unsigned long long a = note_addr(ws), key = a | note_shape(d) << 8;
+        const unsigned i = note_slot(ws);
+        unsigned long long w = g_notes[i].load(std::memory_order_acquire), c = 0ull;
+        if ((w & ADDR_MASK) == a) c = g_note_caps[i].load(std::memory_order_acquire);
+        // lock-free hit: both words of this workspace.  Otherwise (the note is in the overflow map, or a plan of a colliding
+        // workspace replaced the entry between the two loads) both are read again under the plans' lock, where they agree
+        if ((w & ADDR_MASK) != a || (c & ADDR_MASK) != a) {
+            w = c = 0ull;
+            if ((g_notes[i].load(std::memory_order_relaxed) & ADDR_MASK) == a || g_note_over_n.load(std::memory_order_relaxed) != 0) {
+                std::lock_guard<std::mutex> lk(g_note_mu);
+                w = g_notes[i].load(std::memory_order_relaxed);
+                if ((w & ADDR_MASK) == a) {
+                    c = g_note_caps[i].load(std::memory_order_relaxed);
+                } else {
+                    const auto it = g_note_over.find((uintptr_t)ws & 0x0000ffffffffff00ull);
+                    w = it != g_note_over.end() ? it->second.w : 0ull;
+                    c = it != g_note_over.end() ? it->second.c : 0ull;
+                }
+            }
+        }
+        // (a capacity word of another workspace never passes: no list region sized by a guessed capacity)
+        found = (w & ~0xffull) == key && (c & ADDR_MASK) == a;
+        if (found) {
             part_k = (int)(w & 0x1full);
             tl_hlog = (int)((w >> 5) & 3ull) ? (int)((w >> 5) & 3ull) + 3 : 0;
-            const unsigned long long c = g_note_caps[note_slot(ws)].load(std::memory_order_acquire);
-            if ((c >> 32) == note_shape(d)) tl_cap = (int)(unsigned)(c & 0xffffffffull);
-            else cap_lost = true;  // (the capacity word belongs to another plan: the lists are not read -- never with a guessed stride)
+            tl_cap = (int)(c & 0xffffffull);
         }
     }
-    // (without a note the list region is still SIZED from the dims -- the step entry points place their scratch behind the
-    // plan -- but nothing reads it)
+    if (noted) *noted = found;
     Layout L = make_layout(d, part_k, tl_hlog, tl_cap);
-    if (tl_hlog < 0 || cap_lost) L.tl_ok = false;
+    if (!found) L.tl_ok = false;
     return L;
 }
 
@@ -148,8 +214,10 @@ int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L,
     } else if (dims->batch <= 1 && dims->grad_rows != 0 && dims->grad_rows != dims->row1 - dims->row0) {
         return fail(GSASR_ERR_ARG, "grad_rows applies to a batched canvas only (leave it 0)");
     }
-    L = planning ? make_layout(dims) : plan_layout(dims, ws);
+    bool noted = true;
+    L = planning ? make_layout(dims) : plan_layout(dims, ws, &noted);
     if (!ws || ((uintptr_t)ws & 255u)) return fail(GSASR_ERR_WORKSPACE, "workspace null or not 256-byte aligned");
+    if (!noted) return fail(GSASR_ERR_PLAN, "the workspace holds no plan of these dims (plan it, or re-plan it, first)");
     if (ws_bytes < L.total) return fail(GSASR_ERR_WORKSPACE, "workspace smaller than gsasr_splat_workspace_bytes()");
     return GSASR_OK;
 }

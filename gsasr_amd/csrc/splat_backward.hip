@@ -639,6 +639,11 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
     if (gather && (!g_sigmas || !g_coords || !g_colors)) return fail(GSASR_ERR_ARG, "null pointer");
     if (mode == 0 && (dims->flags & GSASR_FLAG_CHW_GRAD))
         return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward");
+    if (mode == 2 && (dims->flags & GSASR_FLAG_CHW_GRAD) && !(dims->flags & (GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_ATOMIC)) &&
+        (registered_choice(dims).flags & (GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_HOME)))
+        // (a planar gradient on a plan without slots leaves only the atomic kernel: not when the shape's registered choice names a
+        // kernel that reads interleaved gradients -- the choice would be dropped for an order-dependent one without a word)
+        return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward (the kernel registered for this shape reads [rows, w, 3])");
     hipStream_t st = (hipStream_t)stream;
     const Params P = make_params(dims, L);
     const PlanView V = make_view(L, const_cast<void *>(workspace));
@@ -753,6 +758,10 @@ int gsasr_splat_backward(const float *sigmas, const float *coords, const float *
                          float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
                          const void *workspace, size_t workspace_bytes, void *stream)
 {
+    // (the home-tile kernel sweeps interleaved gradients: a planar one would otherwise quietly go to the order-dependent atomic
+    // kernel -- the step entry points interleave it first, this one does not)
+    if (dims && (dims->flags & GSASR_FLAG_BWD_HOME) && (dims->flags & GSASR_FLAG_CHW_GRAD))
+        return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward (GSASR_FLAG_BWD_HOME reads [rows, w, 3])");
     return splat_backward(sigmas, coords, colors, grad_img, g_sigmas, g_coords, g_colors, dims, workspace, workspace_bytes,
                           stream, true, nullptr);
 }

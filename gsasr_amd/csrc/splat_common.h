@@ -605,8 +605,10 @@ inline Params make_params(const gsasr_dims *d, const Layout &L)
 }
 
 // ---- plan notes (splat_api.hip) ----
-void note_plan(const void *ws, const gsasr_dims *d, int part_k, int tl_hlog, int tl_cap);
-Layout plan_layout(const gsasr_dims *d, const void *ws);     // layout of the plan in `ws`: from the note its plan left, else from these dims
+void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap);
+// layout of the plan in `ws`, from the note its plan left; *noted = false when `ws` holds no plan of these dims (the layout is
+// then the dims' own, for its size only)
+Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted = nullptr);
 int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning = false);
 
 #define HIP_TRY(expr)                                    \
@@ -956,7 +958,7 @@ int launch_bwd_home(const Params &P, const PlanView &V, const float *grad_img, f
 struct StepLayout {
     size_t plan_bytes, off_step, off_sig, off_xy, off_col, off_gsig, off_gxy, off_gcol, off_ghwc, total;
 };
-StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws = nullptr);
+StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws = nullptr, bool *noted = nullptr);
 int step_prologue_plan(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims, void *workspace,
                        size_t workspace_bytes, void *stream, StepLayout &S);
 int prologue_backward_batched(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,

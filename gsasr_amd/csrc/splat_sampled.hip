@@ -597,9 +597,11 @@ int gsasr_step_sample_backward(const float *gs_parameters, const float *step_siz
     gsasr_dims dn = *dims;      // (the layout the sampled forward planned with: no tile lists)
     dn.list_cap = -1;
     dims = &dn;
-    const StepLayout S = make_step_layout(dims, workspace);
+    bool noted = false;
+    const StepLayout S = make_step_layout(dims, workspace, &noted);
     if (!workspace || ((uintptr_t)workspace & 255u) || workspace_bytes < S.total)
         return fail(GSASR_ERR_WORKSPACE, "workspace null, misaligned or smaller than gsasr_step_workspace_bytes()");
+    if (!noted) return fail(GSASR_ERR_PLAN, "the workspace holds no step forward of these dims (run it, or run it again, first)");
     char *b = (char *)workspace;
     float *sig = (float *)(b + S.off_sig), *xy = (float *)(b + S.off_xy), *col = (float *)(b + S.off_col);
     float *gs = (float *)(b + S.off_gsig), *gc = (float *)(b + S.off_gxy), *gk = (float *)(b + S.off_gcol);

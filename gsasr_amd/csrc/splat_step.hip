@@ -142,11 +142,13 @@ int gsasr_prologue_backward(const float *gs_parameters, const float *step_size, 
 }  // extern "C"
 
 namespace gsasr_detail {
-StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws)
+StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws, bool *noted)
 {
     StepLayout S;
     const size_t n = (size_t)d->s;
-    S.plan_bytes = (planned_ws ? plan_layout(d, planned_ws) : make_layout(d)).total;   // (the plan's own slot count: plan_layout)
+    // (the plan's own slot count and lists: plan_layout -- the scratch behind them stays where the step's plan put it, whatever
+    // the registry holds now)
+    S.plan_bytes = (planned_ws ? plan_layout(d, planned_ws, noted) : make_layout(d)).total;
     size_t o = S.plan_bytes;
     S.off_step = o; o += align_up(GSASR_MAX_BATCH * 4, 256);   // the step size of every sample, as the prologue used it
     S.off_sig = o;  o += align_up(n * 12, 256);
@@ -246,9 +248,11 @@ int gsasr_step_backward(const float *gs_parameters, const float *step_size, cons
 {
     if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims");
     if (dims->flags & GSASR_FLAG_STRIDE8) return fail(GSASR_ERR_ARG, "GSASR_FLAG_STRIDE8 does not apply to the step entry points");
-    const StepLayout S = make_step_layout(dims, workspace);
+    bool noted = false;
+    const StepLayout S = make_step_layout(dims, workspace, &noted);
     if (!workspace || ((uintptr_t)workspace & 255u) || workspace_bytes < S.total)
         return fail(GSASR_ERR_WORKSPACE, "workspace null, misaligned or smaller than gsasr_step_workspace_bytes()");
+    if (!noted) return fail(GSASR_ERR_PLAN, "the workspace holds no step forward of these dims (run it, or run it again, first)");
     char *b = (char *)workspace;
     float *sig = (float *)(b + S.off_sig), *xy = (float *)(b + S.off_xy), *col = (float *)(b + S.off_col);
     float *gs = (float *)(b + S.off_gsig), *gc = (float *)(b + S.off_gxy), *gk = (float *)(b + S.off_gcol);

@@ -178,12 +178,14 @@ def _tune_on_device(sigmas, coords, colors, h, w, dmax, backward, rows, cutoff, 
     return res
 
 
-def _fused_candidates(s: int, w: int, rows: int, default_tile: bool):
+def _fused_candidates(s: int, w: int, rows: int, default_kernel: int):
     """backward kernel x lists for the fused entry points (their forward is the 8 x 16 kernel or, on single images, the library's
-    own choice): the first entry is what gsasr_amd.gaussian_splatting does untuned"""
+    own choice): the first entry is what gsasr_amd.gaussian_splatting does untuned -- `default_kernel` is the flag its rule
+    (`_backward_kernel` without a registration) picks, so that "default" winning and being registered as flags 0 means the
+    kernel that was measured"""
     T, G, Hm = _cabi.FLAG_BWD_TILE, _cabi.FLAG_BWD_GAUSSIAN, _cabi.FLAG_BWD_HOME
     cap = default_list_capacity(s, w, rows, False)
-    return [("default", T if default_tile else G, 0), ("gaussian-search", G, -1), ("gaussian-lists", G, cap),
+    return [("default", int(default_kernel), 0), ("gaussian-search", G, -1), ("gaussian-lists", G, cap),
             ("tile-search", T, -1), ("tile-lists", T, cap), ("home-search", Hm, -1), ("home-lists", Hm, cap)]
 
 
@@ -214,7 +216,7 @@ def tune_batch(gs_parameters: torch.Tensor, steps: torch.Tensor, sizes, dmax: Op
     """The batched training step (`generate_2D_gaussian_splatting_batch`: `gs_parameters[B,N,9]`, per-sample step sizes and
     `(h, w)`): time prologue + plan + forward + backward for {Gaussian-, tile-stationary backward} x {lists, search} on THIS
     batch and register the winner for the canvas shape; the fused host path follows the registration from then on."""
-    from .gaussian_splatting import _tile_backward
+    from .gaussian_splatting import _backward_kernel
     if not gs_parameters.is_cuda or torch.cuda.is_current_stream_capturing():
         raise RuntimeError("tune_batch() measures on the GPU, outside stream capture")
     B, n = gs_parameters.shape[0], gs_parameters.shape[1]
@@ -227,14 +229,14 @@ def tune_batch(gs_parameters: torch.Tensor, steps: torch.Tensor, sizes, dmax: Op
         _, plan = _cabi.batch_forward(gp, steps, sizes, dmax, _cabi.FLAG_CHW_GRAD | flags)
         _cabi.batch_backward(plan, gp, None, grad, chw=True)
 
-    default_tile = _tile_backward(sum(h * w for h, w in sizes), B * n)
-    return _tune_fused(shape, _fused_candidates(B * n, w_max, shape.slot * B, default_tile), run, iters, rounds, register)
+    default_kernel = _backward_kernel(sum(h * w for h, w in sizes), B * n)
+    return _tune_fused(shape, _fused_candidates(B * n, w_max, shape.slot * B, default_kernel), run, iters, rounds, register)
 
 
 def tune_step(gs_parameters: torch.Tensor, step: torch.Tensor, h: int, w: int, dmax: Optional[float], *, iters: int = 3,
               rounds: int = 3, register: bool = True) -> TuneResult:
     """The fused single-image step (`generate_2D_gaussian_splatting_step` on raw decoder output `[N,9]`): as `tune_batch`."""
-    from .gaussian_splatting import _tile_backward
+    from .gaussian_splatting import _backward_kernel
     if not gs_parameters.is_cuda or torch.cuda.is_current_stream_capturing():
         raise RuntimeError("tune_step() measures on the GPU, outside stream capture")
     n = gs_parameters.shape[0]
@@ -246,7 +248,7 @@ def tune_step(gs_parameters: torch.Tensor, step: torch.Tensor, h: int, w: int, d
         _, plan = _cabi.step_forward(gp, step, h, w, dmax, _cabi.FLAG_CHW_GRAD | flags)
         _cabi.step_backward(plan, gp, None, grad, chw=True)
 
-    return _tune_fused(shape, _fused_candidates(n, w, h, _tile_backward(h * w, n)), run, iters, rounds, register)
+    return _tune_fused(shape, _fused_candidates(n, w, h, _backward_kernel(h * w, n)), run, iters, rounds, register)
 
 
 def autotune_hook(sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tensor, h: int, w: int, dmax: Optional[float],

@@ -50,7 +50,10 @@ enum gsasr_status {
     GSASR_OK = 0,
     GSASR_ERR_ARG = -1,        /* bad dims / null pointer / c != 3 */
     GSASR_ERR_WORKSPACE = -2,  /* workspace too small or misaligned */
-    GSASR_ERR_PLAN = -3        /* workspace does not hold a plan for these dims */
+    GSASR_ERR_PLAN = -3        /* workspace does not hold a plan for these dims: the library keeps what each plan decided
+                                  about its workspace's layout (slots, tile lists) per workspace address, losslessly, and a
+                                  forward / backward on an address it holds no plan of this shape for is refused -- never
+                                  laid out from the kernel choice registered at the time of the call.  Re-plan. */
 };
 
 /* flags */
@@ -88,7 +91,11 @@ enum gsasr_status {
                                          (items of 8 x 8 px per lane, added in LDS, one write per Gaussian): no slots, no gather, no
                                          atomics, deterministic.  Needs nothing from the plan beyond what the Gaussian-stationary
                                          kernel reads; a Gaussian whose window does not fit the region is swept by a whole wave
-                                         (that kernel's code), so any input stays correct.  Interleaved [rows, w, 3] gradients.
+                                         (that kernel's code), so any input stays correct.  Interleaved [rows, w, 3] gradients:
+                                         with GSASR_FLAG_CHW_GRAD gsasr_splat_backward returns GSASR_ERR_ARG, as it does
+                                         when this kernel or the Gaussian-stationary one is the shape's registered choice
+                                         and the plan has no slots (the step backwards interleave a planar gradient first
+                                         and run the chosen kernel on it).
                                          The default of whole images and batched canvases denser than one Gaussian per two pixels on
                                          at least 1024 tiles of 32 x 16 px (1024^2 at GSASR's 16 per LR pixel: -8..-9% against the
                                          Gaussian-stationary kernel) */
@@ -350,7 +357,9 @@ GSASR_API int gsasr_forward_subtile_width(const gsasr_dims *dims);
  *     flags    : any of GSASR_FLAG_FWD_WIDE | GSASR_FLAG_FWD_NARROW, GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_GAUSSIAN
  *     list_cap : as gsasr_dims.list_cap (0 = the library's rule, > 0 entries per tile, < 0 no lists).
  * Results are the same sums in another order.  Register BEFORE sizing workspaces for the shape (gsasr_splat_workspace_bytes
- * follows the registered choice; a workspace sized earlier may be too small and is refused, never overrun).  Process-wide,
+ * follows the registered choice; a workspace sized earlier may be too small and is refused, never overrun).  A workspace that
+ * has been planned keeps its plan's layout (slots, tile lists, the step scratch behind them) whatever is registered, switched or
+ * cleared afterwards: only the kernel its calls pick may follow the new choice.  Process-wide,
  * thread-safe; at most 256 shapes (GSASR_ERR_ARG beyond, or on flags outside the four above). */
 GSASR_API int gsasr_set_kernel_choice(const gsasr_dims *shape, unsigned flags, int list_cap);
 /* 1 and the registered values if `shape` has a registered choice, else 0 */
