@@ -29,6 +29,7 @@ EXPORTS = (
     "gsasr_step_sample_forward", "gsasr_step_sample_backward",
     "gsasr_step_forward_sm", "gsasr_step_sample_forward_sm", "gsasr_plan_cutoff", "gsasr_release_launcher_scratch", "gsasr_forward_subtile_width",
     "gsasr_set_kernel_choice", "gsasr_get_kernel_choice", "gsasr_clear_kernel_choices",
+    "gsasr_splat_forward_u8", "gsasr_step_forward_u8", "gsasr_step_forward_sm_u8",
 )
 
 FLAG_OVERWRITE_IMAGE = 2   # GSASR_FLAG_OVERWRITE_IMAGE
@@ -45,6 +46,7 @@ FLAG_COUNTERS_CLEAN = 1024 # GSASR_FLAG_COUNTERS_CLEAN
 FLAG_PARITY = 2048         # GSASR_FLAG_PARITY
 FLAG_CUTOFF_CAP = 4096     # GSASR_FLAG_CUTOFF_CAP
 FLAG_FWD_WIDE, FLAG_FWD_NARROW = 8192, 16384      # forward kernel choice (development A/B, tests): 16x16 / 8x16 sub-tiles
+U8_SWAP_RB = 1             # GSASR_U8_SWAP_RB (u8_flags of the 8-bit forwards)
 EXACT_CUTOFF = 104.0    # GSASR_SPLAT_EXACT_CUTOFF
 NO_CUTOFF = -1.0
 
@@ -132,6 +134,13 @@ def lib():
         L.gsasr_get_kernel_choice.restype = i
         L.gsasr_get_kernel_choice.argtypes = [dp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int)]
         L.gsasr_clear_kernel_choices.restype = None
+        u = ctypes.c_uint
+        L.gsasr_splat_forward_u8.restype = i
+        L.gsasr_splat_forward_u8.argtypes = [dp, vp, sz, vp, i, i, sz, u, vp]
+        L.gsasr_step_forward_u8.restype = i
+        L.gsasr_step_forward_u8.argtypes = [vp, vp, dp, vp, sz, vp, i, i, sz, u, vp]
+        L.gsasr_step_forward_sm_u8.restype = i
+        L.gsasr_step_forward_sm_u8.argtypes = [vp, vp, i, f, vp, dp, vp, sz, vp, i, i, sz, u, vp]
         if L.gsasr_abi_version() != 7:
             raise RuntimeError("libgsasr_splat.so ABI version mismatch")
         _lib = L
@@ -392,6 +401,48 @@ def forward(p: Plan, img: torch.Tensor, overwrite: bool = False, chw: bool = Fal
 def forward_subtile_width(p: Plan, flags: int = 0) -> int:
     """16 when `forward(p, ..., flags=flags)` runs the wide forward (16 x 16 sub-tiles), 8 for the 8 x 16 kernels"""
     return int(lib().gsasr_forward_subtile_width(ctypes.byref(_dims_with(p, flags & (FLAG_FWD_WIDE | FLAG_FWD_NARROW)))))
+
+
+# ---- 8-bit image output (include/gsasr_splat.h: gsasr_splat_forward_u8) ---------------------------------------------
+def _u8_target(d: Dims, crop, out: Optional[torch.Tensor], dev):
+    """(crop rows, crop columns, output tensor, pitch in bytes) of an 8-bit forward with dims `d`.  `crop` = (rows, columns) of
+    the grid's top-left corner (None: all of it).  The tensor is `[rows of the band inside the crop, columns, 3]` (batched
+    canvas: `[B, rows, columns, 3]`), fresh or the caller's `out`, whose row stride is the pitch."""
+    B = int(d.batch) if d.batch > 1 else 0
+    full_h, full_w = (d.slot if B else d.h), d.w
+    if B and crop is None:
+        full_h = max(d.sample_hw[2 * b] for b in range(B))
+    rows, cols = (full_h, full_w) if crop is None else (int(crop[0]), int(crop[1]))
+    if not (1 <= rows <= (d.slot if B else d.h) and 1 <= cols <= d.w):
+        raise RuntimeError(f"crop {(rows, cols)} must be at least 1 x 1 and at most the grid, {(d.slot if B else d.h, d.w)}")
+    n_rows = rows if B else min(d.row1, rows) - d.row0
+    if n_rows <= 0:
+        raise RuntimeError("the plan's row band lies outside the crop")
+    shape = (B, n_rows, cols, 3) if B else (n_rows, cols, 3)
+    if out is None:
+        return rows, cols, torch.empty(shape, dtype=torch.uint8, device=dev), 3 * cols
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.device == dev):
+        raise RuntimeError("out must be a uint8 CUDA tensor on the plan's device")
+    pitch = out.stride(-3)
+    if tuple(out.shape) != shape or out.stride(-1) != 1 or out.stride(-2) != 3 or pitch < 3 * cols or \
+            (B and out.stride(0) != n_rows * pitch):
+        raise RuntimeError(f"out must be {shape} with interleaved pixels (strides [pitch >= {3 * cols}, 3, 1]"
+                           + (", samples rows * pitch apart)" if B else ")") + f", got {tuple(out.shape)} / {out.stride()}")
+    return rows, cols, out, int(pitch)
+
+
+def forward_u8(p: Plan, crop=None, bgr: bool = False, out: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+    """The splat of plan `p` as an 8-bit image `[rows, cols, 3]` (batched canvas `[B, rows, cols, 3]`): per channel value
+    `rint(clamp(v, 0, 1) * 255)`, stored by the forward kernels themselves -- no float image exists.  `crop` = (rows, cols):
+    the top-left corner of the grid (the reference's `[:gt_h, :gt_w]`); `bgr`: bytes in b, g, r order; `out`: write into
+    the caller's uint8 tensor (its row stride is the pitch; bytes outside the pixels are left alone).  `flags`:
+    FLAG_FWD_WIDE / FLAG_FWD_NARROW, as for `forward`, which runs the same kernel for the same plan and flags."""
+    d = _dims_with(p, flags & (FLAG_FWD_WIDE | FLAG_FWD_NARROW))
+    with _on(p.device):
+        rows, cols, out, pitch = _u8_target(d, crop, out, p.device)
+        check(lib().gsasr_splat_forward_u8(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), out.data_ptr(), rows, cols,
+                                           pitch, U8_SWAP_RB if bgr else 0, _stream(p.device)), "gsasr_splat_forward_u8")
+    return out
 
 
 def backward(p: Plan, sigmas, coords, colors, grad_img, g_sigmas, g_coords, g_colors, overwrite: bool = False) -> None:
@@ -662,6 +713,44 @@ def step_forward(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: i
     return img, Plan(d, ws, dev, pool_key, parity)
 
 
+def _step_u8(d: Dims, pp: int, ps, sm, default_step_size: float, crop, bgr: bool, out, dev):
+    """prologue + plan + 8-bit forward with dims `d` (ps: pointer of the step sizes, or `sm` = (pointer, stride) of scale_modify)"""
+    L = lib()
+    nbytes = L.gsasr_step_workspace_bytes(ctypes.byref(d))
+    if nbytes == 0:
+        check(-1, "gsasr_step_workspace_bytes")
+    with _on(dev):
+        stream = _stream(dev)
+        rows, cols, out, pitch = _u8_target(d, crop, out, dev)
+        ws, pool_key, parity = _pooled_workspace(d, nbytes, dev)
+        tail = (ctypes.byref(d), ws.data_ptr(), nbytes, out.data_ptr(), rows, cols, pitch, U8_SWAP_RB if bgr else 0, stream)
+        if sm is None:
+            check(L.gsasr_step_forward_u8(pp, ps, *tail), "gsasr_step_forward_u8")
+        else:
+            check(L.gsasr_step_forward_sm_u8(pp, sm[0], sm[1], float(default_step_size), mismatch_flag(dev).data_ptr(), *tail),
+                  "gsasr_step_forward_sm_u8")
+    return out, Plan(d, ws, dev, pool_key, parity)
+
+
+def step_forward_u8(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
+                    crop=None, bgr: bool = False, out: Optional[torch.Tensor] = None, extra_flags: int = 0,
+                    scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+    """`step_forward` ending in the 8-bit store: raw `gs_parameters[N,9]` -> uint8 `[rows, cols, 3]` (see `forward_u8`) and
+    the plan, always FLAG_FORWARD_ONLY (an 8-bit image has no backward).  `extra_flags`: FLAG_FWD_WIDE / FLAG_FWD_NARROW."""
+    pp = _ptr3(gs_parameters, "gs_parameters", 9)
+    if gs_parameters.dim() != 2:
+        raise RuntimeError("gs_parameters must be [N,9]")
+    sm = ps = None
+    if scale_modify is None:
+        ps = _chk(step, "step_size")
+    else:
+        sm = _sm_ptr(scale_modify, 1)
+    if dmax is not None and not (float(dmax) >= 0.0):
+        raise RuntimeError("dmax must be >= 0")
+    d = make_dims(gs_parameters.shape[0], h, w, dmax, flags=FLAG_FORWARD_ONLY | int(extra_flags))
+    return _step_u8(d, pp, ps, sm, default_step_size, crop, bgr, out, gs_parameters.device)
+
+
 def step_backward(p: Plan, gs_parameters: torch.Tensor, step: Optional[torch.Tensor], grad: torch.Tensor, chw: bool = False) -> torch.Tensor:
     """splat backward + prologue backward in ONE call; `grad` is `[h,w,3]`, or with `chw` the planar `[3,h,w]` autograd
     hands back (tile-stationary backward, GSASR_FLAG_CHW_GRAD); returns d/d gs_parameters `[N,9]`.  `step=None`: the step
@@ -731,6 +820,28 @@ def batch_forward(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], si
                                           ctypes.byref(d), ws.data_ptr(), nbytes, img.data_ptr(), stream),
                   "gsasr_step_forward_sm")
     return img, Plan(d, ws, dev, pool_key, parity)
+
+
+def batch_forward_u8(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], sizes, dmax: Optional[float], crop=None,
+                     bgr: bool = False, out: Optional[torch.Tensor] = None, extra_flags: int = 0,
+                     scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+    """`batch_forward` ending in the 8-bit store: `gs_parameters` [B,N,9] -> uint8 `[B, rows, cols, 3]` (`crop`, default the
+    largest sample's size; sample b in `[b, :h_b, :w_b]`, zero elsewhere) and the plan (FLAG_FORWARD_ONLY)."""
+    pp = _chk(gs_parameters, "gs_parameters", (9,))
+    if gs_parameters.dim() != 3 or len(sizes) != gs_parameters.shape[0]:
+        raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
+    sm = ps = None
+    if scale_modify is None:
+        ps = _chk(steps, "step_sizes")
+        if steps.numel() != gs_parameters.shape[0]:
+            raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
+    else:
+        sm = _sm_ptr(scale_modify, gs_parameters.shape[0])
+    if dmax is not None and not (float(dmax) >= 0.0):
+        raise RuntimeError("dmax must be >= 0")
+    h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
+    d = make_batch_dims(gs_parameters.shape[1], sizes, w_max, h_max, dmax, flags=FLAG_FORWARD_ONLY | int(extra_flags))
+    return _step_u8(d, pp, ps, sm, default_step_size, crop, bgr, out, gs_parameters.device)
 
 
 def batch_backward(p: Plan, gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], grad: torch.Tensor, chw: bool = False) -> torch.Tensor:

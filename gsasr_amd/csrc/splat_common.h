@@ -116,6 +116,12 @@ struct Params {
                      // wide forward); 0: this plan carries none
     int tl_cap;      // ... entries a tile's list can hold (a tile whose cursor ends above it is rendered by the search instead)
     int tl_ntx, tl_ntiles;   // ... tiles per row of tiles, tiles in all (over the rows [row0, row1))
+    // 8-bit image output (gsasr_splat_forward_u8; set by the forward launcher, null everywhere else): the forward kernels store
+    // rint(clamp(v, 0, 1) * 255) as interleaved bytes at the cropped position instead of the float image (fwd_store_u8_px)
+    unsigned char *u8;       // the band's first row (batched canvas: [B, u8_rows, u8_cols, 3]); null: the float image
+    int u8_rows, u8_cols;    // crop: rows / columns of the full grid (of every sample's slot) that are written
+    unsigned u8_swap;        // 1: channel k goes to byte 2 - k (b, g, r)
+    size_t u8_pitch;         // bytes per output row (>= 3 * u8_cols)
 };
 
 // One sample of a batched canvas: its own pixel-grid size, its first canvas row and its px-table offset.
@@ -601,6 +607,7 @@ inline Params make_params(const gsasr_dims *d, const Layout &L)
     batch_uniform(d, P.geo_h, P.geo_w);
     P.grad_rows = d->grad_rows > 0 ? d->grad_rows : P.slot;
     P.tl_hlog = L.tl_hlog; P.tl_cap = L.tl_cap; P.tl_ntx = L.tl_ntx; P.tl_ntiles = L.tl_ntiles;
+    P.u8 = nullptr; P.u8_rows = P.u8_cols = 0; P.u8_swap = 0u; P.u8_pitch = 0;
     return P;
 }
 
@@ -610,6 +617,9 @@ void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_
 // then the dims' own, for its size only)
 Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted = nullptr);
 int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning = false);
+
+// arguments of the 8-bit forwards (gsasr_splat_forward_u8 and the step forms, which check them before they enqueue anything)
+int u8_args_check(const gsasr_dims *dims, const unsigned char *out, int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags);
 
 #define HIP_TRY(expr)                                    \
     do {                                                 \

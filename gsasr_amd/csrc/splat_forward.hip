@@ -463,6 +463,24 @@ __device__ __forceinline__ void fwd_block(const Params &P, const PlanView &V, in
     }
 }
 
+// 8-bit form of the image store (gsasr_splat_forward_u8): the finished pixel as rint(clamp(v, 0, 1) * 255) -- round half to
+// even (v_rndne_f32), what numpy's .round() does; NaN -> 0 (the max drops it) -- in three interleaved bytes at row `row` of the
+// output, channel k in byte k, or 2 - k with GSASR_U8_SWAP_RB.  The caller has tested the pixel against the crop.  Plain byte
+// stores: per store instruction a wave writes the same pixels as the float path with a quarter of the bytes.
+__device__ __forceinline__ unsigned char fwd_quant(float v)
+{
+    return (unsigned char)rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.0f);
+}
+
+__device__ __forceinline__ void fwd_store_u8_px(const Params &P, size_t row, int X, float r, float g, float b)
+{
+    unsigned char *o = P.u8 + row * P.u8_pitch + 3 * (size_t)X;
+    const unsigned char qr = fwd_quant(r), qg = fwd_quant(g), qb = fwd_quant(b);
+    o[0] = P.u8_swap ? qb : qr;
+    o[1] = qg;
+    o[2] = P.u8_swap ? qr : qb;
+}
+
 __device__ __forceinline__ void fwd_store(const Params &P, const PlanView &V, float *__restrict__ img, int sx0, int sy0,
                                           int lane, v2f ar, v2f ag, v2f ab)
 {
@@ -485,6 +503,17 @@ __device__ __forceinline__ void fwd_store(const Params &P, const PlanView &V, fl
         plane = (size_t)P.slot * P.w;
         chw0 = ((size_t)smp * 3 * P.slot + (size_t)(Y0 - g.base)) * P.w + X;
         chw1 = chw0 + 8 * (size_t)P.w;
+    }
+    if (P.u8) {
+        // (the launcher sets OVERWRITE_IMAGE: padding of a batched canvas arrives here as zeros.)  Rows count from the band's
+        // first, on a batched canvas from the sample's rectangle [u8_rows, u8_cols] in a stack of B of them
+        const int smp = P.batch > 1 ? sy0 / P.slot : 0, base = P.batch > 1 ? smp * P.slot : 0;
+        const size_t r0 = P.batch > 1 ? (size_t)smp * P.u8_rows + (size_t)(Y0 - base) : (size_t)(Y0 - P.row0);
+        if (X < P.u8_cols) {
+            if (ok0 && Y0 - base < P.u8_rows) fwd_store_u8_px(P, r0, X, ar.x, ag.x, ab.x);
+            if (ok1 && Y1 - base < P.u8_rows) fwd_store_u8_px(P, r0 + 8, X, ar.y, ag.y, ab.y);
+        }
+        return;
     }
     if (P.flags & GSASR_FLAG_CHW_IMAGE) {
         if (ok0) {
@@ -558,6 +587,10 @@ constexpr int WIDE = 16;   // sub-tile side
 __device__ __forceinline__ void fwd_store_px(const Params &P, float *__restrict__ img, int X, int Y, float r, float g, float b)
 {
     if (Y >= P.row1) return;
+    if (P.u8) {   // (single images only reach these kernels)
+        if (Y < P.u8_rows && X < P.u8_cols) fwd_store_u8_px(P, (size_t)(Y - P.row0), X, r, g, b);
+        return;
+    }
     const bool store = P.flags & GSASR_FLAG_OVERWRITE_IMAGE;
     if (P.flags & GSASR_FLAG_CHW_IMAGE) {
         const size_t plane = (size_t)(P.row1 - P.row0) * P.w;
@@ -1204,19 +1237,32 @@ __global__ __launch_bounds__(1024) void k_render_fwd_split(Params P, PlanView V,
     }
 }
 
-}  // namespace
+// where gsasr_splat_forward_u8 writes (null for the float image)
+struct U8Out {
+    unsigned char *out;
+    int rows, cols;
+    size_t pitch;
+    unsigned flags;
+};
 
-extern "C" {
-
-int gsasr_splat_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, float *img,
-                        void *stream)
+// The forward of both image forms: ONE kernel choice, so that the float and the 8-bit entry point can never render the same
+// dims with different kernels.
+static int forward_launch(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, float *img, const U8Out *u8,
+                          void *stream)
 {
+    // (before the workspace: argument errors are reported whatever the workspace holds)
+    if (u8) if (int rc = u8_args_check(dims, u8->out, u8->rows, u8->cols, u8->pitch, u8->flags)) return rc;
     Layout L;
     if (int rc = check_ws(dims, workspace, workspace_bytes, L)) return rc;
     const int rows = dims->row1 - dims->row0;
     if (rows == 0) return GSASR_OK;
-    if (!img) return fail(GSASR_ERR_ARG, "null image pointer");
-    const Params P = make_params(dims, L);
+    if (!u8 && !img) return fail(GSASR_ERR_ARG, "null image pointer");
+    Params P = make_params(dims, L);
+    if (u8) {   // always a store, interleaved: the two image flags of the dims do not apply
+        P.flags = (P.flags | GSASR_FLAG_OVERWRITE_IMAGE) & ~GSASR_FLAG_CHW_IMAGE;
+        P.u8 = u8->out; P.u8_rows = u8->rows; P.u8_cols = u8->cols; P.u8_pitch = u8->pitch;
+        P.u8_swap = (u8->flags & GSASR_U8_SWAP_RB) ? 1u : 0u;
+    }
     const PlanView V = make_view(L, const_cast<void *>(workspace));
     const int subs_x = (dims->w + SUBX - 1) / SUBX, tiles_y = (rows + SUBY - 1) / SUBY;
     hipStream_t st = (hipStream_t)stream;
@@ -1295,6 +1341,37 @@ int gsasr_splat_forward(const gsasr_dims *dims, const void *workspace, size_t wo
     }
     HIP_TRY(hipGetLastError());
     return GSASR_OK;
+}
+
+}  // namespace
+
+namespace gsasr_detail {
+int u8_args_check(const gsasr_dims *dims, const unsigned char *out, int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags)
+{
+    if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims (need c==3, 2<=h,w<=32767, 0<=row0<=row1<=h)");
+    if (u8_flags & ~GSASR_U8_SWAP_RB) return fail(GSASR_ERR_ARG, "unknown u8_flags (GSASR_U8_SWAP_RB only)");
+    if (crop_rows < 1 || crop_cols < 1) return fail(GSASR_ERR_ARG, "crop_rows and crop_cols must be >= 1");
+    if (crop_rows > (dims->batch > 1 ? dims->slot : dims->h) || crop_cols > dims->w)
+        return fail(GSASR_ERR_ARG, "the crop is larger than the grid");
+    if (pitch < 3 * (size_t)crop_cols) return fail(GSASR_ERR_ARG, "pitch is smaller than 3 * crop_cols bytes");
+    if (!out) return fail(GSASR_ERR_ARG, "null image pointer");
+    return GSASR_OK;
+}
+}  // namespace gsasr_detail
+
+extern "C" {
+
+int gsasr_splat_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, float *img,
+                        void *stream)
+{
+    return forward_launch(dims, workspace, workspace_bytes, img, nullptr, stream);
+}
+
+int gsasr_splat_forward_u8(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, unsigned char *out,
+                           int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags, void *stream)
+{
+    const U8Out u8{out, crop_rows, crop_cols, pitch, u8_flags};
+    return forward_launch(dims, workspace, workspace_bytes, nullptr, &u8, stream);
 }
 
 int gsasr_forward_subtile_width(const gsasr_dims *dims)

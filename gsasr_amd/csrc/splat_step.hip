@@ -242,6 +242,32 @@ int gsasr_step_forward_sm(const float *gs_parameters, const float *scale_modify,
     return gsasr_splat_forward(dims, workspace, S.plan_bytes, img, stream);
 }
 
+// the 8-bit forms: the same prologue + plan, ending in gsasr_splat_forward_u8
+int gsasr_step_forward_u8(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
+                          size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
+                          unsigned u8_flags, void *stream)
+{
+    if (int rc = u8_args_check(dims, out, crop_rows, crop_cols, pitch, u8_flags)) return rc;
+    StepLayout S;
+    StepSrc SS{};
+    SS.step = step_size;
+    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S)) return rc;
+    return gsasr_splat_forward_u8(dims, workspace, S.plan_bytes, out, crop_rows, crop_cols, pitch, u8_flags, stream);
+}
+
+int gsasr_step_forward_sm_u8(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
+                             int *mismatch, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                             unsigned char *out, int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags, void *stream)
+{
+    if (int rc = u8_args_check(dims, out, crop_rows, crop_cols, pitch, u8_flags)) return rc;
+    StepLayout S;
+    StepSrc SS{};
+    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
+    if (!scale_modify && dims && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
+    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S)) return rc;
+    return gsasr_splat_forward_u8(dims, workspace, S.plan_bytes, out, crop_rows, crop_cols, pitch, u8_flags, stream);
+}
+
 int gsasr_step_backward(const float *gs_parameters, const float *step_size, const float *grad_img,
                         float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
                         void *stream)

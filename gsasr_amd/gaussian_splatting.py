@@ -535,6 +535,53 @@ def generate_2D_gaussian_splatting_step(sr_size, gs_parameters, scale, scale_mod
     return _sample(final_image, sample_coords)
 
 
+def quantise_uint8(image, crop=None, bgr=False):
+    """The reference's inference epilogue (inference_paper.py:134-140, basicsr/utils/img_util.py:73-96) with torch ops: planar
+    float `[3,H,W]` -> uint8 `[crop_h, crop_w, 3]` = `(clamp(x[:, :crop_h, :crop_w], 0, 1) * 255).round()` (half to even, like
+    numpy), channels reversed with `bgr`; NaN -> 0.  What the 8-bit forward kernels store, for images that exist as floats."""
+    x = image.detach()
+    if crop is not None:
+        x = x[:, : crop[0], : crop[1]]
+    x = torch.nan_to_num(x.float(), nan=0.0).clamp(0, 1)
+    if bgr:
+        x = x.flip(0)
+    return (x.permute(1, 2, 0) * 255.0).round().to(torch.uint8).contiguous()
+
+
+def generate_2D_gaussian_splatting_step_uint8(sr_size, gs_parameters, scale, scale_modify, default_step_size=1.2,
+                                              mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, crop=None, bgr=False):
+    """`generate_2D_gaussian_splatting_step` for inference, handing over the picture instead of the tensor: uint8
+    `[crop_h, crop_w, 3]` = `quantise_uint8` of the `[3,H,W]` image, i.e. the reference's
+    `x[:, :, :gt_h, :gt_w] -> clamp_(0, 1) -> HWC -> (x * 255.0).round().astype(uint8)` in the call itself.  On CUDA tensors
+    the forward kernels store the bytes directly (gsasr_step_forward_u8: no float image, a forward-only plan, no autograd
+    graph) and there is no other path: anything the fused call cannot take raises.  On CPU tensors the image of
+    `rendering_python` is quantised with torch ops.  `crop` = (rows, cols) of the top-left corner (default: everything),
+    `bgr`: b, g, r byte order (cv2.imwrite)."""
+    if gs_parameters.dtype != torch.float32:
+        gs_parameters = gs_parameters.float()
+    H, W = _hw(sr_size)
+    crop = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
+    if not (1 <= crop[0] <= H and 1 <= crop[1] <= W):
+        raise ValueError(f"crop-{crop} must lie inside sr_size-{(H, W)}")
+    if gs_parameters.is_cuda:
+        if not _fused_ok(gs_parameters):
+            raise RuntimeError("generate_2D_gaussian_splatting_step_uint8 needs gs_parameters [N,9] on the GPU (no fallback)")
+        from . import _cabi
+        step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=True)
+        dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
+        dm = None if dmax_eff is None else float(dmax_eff)
+        gp, flags = gs_parameters.detach().contiguous(), _forward_flag(scale, H, W)
+        if step_size.__class__ is _StepSource:
+            out, _ = _cabi.step_forward_u8(gp, None, H, W, dm, crop, bgr, None, flags, step_size.scale_modify, step_size.default_step)
+            deferred_asserts.watch(gp.device)      # (after the launch: a look covers this call's own pair)
+            return out
+        return _cabi.step_forward_u8(gp, _step_tensor(step_size, gp.device), H, W, dm, crop, bgr, None, flags)[0]
+    step_size = _step_size(scale, scale_modify, default_step_size, mode)
+    sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
+    image = rendering_python(sigma_x, sigma_y, rho, coords, colours_with_alpha, sr_size, step_size, device=sigma_x.device)
+    return quantise_uint8(image, crop, bgr)
+
+
 class _FusedBatch(torch.autograd.Function):
     """A whole training batch in one set of launches: `gs_parameters[B,N,9]` ->
     `[B,3,Hmax,Wmax]`, sample b rendered on its own `sizes[b]` pixel grid in the top-left corner of its slot

@@ -210,6 +210,23 @@ GSASR_API int gsasr_splat_plan(const float *sigmas /*[s,3]*/, const float *coord
 GSASR_API int gsasr_splat_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes,
                         float *img, void *stream);
 
+/* 8-bit image output (inference: what every caller of the reference does to the float image straight away --
+ * x[:, :, :gt_h, :gt_w] -> clamp(0, 1) -> HWC -> (x * 255).round().astype(uint8), basicsr/utils/img_util.py:73-96 -- fused
+ * into the forward's store).  Per pixel (Y, X) of the full grid and channel k, with v the finished fp32 sum:
+ *     out[(Y - row0) * pitch + 3 * X + (swap ? 2 - k : k)] = (unsigned char) rintf(fminf(fmaxf(v, 0), 1) * 255)
+ * for Y < crop_rows and X < crop_cols only (the top-left crop_rows x crop_cols of the grid, 1 <= crop_* <= h, w); no other
+ * byte of `out` is touched, row padding (pitch > 3 * crop_cols bytes) included.  Rounding is half-to-even like numpy's
+ * .round(); a NaN sum gives 0.  Always a store, always interleaved: GSASR_FLAG_OVERWRITE_IMAGE / _CHW_IMAGE of dims.flags
+ * are ignored; everything else (row bands: `out` points at the band's first row; kernel-choice flags, registered choices,
+ * list_cap, GSASR_FLAG_FORWARD_ONLY plans) is as in gsasr_splat_forward -- both run the same kernel for the same dims.
+ * Batched canvas: out is [batch, crop_rows, crop_cols, 3] (sample stride crop_rows * pitch, crop_rows <= slot); sample b
+ * writes its own grid's pixels and 0 in the part of its rectangle beyond h_b x w_b.
+ * GSASR_ERR_ARG: crop_* < 1 or larger than the grid, pitch < 3 * crop_cols, null out, unknown u8_flags. */
+#define GSASR_U8_SWAP_RB 1u   /* write b,g,r (what cv2.imwrite / tensor2img(rgb2bgr=True) want) */
+GSASR_API int gsasr_splat_forward_u8(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes,
+                                     unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
+                                     unsigned u8_flags, void *stream);
+
 /* g_* += d(sum(grad_img*img))/d{sigmas,coords,colors} over rows [row0,row1).  Outputs must be
  * zero-initialised by the caller when a plain gradient is wanted (the reference wrapper does
  * torch.zeros_like, gs_cuda_dmax/gswrapper.py:40-42), unless GSASR_FLAG_OVERWRITE_GRADS is set. */
@@ -250,6 +267,14 @@ GSASR_API int gsasr_step_forward(const float *gs_parameters, const float *step_s
 GSASR_API int gsasr_step_forward_sm(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
                           int *mismatch, const gsasr_dims *dims, void *workspace, size_t workspace_bytes, float *img,
                           void *stream);
+/* gsasr_step_forward / gsasr_step_forward_sm ending in gsasr_splat_forward_u8 instead of the float forward */
+GSASR_API int gsasr_step_forward_u8(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
+                          size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
+                          unsigned u8_flags, void *stream);
+GSASR_API int gsasr_step_forward_sm_u8(const float *gs_parameters, const float *scale_modify, int sm_stride,
+                             float default_step_size, int *mismatch, const gsasr_dims *dims, void *workspace,
+                             size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
+                             unsigned u8_flags, void *stream);
 GSASR_API int gsasr_step_backward(const float *gs_parameters, const float *step_size, const float *grad_img,
                         float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
                         void *stream);
