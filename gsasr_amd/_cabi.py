@@ -18,20 +18,6 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # (GSASR_SPLAT_LIB: development override, e.g. to A/B two builds of the library on the same GPU box)
 LIB_PATH = os.environ.get("GSASR_SPLAT_LIB") or os.path.join(_PKG, "lib", "libgsasr_splat.so")
 
-EXPORTS = (
-    "gsasr_abi_version", "gsasr_last_error", "gsasr_splat_workspace_bytes", "gsasr_splat_plan",
-    "gsasr_splat_forward", "gsasr_splat_backward", "gsasr_gs_render", "gsasr_gs_render_backward",
-    "gsasr_gs_render_dmax", "gsasr_gs_render_backward_dmax", "gsasr_set_default_cutoff",
-    "gsasr_get_default_cutoff", "gsasr_prologue_forward", "gsasr_prologue_backward",
-    "gsasr_step_workspace_bytes", "gsasr_step_forward", "gsasr_step_backward",
-    "gsasr_band_select", "gsasr_band_merge", "gsasr_resolve_cutoff",
-    "gsasr_sample_workspace_bytes", "gsasr_splat_sample_forward", "gsasr_splat_sample_backward",
-    "gsasr_step_sample_forward", "gsasr_step_sample_backward",
-    "gsasr_step_forward_sm", "gsasr_step_sample_forward_sm", "gsasr_plan_cutoff", "gsasr_release_launcher_scratch", "gsasr_forward_subtile_width",
-    "gsasr_set_kernel_choice", "gsasr_get_kernel_choice", "gsasr_clear_kernel_choices",
-    "gsasr_splat_forward_u8", "gsasr_step_forward_u8", "gsasr_step_forward_sm_u8",
-)
-
 FLAG_OVERWRITE_IMAGE = 2   # GSASR_FLAG_OVERWRITE_IMAGE
 FLAG_OVERWRITE_GRADS = 4   # GSASR_FLAG_OVERWRITE_GRADS
 FLAG_CHW_IMAGE = 8         # GSASR_FLAG_CHW_IMAGE
@@ -60,6 +46,48 @@ class Dims(ctypes.Structure):
                 ("grad_rows", ctypes.c_int), ("list_cap", ctypes.c_int)]
 
 
+_vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
+_step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
+_SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
+    "gsasr_abi_version": (_i, []),
+    "gsasr_last_error": (ctypes.c_char_p, []),
+    "gsasr_splat_workspace_bytes": (_sz, [_dp]),
+    "gsasr_splat_plan": (_i, [_vp, _vp, _vp, _dp, _vp, _sz, _vp]),
+    "gsasr_splat_forward": (_i, [_dp, _vp, _sz, _vp, _vp]),
+    "gsasr_splat_forward_u8": (_i, _u8_tail),
+    "gsasr_splat_backward": (_i, [_vp] * 7 + [_dp, _vp, _sz, _vp]),
+    "gsasr_gs_render": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "gsasr_gs_render_backward": (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp]),
+    "gsasr_gs_render_dmax": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "gsasr_gs_render_backward_dmax": (_i, [_vp] * 7 + [_i, _i, _i, _i, _f, _vp]),
+    "gsasr_release_launcher_scratch": (_i, []),
+    "gsasr_prologue_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gsasr_prologue_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gsasr_step_workspace_bytes": (_sz, [_dp]),
+    "gsasr_step_forward": (_i, [_vp, _vp] + _step_tail),
+    "gsasr_step_forward_sm": (_i, [_vp, _vp, _i, _f, _vp] + _step_tail),
+    "gsasr_step_forward_u8": (_i, [_vp, _vp] + _u8_tail),
+    "gsasr_step_forward_sm_u8": (_i, [_vp, _vp, _i, _f, _vp] + _u8_tail),
+    "gsasr_step_backward": (_i, [_vp, _vp, _vp, _vp, _dp, _vp, _sz, _vp]),
+    "gsasr_band_select": (_i, [_vp, _dp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsasr_band_merge": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gsasr_sample_workspace_bytes": (_sz, [_dp, _i]),
+    "gsasr_splat_sample_forward": (_i, _sample_tail),
+    "gsasr_splat_sample_backward": (_i, [_vp] * 7 + [_dp, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "gsasr_step_sample_forward": (_i, [_vp, _vp] + _sample_tail),
+    "gsasr_step_sample_forward_sm": (_i, [_vp, _vp, _i, _f, _vp] + _sample_tail),
+    "gsasr_step_sample_backward": (_i, [_vp, _vp, _vp, _vp, _dp, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "gsasr_set_default_cutoff": (None, [_f]),
+    "gsasr_get_default_cutoff": (_f, []),
+    "gsasr_resolve_cutoff": (_f, [_f, _i]),
+    "gsasr_forward_subtile_width": (_i, [_dp]),
+    "gsasr_plan_cutoff": (_i, [_dp, _vp, _sz, _vp, ctypes.POINTER(_f), ctypes.POINTER(_u)]),
+    "gsasr_set_kernel_choice": (_i, [_dp, _u, _i]),
+    "gsasr_get_kernel_choice": (_i, [_dp, ctypes.POINTER(_u), ctypes.POINTER(_i)]),
+    "gsasr_clear_kernel_choices": (None, []),
+}
+EXPORTS = tuple(_SIGNATURES)
+
 _lib = None
 
 
@@ -72,75 +100,9 @@ def lib():
                 f"{LIB_PATH} not found: the HIP rasterizer is not built. Run `python -m gsasr_amd.build` "
                 "(or __graft_entry__.build()). gsasr_amd has no CPU/eager fallback by design.")
         L = ctypes.CDLL(LIB_PATH)
-        vp, f, i, sz = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_size_t
-        dp = ctypes.POINTER(Dims)
-        L.gsasr_abi_version.restype = i
-        L.gsasr_last_error.restype = ctypes.c_char_p
-        L.gsasr_splat_workspace_bytes.restype = sz
-        L.gsasr_splat_workspace_bytes.argtypes = [dp]
-        L.gsasr_splat_plan.restype = i
-        L.gsasr_splat_plan.argtypes = [vp, vp, vp, dp, vp, sz, vp]
-        L.gsasr_splat_forward.restype = i
-        L.gsasr_splat_forward.argtypes = [dp, vp, sz, vp, vp]
-        L.gsasr_splat_backward.restype = i
-        L.gsasr_splat_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, dp, vp, sz, vp]
-        L.gsasr_gs_render.restype = i
-        L.gsasr_gs_render.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
-        L.gsasr_gs_render_backward.restype = i
-        L.gsasr_gs_render_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
-        L.gsasr_gs_render_dmax.restype = i
-        L.gsasr_gs_render_dmax.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp]
-        L.gsasr_gs_render_backward_dmax.restype = i
-        L.gsasr_gs_render_backward_dmax.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
-        L.gsasr_prologue_forward.restype = i
-        L.gsasr_prologue_forward.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
-        L.gsasr_prologue_backward.restype = i
-        L.gsasr_prologue_backward.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp]
-        L.gsasr_step_workspace_bytes.restype = sz
-        L.gsasr_step_workspace_bytes.argtypes = [dp]
-        L.gsasr_step_forward.restype = i
-        L.gsasr_step_forward.argtypes = [vp, vp, dp, vp, sz, vp, vp]
-        L.gsasr_step_backward.restype = i
-        L.gsasr_step_backward.argtypes = [vp, vp, vp, vp, dp, vp, sz, vp]
-        L.gsasr_step_forward_sm.restype = i
-        L.gsasr_step_forward_sm.argtypes = [vp, vp, i, f, vp, dp, vp, sz, vp, vp]
-        L.gsasr_step_sample_forward_sm.restype = i
-        L.gsasr_step_sample_forward_sm.argtypes = [vp, vp, i, f, vp, dp, vp, sz, vp, i, vp, vp, sz, vp]
-        L.gsasr_band_select.restype = i
-        L.gsasr_band_select.argtypes = [vp, dp, i, i, i, vp, vp, vp, vp, vp, vp]
-        L.gsasr_band_merge.restype = i
-        L.gsasr_band_merge.argtypes = [vp, i, vp, vp, vp, vp, vp, i, vp]
-        L.gsasr_sample_workspace_bytes.restype = sz
-        L.gsasr_sample_workspace_bytes.argtypes = [dp, i]
-        L.gsasr_splat_sample_forward.restype = i
-        L.gsasr_splat_sample_forward.argtypes = [dp, vp, sz, vp, i, vp, vp, sz, vp]
-        L.gsasr_splat_sample_backward.restype = i
-        L.gsasr_splat_sample_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, dp, vp, sz, vp, i, vp, sz, vp]
-        L.gsasr_step_sample_forward.restype = i
-        L.gsasr_step_sample_forward.argtypes = [vp, vp, dp, vp, sz, vp, i, vp, vp, sz, vp]
-        L.gsasr_step_sample_backward.restype = i
-        L.gsasr_step_sample_backward.argtypes = [vp, vp, vp, vp, dp, vp, sz, vp, i, vp, sz, vp]
-        L.gsasr_set_default_cutoff.restype = None
-        L.gsasr_set_default_cutoff.argtypes = [f]
-        L.gsasr_get_default_cutoff.restype = f
-        L.gsasr_resolve_cutoff.restype = f
-        L.gsasr_resolve_cutoff.argtypes = [f, i]
-        L.gsasr_forward_subtile_width.restype = i
-        L.gsasr_forward_subtile_width.argtypes = [dp]
-        L.gsasr_plan_cutoff.restype = i
-        L.gsasr_plan_cutoff.argtypes = [dp, vp, sz, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint)]
-        L.gsasr_set_kernel_choice.restype = i
-        L.gsasr_set_kernel_choice.argtypes = [dp, ctypes.c_uint, i]
-        L.gsasr_get_kernel_choice.restype = i
-        L.gsasr_get_kernel_choice.argtypes = [dp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int)]
-        L.gsasr_clear_kernel_choices.restype = None
-        u = ctypes.c_uint
-        L.gsasr_splat_forward_u8.restype = i
-        L.gsasr_splat_forward_u8.argtypes = [dp, vp, sz, vp, i, i, sz, u, vp]
-        L.gsasr_step_forward_u8.restype = i
-        L.gsasr_step_forward_u8.argtypes = [vp, vp, dp, vp, sz, vp, i, i, sz, u, vp]
-        L.gsasr_step_forward_sm_u8.restype = i
-        L.gsasr_step_forward_sm_u8.argtypes = [vp, vp, i, f, vp, dp, vp, sz, vp, i, i, sz, u, vp]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if L.gsasr_abi_version() != 7:
             raise RuntimeError("libgsasr_splat.so ABI version mismatch")
         _lib = L
@@ -292,24 +254,90 @@ def make_dims(s: int, h: int, w: int, dmax: Optional[float], rows: Optional[Tupl
     return d
 
 
-_PLAN_DIMS = {}     # (s, h, w, dmax, rows, cutoff, flags) -> ([Dims fresh, pooled parity 0, pooled parity 1], workspace bytes)
+# ---- batched canvas: its dims -------------------------------------------------------
+MAX_BATCH = 64   # GSASR_MAX_BATCH
 
 
-def _plan_dims(s: int, h: int, w: int, dmax, rows, cutoff: float, flags: int, list_cap: int = 0):
-    key = (s, h, w, dmax, rows, cutoff, flags, list_cap)
-    hit = _PLAN_DIMS.get(key)
-    if hit is None:      # (dims structs + workspace size per shape: built once, not per call)
-        if dmax is not None and not (float(dmax) >= 0.0):
-            raise RuntimeError("dmax must be >= 0")
-        variants = [make_dims(s, h, w, dmax, rows, cutoff, int(flags) | f, list_cap)
-                    for f in (0, FLAG_COUNTERS_CLEAN, FLAG_COUNTERS_CLEAN | FLAG_PARITY)]
-        nbytes = lib().gsasr_splat_workspace_bytes(ctypes.byref(variants[0]))
-        if nbytes == 0:
-            check(-1, "gsasr_splat_workspace_bytes")
-        if len(_PLAN_DIMS) > 512:
-            _PLAN_DIMS.clear()
-        hit = _PLAN_DIMS[key] = (variants, nbytes)
+def _canvas_slot(h_max: int) -> int:
+    """rows of one slot of a canvas: the tallest sample, in whole 16-row tiles"""
+    return (int(h_max) + 15) // 16 * 16
+
+
+def make_batch_dims(n_per: int, sizes, w_max: int, h_max: int, dmax: Optional[float], cutoff: float = 0.0,
+                    flags: int = 0) -> Dims:
+    """dims of a canvas of len(sizes) slots; `sizes` = [(h_b, w_b)].  The returned struct owns the host array."""
+    B = len(sizes)
+    if not (1 < B <= MAX_BATCH):
+        raise RuntimeError(f"batch size must be in 2..{MAX_BATCH}")
+    slot = _canvas_slot(h_max)
+    hw = (ctypes.c_int * (2 * B))(*[int(v) for hw_ in sizes for v in hw_])
+    d = Dims(int(n_per) * B, slot * B, int(w_max), 3, -1.0 if dmax is None else float(dmax), 0, slot * B,
+             float(cutoff), int(flags), B, slot, ctypes.cast(hw, ctypes.POINTER(ctypes.c_int)))
+    d._keepalive = hw
+    return d
+
+
+# ---- what every planning entry point does first: the shape's dims and workspace size (cached), then a workspace ----
+def _check_dmax(dmax: Optional[float]) -> None:
+    if dmax is not None and not (float(dmax) >= 0.0):
+        raise RuntimeError("dmax must be >= 0")
+
+
+# Per shape, built once and not per call: what a plan's dims are made from -> ([Dims fresh, pooled parity 0, pooled parity 1],
+# workspace bytes).  The Dims are shared by all plans of the shape: nobody edits them (`_dims_with`, and whoever needs other
+# flags, copies first).  Workspace sizes follow a registered kernel choice: set_kernel_choice / clear_kernel_choices empty this.
+_SHAPES = {}
+_SPLAT_BYTES, _STEP_BYTES = "gsasr_splat_workspace_bytes", "gsasr_step_workspace_bytes"
+
+
+def _new_shape(key, dmax, make, bytes_fn: str):
+    """a cache miss of `_image_shape` / `_canvas_shape`: `make(extra_flags)` builds one Dims, the export `bytes_fn` sizes it"""
+    _check_dmax(dmax)
+    variants = [make(f) for f in (0, FLAG_COUNTERS_CLEAN, FLAG_COUNTERS_CLEAN | FLAG_PARITY)]
+    nbytes = getattr(lib(), bytes_fn)(ctypes.byref(variants[0]))
+    if nbytes == 0:
+        check(-1, bytes_fn)
+    if len(_SHAPES) > 512:
+        _SHAPES.clear()
+    hit = _SHAPES[key] = (variants, nbytes)
     return hit
+
+
+def _image_shape(bytes_fn: str, s: int, h: int, w: int, dmax, flags: int, rows=None, cutoff: float = 0.0, list_cap: int = 0):
+    key = (bytes_fn, s, h, w, dmax, flags, rows, cutoff, list_cap)
+    return _SHAPES.get(key) or _new_shape(key, dmax, lambda f: make_dims(s, h, w, dmax, rows, cutoff, int(flags) | f, list_cap), bytes_fn)
+
+
+def _canvas_shape(n_per: int, sizes, dmax, flags: int):
+    """the canvas of `sizes` = [(h_b, w_b)] with `n_per` Gaussians per sample, sized by gsasr_step_workspace_bytes"""
+    sizes = tuple(map(tuple, sizes))
+    key = (n_per, sizes, dmax, flags)
+    return _SHAPES.get(key) or _new_shape(
+        key, dmax, lambda f: make_batch_dims(n_per, sizes, max(w for _, w in sizes), max(h for h, _ in sizes), dmax, flags=int(flags) | f),
+        _STEP_BYTES)
+
+
+_LAYOUT_FLAGS = FLAG_FORWARD_ONLY | FLAG_BWD_TILE | FLAG_BWD_GAUSSIAN | FLAG_BWD_ATOMIC | FLAG_BWD_HOME | FLAG_CHW_GRAD | FLAG_STRIDE8
+
+
+def _pool_key(d: Dims, nbytes: int, dev, stream: int):
+    """Workspaces are interchangeable only between plans of the SAME layout: "the counters of parity p are zero" is a
+    statement about where the counter arrays lie and how long they are (grid size), so the key carries everything the
+    layout depends on, not just the byte count (two small shapes easily round to the same size)."""
+    return (dev.index, stream, nbytes, d.s, d.h, d.w, d.batch, d.slot, d.flags & _LAYOUT_FLAGS)
+
+
+def _acquire(shape, dev, stream: int):
+    """The workspace of a new plan of `shape` (an entry of `_SHAPES`), inside `with _on(dev)`: from the pool, with the Dims
+    variant that tells the plan which counters are clean, or fresh.  Returns (dims to plan with, workspace, pool key or
+    None, parity)."""
+    variants, nbytes = shape
+    if torch.cuda.is_current_stream_capturing():
+        # a captured plan is replayed on the same workspace with the same parity: it must zero its own counters
+        return variants[0], torch.empty(nbytes, dtype=torch.uint8, device=dev), None, 0
+    pool_key = _pool_key(variants[0], nbytes, dev, stream)
+    ws, parity, clean = _POOL.take(pool_key, nbytes, dev)
+    return (variants[1 + parity] if clean else variants[0]), ws, pool_key, parity
 
 
 def plan(sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tensor, h: int, w: int,
@@ -321,42 +349,13 @@ def plan(sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tensor, h: in
     s = sigmas.shape[0]
     if coords.shape[0] != s or colors.shape[0] != s:
         raise RuntimeError("sigmas, coords, colors disagree on the number of Gaussians")
-    variants, nbytes = _plan_dims(s, int(h), int(w), dmax, rows, cutoff, flags, list_cap)
+    shape = _image_shape(_SPLAT_BYTES, s, int(h), int(w), dmax, flags, rows, cutoff, list_cap)
     dev = sigmas.device
     with _on(dev):
         stream = _stream(dev)
-        if torch.cuda.is_current_stream_capturing():
-            # a captured plan is replayed on the same workspace with the same parity: it must zero its own counters
-            ws, parity, clean, pool_key = torch.empty(nbytes, dtype=torch.uint8, device=dev), 0, False, None
-        else:
-            pool_key = (dev.index, stream, nbytes, s, h, w, 0, 0, flags & _LAYOUT_FLAGS)
-            ws, parity, clean = _POOL.take(pool_key, nbytes, dev)
-        d = variants[1 + parity] if clean else variants[0]
-        check(lib().gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), nbytes, stream), "gsasr_splat_plan")
+        d, ws, pool_key, parity = _acquire(shape, dev, stream)
+        check(lib().gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), shape[1], stream), "gsasr_splat_plan")
     return Plan(d, ws, dev, pool_key, parity)
-
-
-_LAYOUT_FLAGS = FLAG_FORWARD_ONLY | FLAG_BWD_TILE | FLAG_BWD_GAUSSIAN | FLAG_BWD_ATOMIC | FLAG_BWD_HOME | FLAG_CHW_GRAD | FLAG_STRIDE8
-
-
-def _pool_key(d: Dims, nbytes: int, dev):
-    """Workspaces are interchangeable only between plans of the SAME layout: "the counters of parity p are zero" is a
-    statement about where the counter arrays lie and how long they are (grid size), so the key carries everything the
-    layout depends on, not just the byte count (two small shapes easily round to the same size)."""
-    return (dev.index, _stream(dev), nbytes, d.s, d.h, d.w, d.batch, d.slot, d.flags & _LAYOUT_FLAGS)
-
-
-def _pooled_workspace(d: Dims, nbytes: int, dev):
-    """a workspace for a plan with dims `d`: from the pool, with the flags that tell the plan its counters are clean
-    (set on `d`), or fresh.  Returns (workspace, pool key or None, parity)."""
-    if torch.cuda.is_current_stream_capturing():
-        # a captured plan is replayed on the same workspace with the same parity: it must zero its own counters
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev), None, 0
-    pool_key = _pool_key(d, nbytes, dev)
-    ws, parity, clean = _POOL.take(pool_key, nbytes, dev)
-    if clean:      # (these two bits do not change the layout)
-        d.flags |= FLAG_COUNTERS_CLEAN | (FLAG_PARITY if parity else 0)
-    return ws, pool_key, parity
 
 
 def _dims_with(p: Plan, extra_flags: int) -> Dims:
@@ -453,12 +452,17 @@ def backward(p: Plan, sigmas, coords, colors, grad_img, g_sigmas, g_coords, g_co
         raise RuntimeError(f"grads has shape {tuple(grad_img.shape)}, expected [rows, {d0.w}, 3]")
     if grad_img.shape[0] != d0.row1 - d0.row0:
         raise RuntimeError("grads does not match the plan's row band")
-    d = _dims_with(p, FLAG_OVERWRITE_GRADS if overwrite else 0)
+    _splat_backward(p, (_ptr3(sigmas, "sigmas", 3), _ptr3(coords, "coords", 2), _ptr3(colors, "colors", 3), pg,
+                        _ptr3(g_sigmas, "grads_sigmas", 3), _ptr3(g_coords, "grads_coords", 2), _ptr3(g_colors, "grads_colors", 3)),
+                    FLAG_OVERWRITE_GRADS if overwrite else 0)
+
+
+def _splat_backward(p: Plan, ptrs, extra_flags: int) -> None:
+    """gsasr_splat_backward on plan `p`; `ptrs` = the three inputs, the image gradient and the three gradient outputs"""
+    d = _dims_with(p, extra_flags)
     with _on(p.device):
-        check(lib().gsasr_splat_backward(_ptr3(sigmas, "sigmas", 3), _ptr3(coords, "coords", 2), _ptr3(colors, "colors", 3), pg,
-                                         _ptr3(g_sigmas, "grads_sigmas", 3), _ptr3(g_coords, "grads_coords", 2),
-                                         _ptr3(g_colors, "grads_colors", 3), ctypes.byref(d), p.workspace.data_ptr(),
-                                         p.workspace.numel(), _stream(p.device)), "gsasr_splat_backward")
+        check(lib().gsasr_splat_backward(*ptrs, ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), _stream(p.device)),
+              "gsasr_splat_backward")
 
 
 _AUTOTUNE = os.environ.get("GSASR_AMD_AUTOTUNE", "0") not in ("", "0")
@@ -488,16 +492,11 @@ def plan_forward(sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tenso
         from . import tune
         tune.autotune_hook(sigmas, coords, colors, h, w, dmax,
                            torch.is_grad_enabled() and (sigmas.requires_grad or coords.requires_grad or colors.requires_grad))
-    variants, nbytes = _plan_dims(s, h, w, dmax, None, 0.0, 0)
-    L = lib()
+    shape = _image_shape(_SPLAT_BYTES, s, h, w, dmax, 0)
+    L, nbytes = lib(), shape[1]
     with _on(dev):
         stream = _stream(dev)
-        if torch.cuda.is_current_stream_capturing():
-            ws, parity, clean, pool_key = torch.empty(nbytes, dtype=torch.uint8, device=dev), 0, False, None
-        else:
-            pool_key = (dev.index, stream, nbytes, s, h, w, 0, 0, 0)
-            ws, parity, clean = _POOL.take(pool_key, nbytes, dev)
-        d = variants[1 + parity] if clean else variants[0]
+        d, ws, pool_key, parity = _acquire(shape, dev, stream)
         pw = ws.data_ptr()
         check(L.gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), pw, nbytes, stream), "gsasr_splat_plan")
         check(L.gsasr_splat_forward(ctypes.byref(d), pw, nbytes, pi, stream), "gsasr_splat_forward")
@@ -525,24 +524,18 @@ def plan_packed(packed: torch.Tensor, h: int, w: int, dmax: Optional[float],
                 flags: int = 0) -> Plan:
     """`plan` for Gaussians held as one `[N,8]` tensor {sx,sy,rho,x,y,r,g,b}; no unpacking copies."""
     ps, pc, pk = _cols(packed, "packed")
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
-    d = make_dims(packed.shape[0], h, w, dmax, rows, cutoff, FLAG_STRIDE8 | int(flags))
-    L = lib()
-    nbytes = L.gsasr_splat_workspace_bytes(ctypes.byref(d))
-    if nbytes == 0:
-        check(-1, "gsasr_splat_workspace_bytes")
+    shape = _image_shape(_SPLAT_BYTES, packed.shape[0], int(h), int(w), dmax, FLAG_STRIDE8 | int(flags),
+                         rows if rows is None else tuple(rows), cutoff)
     dev = packed.device
     with _on(dev):
-        pool_key, parity = None, 0
-        if workspace is not None:
-            ws = workspace
-        else:
-            ws, pool_key, parity = _pooled_workspace(d, nbytes, dev)
-        if ws.numel() < nbytes:
-            raise RuntimeError("workspace smaller than gsasr_splat_workspace_bytes()")
-        check(L.gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), ws.numel(), _stream(dev)),
-              "gsasr_splat_plan")
+        stream = _stream(dev)
+        if workspace is None:
+            d, ws, pool_key, parity = _acquire(shape, dev, stream)
+        else:       # the caller's own workspace: nothing is known about its counters
+            d, ws, pool_key, parity = shape[0][0], workspace, None, 0
+            if ws.numel() < shape[1]:
+                raise RuntimeError("workspace smaller than gsasr_splat_workspace_bytes()")
+        check(lib().gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), ws.numel(), stream), "gsasr_splat_plan")
     return Plan(d, ws, dev, pool_key, parity)
 
 
@@ -556,10 +549,7 @@ def backward_packed(p: Plan, packed: torch.Tensor, grad_img: torch.Tensor, g_pac
     pg = _chk(grad_img, "grads", (p.dims.w, 3))
     if grad_img.shape[0] != p.dims.row1 - p.dims.row0 or g_packed.shape[0] != p.dims.s or packed.shape[0] != p.dims.s:
         raise RuntimeError("grads / g_packed do not match the plan")
-    d = _dims_with(p, FLAG_OVERWRITE_GRADS if overwrite else 0)
-    with _on(p.device):
-        check(lib().gsasr_splat_backward(ps, pc, pk, pg, gs, gc, gk, ctypes.byref(d), p.workspace.data_ptr(),
-                                         p.workspace.numel(), _stream(p.device)), "gsasr_splat_backward")
+    _splat_backward(p, (ps, pc, pk, pg, gs, gc, gk), FLAG_OVERWRITE_GRADS if overwrite else 0)
 
 
 def backward_to_packed(p: Plan, sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tensor, grad_img: torch.Tensor,
@@ -574,10 +564,7 @@ def backward_to_packed(p: Plan, sigmas: torch.Tensor, coords: torch.Tensor, colo
     pg = _chk(grad_img, "grads", (p.dims.w, 3))
     if grad_img.shape[0] != p.dims.row1 - p.dims.row0 or g_packed.shape[0] != p.dims.s or sigmas.shape[0] != p.dims.s:
         raise RuntimeError("grads / g_packed do not match the plan")
-    d = _dims_with(p, FLAG_STRIDE8 | (FLAG_OVERWRITE_GRADS if overwrite else 0))
-    with _on(p.device):
-        check(lib().gsasr_splat_backward(ps, pc, pk, pg, gs, gc, gk, ctypes.byref(d), p.workspace.data_ptr(),
-                                         p.workspace.numel(), _stream(p.device)), "gsasr_splat_backward")
+    _splat_backward(p, (ps, pc, pk, pg, gs, gc, gk), FLAG_STRIDE8 | (FLAG_OVERWRITE_GRADS if overwrite else 0))
 
 
 def _chk_i32(t: torch.Tensor, name: str, n: int) -> int:
@@ -637,9 +624,6 @@ def prologue_backward(gs_parameters, step, h: int, w: int, g_sigmas, g_coords, g
     return gp
 
 
-_STEP_DIMS = {}     # (n, h, w, dmax, flags) -> (Dims, workspace bytes) of the single-image step entry points
-
-
 _MISMATCH = {}      # device index -> int32[2] device tensor: the sticky "scale_modify pair differs" word of the _sm entry points
 
 
@@ -664,72 +648,73 @@ def _sm_ptr(sm: torch.Tensor, batch: int):
     return sm.data_ptr(), int(sm.stride(0))
 
 
+_BATCH_ARGS = "gs_parameters must be [B,N,9] with one step size and one (h,w) per sample"
+
+
+def _step_args(gs_parameters: torch.Tensor, step, scale_modify, default_step_size: float, sizes=None):
+    """The argument checks of the step-shaped entry points (`sizes` given: a batched canvas, `gs_parameters` [B,N,9]).  Returns
+    the pointer of `gs_parameters` and the step-size source, as the C arguments that follow that pointer: `(step sizes,)`, or for
+    the `_sm` twins `(scale_modify, its stride, default step size, mismatch word)`."""
+    pp = _ptr3(gs_parameters, "gs_parameters", 9)
+    if sizes is None:
+        B = 1
+        if gs_parameters.dim() != 2:
+            raise RuntimeError("gs_parameters must be [N,9]")
+    else:
+        B = gs_parameters.shape[0]
+        if gs_parameters.dim() != 3 or len(sizes) != B:
+            raise RuntimeError(_BATCH_ARGS)
+    if scale_modify is not None:
+        psm, stride = _sm_ptr(scale_modify, B)
+        return pp, (psm, stride, float(default_step_size), mismatch_flag(gs_parameters.device).data_ptr())
+    ps = _chk(step, "step_size" if sizes is None else "step_sizes")
+    if sizes is not None and step.numel() != B:
+        raise RuntimeError(_BATCH_ARGS)
+    return pp, (ps,)
+
+
+_STEP_FWD = ("gsasr_step_forward", "gsasr_step_forward_sm")
+_STEP_FWD_U8 = ("gsasr_step_forward_u8", "gsasr_step_forward_sm_u8")
+_STEP_SAMPLE = ("gsasr_step_sample_forward", "gsasr_step_sample_forward_sm")
+
+
+def _step_call(names, pp: int, src, d: Dims, ws: torch.Tensor, nbytes: int, *tail) -> None:
+    """prologue + plan + forward with dims `d` on workspace `ws`: the export `names[0]`, or for a scale_modify source
+    (`_step_args`) its `_sm` twin `names[1]`; `tail` = the arguments behind the workspace"""
+    name = names[len(src) > 1]
+    check(getattr(lib(), name)(pp, *src, ctypes.byref(d), ws.data_ptr(), nbytes, *tail), name)
+
+
+def _step_planar(shape, pp: int, src, dev):
+    """prologue + plan + forward into a fresh planar image, for an image or a canvas `shape` (an entry of `_SHAPES`)"""
+    with _on(dev):
+        stream = _stream(dev)
+        d, ws, pool_key, parity = _acquire(shape, dev, stream)
+        img = torch.empty((d.batch, 3, d.slot, d.w) if d.batch > 1 else (3, d.h, d.w), dtype=torch.float32, device=dev)
+        _step_call(_STEP_FWD, pp, src, d, ws, shape[1], img.data_ptr(), stream)
+    return img, Plan(d, ws, dev, pool_key, parity)
+
+
+def _step_u8(shape, pp: int, src, crop, bgr: bool, out, dev):
+    """prologue + plan + 8-bit forward, likewise"""
+    with _on(dev):
+        stream = _stream(dev)
+        rows, cols, out, pitch = _u8_target(shape[0][0], crop, out, dev)
+        d, ws, pool_key, parity = _acquire(shape, dev, stream)
+        _step_call(_STEP_FWD_U8, pp, src, d, ws, shape[1], out.data_ptr(), rows, cols, pitch, U8_SWAP_RB if bgr else 0, stream)
+    return out, Plan(d, ws, dev, pool_key, parity)
+
+
 def step_forward(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
                  extra_flags: int = 0, scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
     """prologue + plan + forward in ONE call: raw `gs_parameters[N,9]` -> planar image `[3,h,w]` (fresh).
     `extra_flags`: FLAG_FORWARD_ONLY (no backward will follow), FLAG_BWD_TILE (plan for the tile-stationary backward).
     The step size is `step` (a `[1]` device tensor), or with `scale_modify` (a `[2]` float32 CUDA tensor) the reference's
     `default_step_size / scale_modify[0]` formed on the device, its `[0] == [1]` assert reported through `mismatch_flag`."""
-    pp = _ptr3(gs_parameters, "gs_parameters", 9)
-    dev = gs_parameters.device
-    if scale_modify is None:
-        ps = _chk(step, "step_size")
-    else:
-        psm, stride = _sm_ptr(scale_modify, 1)
-    L = lib()
-    key = (gs_parameters.shape[0], int(h), int(w), dmax, int(extra_flags))
-    hit = _STEP_DIMS.get(key)
-    if hit is None:      # (dims structs + workspace size per shape: built once, not per call)
-        if dmax is not None and not (float(dmax) >= 0.0):
-            raise RuntimeError("dmax must be >= 0")
-        base = FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags)
-        variants = [make_dims(gs_parameters.shape[0], h, w, dmax, flags=base | f)
-                    for f in (0, FLAG_COUNTERS_CLEAN, FLAG_COUNTERS_CLEAN | FLAG_PARITY)]   # fresh / pooled parity 0 / 1
-        nbytes = L.gsasr_step_workspace_bytes(ctypes.byref(variants[0]))
-        if nbytes == 0:
-            check(-1, "gsasr_step_workspace_bytes")
-        if len(_STEP_DIMS) > 256:
-            _STEP_DIMS.clear()
-        hit = _STEP_DIMS[key] = (variants, nbytes)
-    variants, nbytes = hit
-    with _on(dev):
-        stream = _stream(dev)
-        if torch.cuda.is_current_stream_capturing():
-            # a captured plan is replayed on the same workspace with the same parity: it must zero its own counters
-            ws, parity, clean, pool_key = torch.empty(nbytes, dtype=torch.uint8, device=dev), 0, False, None
-        else:
-            d0 = variants[0]
-            pool_key = (dev.index, stream, nbytes, d0.s, d0.h, d0.w, 0, 0, d0.flags & _LAYOUT_FLAGS)
-            ws, parity, clean = _POOL.take(pool_key, nbytes, dev)
-        d = variants[1 + parity] if clean else variants[0]
-        img = torch.empty(3, int(h), int(w), dtype=torch.float32, device=dev)
-        if scale_modify is None:
-            check(L.gsasr_step_forward(pp, ps, ctypes.byref(d), ws.data_ptr(), nbytes, img.data_ptr(), stream),
-                  "gsasr_step_forward")
-        else:
-            check(L.gsasr_step_forward_sm(pp, psm, stride, float(default_step_size), mismatch_flag(dev).data_ptr(),
-                                          ctypes.byref(d), ws.data_ptr(), nbytes, img.data_ptr(), stream),
-                  "gsasr_step_forward_sm")
-    return img, Plan(d, ws, dev, pool_key, parity)
-
-
-def _step_u8(d: Dims, pp: int, ps, sm, default_step_size: float, crop, bgr: bool, out, dev):
-    """prologue + plan + 8-bit forward with dims `d` (ps: pointer of the step sizes, or `sm` = (pointer, stride) of scale_modify)"""
-    L = lib()
-    nbytes = L.gsasr_step_workspace_bytes(ctypes.byref(d))
-    if nbytes == 0:
-        check(-1, "gsasr_step_workspace_bytes")
-    with _on(dev):
-        stream = _stream(dev)
-        rows, cols, out, pitch = _u8_target(d, crop, out, dev)
-        ws, pool_key, parity = _pooled_workspace(d, nbytes, dev)
-        tail = (ctypes.byref(d), ws.data_ptr(), nbytes, out.data_ptr(), rows, cols, pitch, U8_SWAP_RB if bgr else 0, stream)
-        if sm is None:
-            check(L.gsasr_step_forward_u8(pp, ps, *tail), "gsasr_step_forward_u8")
-        else:
-            check(L.gsasr_step_forward_sm_u8(pp, sm[0], sm[1], float(default_step_size), mismatch_flag(dev).data_ptr(), *tail),
-                  "gsasr_step_forward_sm_u8")
-    return out, Plan(d, ws, dev, pool_key, parity)
+    pp, src = _step_args(gs_parameters, step, scale_modify, default_step_size)
+    shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax,
+                         FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags))
+    return _step_planar(shape, pp, src, gs_parameters.device)
 
 
 def step_forward_u8(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
@@ -737,18 +722,9 @@ def step_forward_u8(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h
                     scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
     """`step_forward` ending in the 8-bit store: raw `gs_parameters[N,9]` -> uint8 `[rows, cols, 3]` (see `forward_u8`) and
     the plan, always FLAG_FORWARD_ONLY (an 8-bit image has no backward).  `extra_flags`: FLAG_FWD_WIDE / FLAG_FWD_NARROW."""
-    pp = _ptr3(gs_parameters, "gs_parameters", 9)
-    if gs_parameters.dim() != 2:
-        raise RuntimeError("gs_parameters must be [N,9]")
-    sm = ps = None
-    if scale_modify is None:
-        ps = _chk(step, "step_size")
-    else:
-        sm = _sm_ptr(scale_modify, 1)
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
-    d = make_dims(gs_parameters.shape[0], h, w, dmax, flags=FLAG_FORWARD_ONLY | int(extra_flags))
-    return _step_u8(d, pp, ps, sm, default_step_size, crop, bgr, out, gs_parameters.device)
+    pp, src = _step_args(gs_parameters, step, scale_modify, default_step_size)
+    shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax, FLAG_FORWARD_ONLY | int(extra_flags))
+    return _step_u8(shape, pp, src, crop, bgr, out, gs_parameters.device)
 
 
 def step_backward(p: Plan, gs_parameters: torch.Tensor, step: Optional[torch.Tensor], grad: torch.Tensor, chw: bool = False) -> torch.Tensor:
@@ -766,60 +742,15 @@ def step_backward(p: Plan, gs_parameters: torch.Tensor, step: Optional[torch.Ten
     return gp
 
 
-# ---- batched canvas --------------------------------------------------------------
-MAX_BATCH = 64   # GSASR_MAX_BATCH
-
-
-def make_batch_dims(n_per: int, sizes, w_max: int, h_max: int, dmax: Optional[float], cutoff: float = 0.0,
-                    flags: int = 0) -> Dims:
-    """dims of a canvas of len(sizes) slots; `sizes` = [(h_b, w_b)].  The returned struct owns the host array."""
-    B = len(sizes)
-    if not (1 < B <= MAX_BATCH):
-        raise RuntimeError(f"batch size must be in 2..{MAX_BATCH}")
-    slot = (int(h_max) + 15) // 16 * 16
-    hw = (ctypes.c_int * (2 * B))(*[int(v) for hw_ in sizes for v in hw_])
-    d = Dims(int(n_per) * B, slot * B, int(w_max), 3, -1.0 if dmax is None else float(dmax), 0, slot * B,
-             float(cutoff), int(flags), B, slot, ctypes.cast(hw, ctypes.POINTER(ctypes.c_int)))
-    d._keepalive = hw
-    return d
-
-
+# ---- batched canvas: the step entry points on `make_batch_dims`' dims ----------------------------------------
 def batch_forward(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], sizes, dmax: Optional[float], extra_flags: int = 0,
                   scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
     """prologue + plan + forward of a whole batch in ONE set of launches.
     `gs_parameters` [B,N,9], `steps` [B] (device), `sizes` [(h_b, w_b)] -> planar images `[B,3,slot,w_max]`
     (sample b in `[:, :, :h_b, :w_b]`, zero elsewhere) and the plan for `batch_backward`."""
-    pp = _chk(gs_parameters, "gs_parameters", (9,))
-    if gs_parameters.dim() != 3 or len(sizes) != gs_parameters.shape[0]:
-        raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
-    if scale_modify is None:
-        ps = _chk(steps, "step_sizes")
-        if steps.numel() != gs_parameters.shape[0]:
-            raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
-    else:
-        psm, stride = _sm_ptr(scale_modify, gs_parameters.shape[0])
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
-    B, n = gs_parameters.shape[0], gs_parameters.shape[1]
-    h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
-    d = make_batch_dims(n, sizes, w_max, h_max, dmax, flags=FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags))
-    L = lib()
-    nbytes = L.gsasr_step_workspace_bytes(ctypes.byref(d))
-    if nbytes == 0:
-        check(-1, "gsasr_step_workspace_bytes")
-    dev = gs_parameters.device
-    with _on(dev):
-        stream = _stream(dev)
-        ws, pool_key, parity = _pooled_workspace(d, nbytes, dev)
-        img = torch.empty(B, 3, d.slot, w_max, dtype=torch.float32, device=dev)
-        if scale_modify is None:
-            check(L.gsasr_step_forward(pp, ps, ctypes.byref(d), ws.data_ptr(), nbytes, img.data_ptr(), stream),
-                  "gsasr_step_forward")
-        else:
-            check(L.gsasr_step_forward_sm(pp, psm, stride, float(default_step_size), mismatch_flag(dev).data_ptr(),
-                                          ctypes.byref(d), ws.data_ptr(), nbytes, img.data_ptr(), stream),
-                  "gsasr_step_forward_sm")
-    return img, Plan(d, ws, dev, pool_key, parity)
+    pp, src = _step_args(gs_parameters, steps, scale_modify, default_step_size, sizes)
+    shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags))
+    return _step_planar(shape, pp, src, gs_parameters.device)
 
 
 def batch_forward_u8(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], sizes, dmax: Optional[float], crop=None,
@@ -827,21 +758,9 @@ def batch_forward_u8(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor],
                      scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
     """`batch_forward` ending in the 8-bit store: `gs_parameters` [B,N,9] -> uint8 `[B, rows, cols, 3]` (`crop`, default the
     largest sample's size; sample b in `[b, :h_b, :w_b]`, zero elsewhere) and the plan (FLAG_FORWARD_ONLY)."""
-    pp = _chk(gs_parameters, "gs_parameters", (9,))
-    if gs_parameters.dim() != 3 or len(sizes) != gs_parameters.shape[0]:
-        raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
-    sm = ps = None
-    if scale_modify is None:
-        ps = _chk(steps, "step_sizes")
-        if steps.numel() != gs_parameters.shape[0]:
-            raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
-    else:
-        sm = _sm_ptr(scale_modify, gs_parameters.shape[0])
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
-    h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
-    d = make_batch_dims(gs_parameters.shape[1], sizes, w_max, h_max, dmax, flags=FLAG_FORWARD_ONLY | int(extra_flags))
-    return _step_u8(d, pp, ps, sm, default_step_size, crop, bgr, out, gs_parameters.device)
+    pp, src = _step_args(gs_parameters, steps, scale_modify, default_step_size, sizes)
+    shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_FORWARD_ONLY | int(extra_flags))
+    return _step_u8(shape, pp, src, crop, bgr, out, gs_parameters.device)
 
 
 def batch_backward(p: Plan, gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], grad: torch.Tensor, chw: bool = False) -> torch.Tensor:
@@ -920,50 +839,28 @@ def sample_backward(p: Plan, state, sigmas, coords, colors, grad_out, g_sigmas, 
 def step_sample_forward(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
                         points: torch.Tensor, scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
     """prologue + plan + sampled forward in ONE call: raw `gs_parameters[N,9]` -> `[3,S]` (step size as in `step_forward`)."""
-    pp = _chk(gs_parameters, "gs_parameters", (9,))
-    ps = None if scale_modify is not None else _chk(step, "step_size")
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
-    dev = gs_parameters.device
-    d = make_dims(gs_parameters.shape[0], h, w, dmax)
-    return _step_sample_forward(d, pp, ps, points, dev, scale_modify, default_step_size)
+    pp, src = _step_args(gs_parameters, step, scale_modify, default_step_size)
+    shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax, 0)
+    return _step_sampled(shape, pp, src, points, gs_parameters.device)
 
 
 def batch_sample_forward(gs_parameters: torch.Tensor, steps: torch.Tensor, sizes, dmax: Optional[float],
                          points: torch.Tensor):
     """the same for a whole batch: `gs_parameters` [B,N,9], `points` [B,S,2] on each sample's own grid -> `[B,3,S]`."""
-    pp = _chk(gs_parameters, "gs_parameters", (9,))
-    ps = _chk(steps, "step_sizes")
-    if gs_parameters.dim() != 3 or steps.numel() != gs_parameters.shape[0] or len(sizes) != gs_parameters.shape[0]:
-        raise RuntimeError("gs_parameters must be [B,N,9] with one step size and one (h,w) per sample")
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
-    h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
-    d = make_batch_dims(gs_parameters.shape[1], sizes, w_max, h_max, dmax)
-    return _step_sample_forward(d, pp, ps, points, gs_parameters.device)
+    pp, src = _step_args(gs_parameters, steps, None, 1.2, sizes)
+    return _step_sampled(_canvas_shape(gs_parameters.shape[1], sizes, dmax, 0), pp, src, points, gs_parameters.device)
 
 
-def _step_sample_forward(d: Dims, pp: int, ps, points: torch.Tensor, dev, scale_modify=None, default_step_size: float = 1.2):
-    L = lib()
+def _step_sampled(shape, pp: int, src, points: torch.Tensor, dev):
+    """prologue + plan + sampled forward (`_step_planar`'s sibling; these plans take a fresh workspace each)"""
+    d, nbytes = shape[0][0], shape[1]
     B = max(int(d.batch), 1)
-    if scale_modify is not None:
-        psm, stride = _sm_ptr(scale_modify, B)
     pts, n = _points(points, B, dev)
-    nbytes = L.gsasr_step_workspace_bytes(ctypes.byref(d))
-    if nbytes == 0:
-        check(-1, "gsasr_step_workspace_bytes")
     with _on(dev):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         sws = _sample_ws(d, n, dev)
         out = torch.empty((B, 3, n) if B > 1 else (3, n), dtype=torch.float32, device=dev)
-        if scale_modify is None:
-            check(L.gsasr_step_sample_forward(pp, ps, ctypes.byref(d), ws.data_ptr(), nbytes, pts.data_ptr(), n,
-                                              out.data_ptr(), sws.data_ptr(), sws.numel(), _stream(dev)),
-                  "gsasr_step_sample_forward")
-        else:
-            check(L.gsasr_step_sample_forward_sm(pp, psm, stride, float(default_step_size), mismatch_flag(dev).data_ptr(),
-                                                 ctypes.byref(d), ws.data_ptr(), nbytes, pts.data_ptr(), n, out.data_ptr(),
-                                                 sws.data_ptr(), sws.numel(), _stream(dev)), "gsasr_step_sample_forward_sm")
+        _step_call(_STEP_SAMPLE, pp, src, d, ws, nbytes, pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(), _stream(dev))
     return out, Plan(d, ws, dev), (pts, n, sws)
 
 
@@ -1026,8 +923,7 @@ def set_kernel_choice(shape: Dims, flags: int, list_cap: int = 0) -> None:
     global _N_CHOICES
     check(lib().gsasr_set_kernel_choice(ctypes.byref(shape), int(flags), int(list_cap)), "gsasr_set_kernel_choice")
     _N_CHOICES += 1
-    _PLAN_DIMS.clear()      # workspace sizes follow the registered choice
-    _STEP_DIMS.clear()
+    _SHAPES.clear()      # workspace sizes follow the registered choice
 
 
 def get_kernel_choice(shape: Dims) -> Optional[Tuple[int, int]]:
@@ -1041,5 +937,4 @@ def clear_kernel_choices() -> None:
     global _N_CHOICES
     lib().gsasr_clear_kernel_choices()
     _N_CHOICES = 0
-    _PLAN_DIMS.clear()
-    _STEP_DIMS.clear()
+    _SHAPES.clear()

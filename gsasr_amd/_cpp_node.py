@@ -16,6 +16,8 @@ from typing import Optional
 
 import torch
 
+from . import _cabi
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 EXT_PATH = os.path.join(PKG, "lib", "_gsasr_autograd.so")
 _ext = None
@@ -32,7 +34,6 @@ def load():
     if os.environ.get("GSASR_AMD_CPP_NODE", "1") == "0" or not os.path.exists(EXT_PATH):
         return None
     try:
-        from . import _cabi
         L = _cabi.lib()
         spec = importlib.util.spec_from_file_location("_gsasr_autograd", EXT_PATH)
         m = importlib.util.module_from_spec(spec)
@@ -54,8 +55,7 @@ def load():
 
 def fast_apply(sigmas, coords, colors, rendered_img, dmax: Optional[float]):
     """`GSCUDA.apply(sigmas, coords, colors, rendered_img[, dmax])` through the C++ node (dmax None: gs_cuda, the unbounded op)"""
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
+    _cabi._check_dmax(dmax)
     if torch.is_autocast_enabled("cuda"):     # the autocast-safe boundary of _amp.py: fp32 in, autocast off inside
         sigmas, coords, colors = (t.float() if t.is_floating_point() and t.dtype is not torch.float32 else t
                                   for t in (sigmas, coords, colors))
@@ -73,12 +73,8 @@ def _call(sigmas, coords, colors, rendered_img, dmax):
         from . import tune
         tune.autotune_hook(sigmas, coords, colors, rendered_img.shape[0], rendered_img.shape[1], dmax,
                            torch.is_grad_enabled() and (sigmas.requires_grad or coords.requires_grad or colors.requires_grad))
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev):
-            return _ext.gscuda_apply(sigmas, coords, colors, rendered_img, d, torch.cuda.current_stream(dev).cuda_stream,
-                                     torch.cuda.is_current_stream_capturing())
-    return _ext.gscuda_apply(sigmas, coords, colors, rendered_img, d, torch.cuda.current_stream(dev).cuda_stream,
-                             torch.cuda.is_current_stream_capturing())
+    with _cabi._on(dev):
+        return _ext.gscuda_apply(sigmas, coords, colors, rendered_img, d, _cabi._stream(dev), torch.cuda.is_current_stream_capturing())
 
 
 def _f32(t):
@@ -90,9 +86,7 @@ def fused_step_apply(gs_parameters, step, H: int, W: int, dmax: Optional[float],
     """`gsasr_amd.gaussian_splatting._FusedStep.apply` / `_FusedBatch.apply` through the C++ node: raw decoder output
     `[N,9]` -> `[3,H,W]`, or with `sizes` = [(h_b, w_b)] the batched canvas `[B,N,9]` -> `[B,3,Hmax,Wmax]`.  `flags` = the
     plan flags the caller chose (backward kernel, forward-only)."""
-    from . import _cabi
-    if dmax is not None and not (float(dmax) >= 0.0):
-        raise RuntimeError("dmax must be >= 0")
+    _cabi._check_dmax(dmax)
     if torch.is_autocast_enabled("cuda"):
         gs_parameters, step = _f32(gs_parameters), _f32(step)
         with torch.autocast("cuda", enabled=False):
@@ -106,7 +100,7 @@ def fused_step_apply(gs_parameters, step, H: int, W: int, dmax: Optional[float],
         if not (1 < batch <= _cabi.MAX_BATCH) or gs_parameters.dim() != 3 or gs_parameters.shape[0] != batch:
             raise RuntimeError("gs_parameters must be [B,N,9] with one (h,w) per sample")
         h_max, w = max(int(a) for a, _ in sizes), max(int(b) for _, b in sizes)
-        slot = (h_max + 15) // 16 * 16
+        slot = _cabi._canvas_slot(h_max)
         h = slot * batch
         flat = [int(v) for hw in sizes for v in hw]
         if step is not None and step.numel() != batch:
@@ -118,12 +112,9 @@ def fused_step_apply(gs_parameters, step, H: int, W: int, dmax: Optional[float],
     elif step is None:
         raise RuntimeError("step size missing")
     d = -1.0 if dmax is None else float(dmax)
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev):
-            return _ext.step_apply(gs_parameters, step, h, w, d, int(flags), sm, stride, float(default_step), mm, flat, slot, h_max,
-                                   torch.cuda.current_stream(dev).cuda_stream, torch.cuda.is_current_stream_capturing())
-    return _ext.step_apply(gs_parameters, step, h, w, d, int(flags), sm, stride, float(default_step), mm, flat, slot, h_max,
-                           torch.cuda.current_stream(dev).cuda_stream, torch.cuda.is_current_stream_capturing())
+    with _cabi._on(dev):
+        return _ext.step_apply(gs_parameters, step, h, w, d, int(flags), sm, stride, float(default_step), mm, flat, slot, h_max,
+                               _cabi._stream(dev), torch.cuda.is_current_stream_capturing())
 
 
 def clear_pool() -> None:

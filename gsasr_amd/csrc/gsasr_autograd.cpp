@@ -40,22 +40,57 @@ step_fwd_fn p_step_fwd = nullptr;
 step_fwd_sm_fn p_step_fwd_sm = nullptr;
 step_bwd_fn p_step_bwd = nullptr;
 
-// Plan workspaces kept between calls, per (device, stream, size, shape): a workspace that comes back from a finished node
-// has the OTHER parity's cell counters zeroed by its last plan (GSASR_FLAG_COUNTERS_CLEAN / _PARITY), so the next plan on it
-// launches no memset -- the same bookkeeping as gsasr_amd._cabi._WorkspacePool.
+// (the same set as gsasr_amd._cabi._LAYOUT_FLAGS: the two pools agree on what counts as a layout)
+constexpr unsigned LAYOUT_FLAGS = GSASR_FLAG_FORWARD_ONLY | GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_ATOMIC |
+                                  GSASR_FLAG_BWD_HOME | GSASR_FLAG_CHW_GRAD | GSASR_FLAG_STRIDE8;
+
+// Plan workspaces kept between calls: a workspace that comes back from a finished node has the OTHER parity's cell counters
+// zeroed by its last plan (GSASR_FLAG_COUNTERS_CLEAN / _PARITY), so the next plan on it launches no memset -- the same
+// bookkeeping as gsasr_amd._cabi._WorkspacePool.  "Clean" is a statement about where the counter arrays lie, so a workspace is
+// reused only under the same key: everything the layout depends on, and the stream that orders the reuse.
+enum NodeKind { GSCUDA_NODE, STEP_NODE };   // (a step workspace is never handed to a GSCUDA node and vice versa)
+struct PoolKey {
+    int dev = 0;
+    int64_t stream = 0, bytes = 0;
+    int s = 0, h = 0, w = 0;
+    unsigned layout = 0;     // the dims' flags & LAYOUT_FLAGS
+    int batch = 0, slot = 0;
+    NodeKind kind = GSCUDA_NODE;
+    bool operator==(const PoolKey &o) const
+    {
+        return dev == o.dev && stream == o.stream && bytes == o.bytes && s == o.s && h == o.h && w == o.w && layout == o.layout &&
+               batch == o.batch && slot == o.slot && kind == o.kind;
+    }
+};
 struct Pooled {
-    int dev;
-    int64_t stream;
-    int64_t bytes;
-    int s, h, w;
+    PoolKey key;
     at::Tensor ws;
     unsigned parity;
-    unsigned layout = 0;   // layout flags + batch geometry of the plan (step nodes): a workspace is reused only by the same layout
-    int batch = 0, slot = 0;
 };
 std::mutex g_mu;
 std::vector<Pooled> g_pool;
 constexpr size_t POOL_MAX = 64;
+
+// the most recently returned workspace of `key`, if any: its counters are clean for `parity`
+bool pool_take(const PoolKey &key, at::Tensor &ws, unsigned &parity)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (size_t i = g_pool.size(); i-- > 0;) {
+        if (g_pool[i].key == key) {
+            ws = g_pool[i].ws;
+            parity = g_pool[i].parity;
+            g_pool.erase(g_pool.begin() + (long)i);
+            return true;
+        }
+    }
+    return false;
+}
+
+void pool_give(const PoolKey &key, const at::Tensor &ws, unsigned parity)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_pool.size() < POOL_MAX) g_pool.push_back(Pooled{key, ws, parity});
+}
 
 void check(int rc, const char *what)
 {
@@ -76,28 +111,46 @@ const float *fptr(const at::Tensor &t, const char *name, int64_t last)
 // graph kept with retain_graph=True may run it again), clean for the flipped parity.
 struct PlanState : torch::CustomClassHolder {
     at::Tensor ws;
-    int64_t stream = 0;
-    int s = 0, h = 0, w = 0;
+    PoolKey key;       // (also the plan's stream and shape)
+    int parity = -1;   // -1: not pooled (planned under graph capture, or no plan made yet)
     float dmax = 0.f;
-    int parity = -1;   // -1: not pooled (planned under graph capture)
-    unsigned flags = 0, layout = 0;      // (step nodes) the dims' flags; their layout part
-    int batch = 0, slot = 0, grad_rows = 0;
+    unsigned flags = 0;
+    int grad_rows = 0;
     std::vector<int> sample_hw;          // (batched canvas) the host array gsasr_dims points to
     ~PlanState() override
     {
-        if (parity < 0 || !ws.defined()) return;
-        std::lock_guard<std::mutex> lk(g_mu);
-        if (g_pool.size() < POOL_MAX)
-            g_pool.push_back(Pooled{(int)ws.get_device(), stream, (int64_t)ws.numel(), s, h, w, ws, (unsigned)parity ^ 1u, layout, batch, slot});
+        if (parity >= 0 && ws.defined()) pool_give(key, ws, (unsigned)parity ^ 1u);
     }
     gsasr_dims dims() const
     {
         gsasr_dims d{};
-        d.s = s; d.h = h; d.w = w; d.c = 3; d.dmax = dmax; d.row0 = 0; d.row1 = h; d.cutoff = 0.f; d.flags = flags;
-        d.batch = batch; d.slot = slot; d.sample_hw = batch > 1 ? sample_hw.data() : nullptr; d.grad_rows = grad_rows;
+        d.s = key.s; d.h = key.h; d.w = key.w; d.c = 3; d.dmax = dmax; d.row0 = 0; d.row1 = key.h; d.cutoff = 0.f; d.flags = flags;
+        d.batch = key.batch; d.slot = key.slot; d.sample_hw = key.batch > 1 ? sample_hw.data() : nullptr; d.grad_rows = grad_rows;
         return d;
     }
+    void *stream() const { return (void *)key.stream; }
 };
+
+// The workspace of a new plan of `st` (shape, flags and stream filled in; `like`: a tensor on the plan's device), sized by `bytes_of`:
+// from the pool, or fresh.  Returns the dims to PLAN with: the plan's own, plus which counters arrive zeroed.  `planned` is what
+// `st.parity` becomes once that plan has been made (a workspace whose plan failed never goes back to the pool as clean).
+gsasr_dims acquire(PlanState &st, bytes_fn bytes_of, const char *bytes_name, NodeKind kind, const at::Tensor &like, bool capturing,
+                   int &planned)
+{
+    gsasr_dims d = st.dims();
+    const size_t bytes = bytes_of(&d);
+    TORCH_CHECK(bytes != 0, bytes_name, " failed: ", p_err());
+    st.key.dev = (int)like.get_device();
+    st.key.bytes = (int64_t)bytes;
+    st.key.layout = st.flags & LAYOUT_FLAGS;
+    st.key.kind = kind;
+    unsigned parity = 0u;
+    // (a captured plan is replayed on the same workspace with the same parity: it zeroes its own counters)
+    if (!capturing && pool_take(st.key, st.ws, parity)) d.flags |= GSASR_FLAG_COUNTERS_CLEAN | (parity ? GSASR_FLAG_PARITY : 0u);
+    if (!st.ws.defined()) st.ws = at::empty({(int64_t)bytes}, like.options().dtype(at::kByte));
+    planned = capturing ? -1 : (int)parity;
+    return d;
+}
 static auto plan_state_registration = torch::class_<PlanState>("gsasr_amd", "PlanState").def(torch::init<>());
 
 class GSCudaNode : public torch::autograd::Function<GSCudaNode> {
@@ -112,37 +165,16 @@ public:
         const int64_t s = sigmas.size(0);
         TORCH_CHECK(coords.size(0) == s && colors.size(0) == s, "sigmas, coords, colors disagree on the number of Gaussians");
         TORCH_CHECK(rendered_img.get_device() == sigmas.get_device(), "rendered_img does not match the plan (shape / device)");
-        gsasr_dims d{};
-        d.s = (int)s; d.h = (int)rendered_img.size(0); d.w = (int)rendered_img.size(1); d.c = 3;
-        d.dmax = dmax < 0.0 ? -1.f : (float)dmax;
-        d.row0 = 0; d.row1 = d.h; d.cutoff = 0.f; d.flags = 0u;
-        const size_t bytes = p_bytes(&d);
-        TORCH_CHECK(bytes != 0, "gsasr_splat_workspace_bytes failed: ", p_err());
-        at::Tensor ws;
-        unsigned parity = 0u;
-        bool clean = false;
-        if (!capturing) {   // (a captured plan is replayed on the same workspace with the same parity: it zeroes its own counters)
-            std::lock_guard<std::mutex> lk(g_mu);
-            for (size_t i = g_pool.size(); i-- > 0;) {
-                const Pooled &e = g_pool[i];
-                if (e.dev == (int)sigmas.get_device() && e.stream == stream && e.bytes == (int64_t)bytes && e.s == d.s && e.h == d.h && e.w == d.w && e.layout == 0u && e.batch == 0) {
-                    ws = e.ws;
-                    parity = e.parity;
-                    clean = true;
-                    g_pool.erase(g_pool.begin() + (long)i);
-                    break;
-                }
-            }
-        }
-        if (!ws.defined()) ws = at::empty({(int64_t)bytes}, sigmas.options().dtype(at::kByte));
-        gsasr_dims dp = d;
-        if (clean) dp.flags |= GSASR_FLAG_COUNTERS_CLEAN | (parity ? GSASR_FLAG_PARITY : 0u);
-        check(p_plan(ps, pc, pk, &dp, ws.data_ptr(), bytes, (void *)stream), "gsasr_splat_plan");
-        check(p_fwd(&d, ws.data_ptr(), bytes, pi, (void *)stream), "gsasr_splat_forward");
-        ctx->save_for_backward({sigmas, coords, colors});
         auto st = c10::make_intrusive<PlanState>();
-        st->ws = ws; st->stream = stream; st->s = d.s; st->h = d.h; st->w = d.w; st->dmax = d.dmax;
-        st->parity = capturing ? -1 : (int)parity;
+        st->key.s = (int)s; st->key.h = (int)rendered_img.size(0); st->key.w = (int)rendered_img.size(1);
+        st->key.stream = stream;
+        st->dmax = dmax < 0.0 ? -1.f : (float)dmax;
+        int planned;
+        const gsasr_dims dp = acquire(*st, p_bytes, "gsasr_splat_workspace_bytes", GSCUDA_NODE, sigmas, capturing, planned), d = st->dims();
+        check(p_plan(ps, pc, pk, &dp, st->ws.data_ptr(), (size_t)st->key.bytes, st->stream()), "gsasr_splat_plan");
+        st->parity = planned;
+        check(p_fwd(&d, st->ws.data_ptr(), (size_t)st->key.bytes, pi, st->stream()), "gsasr_splat_forward");
+        ctx->save_for_backward({sigmas, coords, colors});
         ctx->saved_data["plan"] = c10::IValue(st);
         ctx->mark_dirty({rendered_img});
         return rendered_img;
@@ -157,20 +189,15 @@ public:
         // must raise there and here alike instead of silently dropping the second-order terms)
         TORCH_CHECK(!torch::autograd::GradMode::is_enabled() || !grads[0].requires_grad(),
                     "gsasr_amd: the rasterizer's backward is not differentiable (create_graph=True is not supported)");
-        const at::Tensor &ws = st->ws;
-        const int64_t stream = st->stream;
         at::Tensor g = grads[0];
         if (g.scalar_type() != at::kFloat) g = g.to(at::kFloat);
         g = g.contiguous();
         at::Tensor gs = at::empty_like(sigmas), gc = at::empty_like(coords), gk = at::empty_like(colors);
-        gsasr_dims d{};
-        d.s = st->s; d.h = st->h; d.w = st->w; d.c = 3;
-        d.dmax = st->dmax;
-        d.row0 = 0; d.row1 = d.h; d.cutoff = 0.f;
-        d.flags = GSASR_FLAG_OVERWRITE_GRADS;   // (the reference zero-fills three tensors and adds into them: stored instead)
+        gsasr_dims d = st->dims();
+        d.flags |= GSASR_FLAG_OVERWRITE_GRADS;   // (the reference zero-fills three tensors and adds into them: stored instead)
         check(p_bwd(sigmas.data_ptr<float>(), coords.data_ptr<float>(), colors.data_ptr<float>(), g.data_ptr<float>(),
-                    gs.data_ptr<float>(), gc.data_ptr<float>(), gk.data_ptr<float>(), &d, ws.data_ptr(), (size_t)ws.numel(),
-                    (void *)stream),
+                    gs.data_ptr<float>(), gc.data_ptr<float>(), gk.data_ptr<float>(), &d, st->ws.data_ptr(), (size_t)st->ws.numel(),
+                    st->stream()),
               "gsasr_splat_backward");
         return {gs, gc, gk, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
     }
@@ -180,10 +207,6 @@ public:
 // image [3,H,W] (or [B,3,slot,W]) and back, one C call each way (prologue + plan + splat; splat backward + chain rule).  What
 // `generate_2D_gaussian_splatting_step` -- the function the reference's training loop calls per sample
 // (basicsr/models/gsasr_model.py:191-233) -- costs on the host is this node.
-// (the same set as gsasr_amd._cabi._LAYOUT_FLAGS: the two pools agree on what counts as a layout)
-constexpr unsigned LAYOUT_FLAGS = GSASR_FLAG_FORWARD_ONLY | GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_ATOMIC |
-                                  GSASR_FLAG_BWD_HOME | GSASR_FLAG_CHW_GRAD | GSASR_FLAG_STRIDE8;
-
 class StepNode : public torch::autograd::Function<StepNode> {
 public:
     static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &gs_parameters, const c10::optional<at::Tensor> &step,
@@ -197,39 +220,17 @@ public:
         TORCH_CHECK(batch <= 1 ? gs_parameters.dim() == 2 : (gs_parameters.dim() == 3 && gs_parameters.size(0) == batch),
                     "gs_parameters must be [N,9] (one image) or [B,N,9] (batched canvas)");
         auto st = c10::make_intrusive<PlanState>();
-        st->s = (int)(gs_parameters.numel() / 9);
-        st->h = (int)h; st->w = (int)w; st->dmax = dmax < 0.0 ? -1.f : (float)dmax;
+        st->key.s = (int)(gs_parameters.numel() / 9);
+        st->key.h = (int)h; st->key.w = (int)w; st->dmax = dmax < 0.0 ? -1.f : (float)dmax;
         st->flags = (unsigned)flags | GSASR_FLAG_OVERWRITE_IMAGE | GSASR_FLAG_CHW_IMAGE;
-        st->layout = st->flags & LAYOUT_FLAGS;
-        st->stream = stream;
+        st->key.stream = stream;
         if (batch > 1) {
-            st->batch = batch; st->slot = (int)slot;
+            st->key.batch = batch; st->key.slot = (int)slot;
             st->sample_hw.assign(sizes.begin(), sizes.end());
         }
-        gsasr_dims d = st->dims();
-        const size_t bytes = p_step_bytes(&d);
-        TORCH_CHECK(bytes != 0, "gsasr_step_workspace_bytes failed: ", p_err());
-        unsigned parity = 0u;
-        bool clean = false;
-        if (!capturing) {
-            std::lock_guard<std::mutex> lk(g_mu);
-            for (size_t i = g_pool.size(); i-- > 0;) {
-                const Pooled &e = g_pool[i];
-                if (e.dev == (int)gs_parameters.get_device() && e.stream == stream && e.bytes == (int64_t)bytes && e.s == d.s && e.h == d.h &&
-                    e.w == d.w && e.layout == (st->layout | 0x80000000u) && e.batch == st->batch && e.slot == st->slot) {
-                    st->ws = e.ws;
-                    parity = e.parity;
-                    clean = true;
-                    g_pool.erase(g_pool.begin() + (long)i);
-                    break;
-                }
-            }
-        }
-        st->layout |= 0x80000000u;     // (a step workspace is never handed to a GSCUDA node and vice versa)
-        if (!st->ws.defined()) st->ws = at::empty({(int64_t)bytes}, gs_parameters.options().dtype(at::kByte));
-        st->parity = capturing ? -1 : (int)parity;
-        gsasr_dims dp = d;
-        if (clean) dp.flags |= GSASR_FLAG_COUNTERS_CLEAN | (parity ? GSASR_FLAG_PARITY : 0u);
+        int planned;
+        const gsasr_dims dp = acquire(*st, p_step_bytes, "gsasr_step_workspace_bytes", STEP_NODE, gs_parameters, capturing, planned);
+        const size_t bytes = (size_t)st->key.bytes;
         at::Tensor img = batch > 1 ? at::empty({batch, 3, slot, w}, gs_parameters.options()) : at::empty({3, h, w}, gs_parameters.options());
         const float *ps = nullptr;
         if (scale_modify.has_value() && scale_modify->defined()) {
@@ -244,6 +245,7 @@ public:
             TORCH_CHECK(step->get_device() == gs_parameters.get_device(), "step_size lives on another device than gs_parameters");
             check(p_step_fwd(pp, ps, &dp, st->ws.data_ptr(), bytes, img.data_ptr<float>(), (void *)stream), "gsasr_step_forward");
         }
+        st->parity = planned;
         ctx->save_for_backward({gs_parameters, (step.has_value() && step->defined()) ? *step : at::Tensor()});
         ctx->saved_data["plan"] = c10::IValue(st);
         // (batched canvas: the slot is h_max rounded up to whole 16-row tiles; the caller sees [B,3,h_max,W], and the backward
@@ -266,9 +268,9 @@ public:
         at::Tensor gp = at::empty_like(gs_parameters);
         gsasr_dims d = st->dims();
         d.flags |= GSASR_FLAG_CHW_GRAD;      // the planar gradient autograd hands back is read as it is
-        if (st->batch > 1) d.grad_rows = (int)g.size(2);     // [B,3,Hmax,W]: rows per plane
+        if (st->key.batch > 1) d.grad_rows = (int)g.size(2);     // [B,3,Hmax,W]: rows per plane
         check(p_step_bwd(gs_parameters.data_ptr<float>(), step.defined() ? step.data_ptr<float>() : nullptr, g.data_ptr<float>(),
-                         gp.data_ptr<float>(), &d, st->ws.data_ptr(), (size_t)st->ws.numel(), (void *)st->stream),
+                         gp.data_ptr<float>(), &d, st->ws.data_ptr(), (size_t)st->ws.numel(), st->stream()),
               "gsasr_step_backward");
         return {gp, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(),
                 at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
@@ -313,7 +315,7 @@ std::vector<std::vector<int64_t>> pool_keys()
 {
     std::lock_guard<std::mutex> lk(g_mu);
     std::vector<std::vector<int64_t>> out;
-    for (const Pooled &e : g_pool) out.push_back({e.bytes, e.s, e.h, e.w, (int64_t)e.layout, e.batch, e.slot});
+    for (const Pooled &e : g_pool) out.push_back({e.key.bytes, e.key.s, e.key.h, e.key.w, (int64_t)e.key.layout, e.key.batch, e.key.slot});
     return out;
 }
 

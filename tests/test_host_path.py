@@ -108,6 +108,14 @@ def test_pooled_workspaces_are_not_shared_between_layouts(dev):
                 ref[(H, W)] = out.clone()
             assert float((out - ref[(H, W)]).abs().max()) <= 1e-5
             assert float((img.permute(2, 0, 1) - ref[(H, W)]).abs().max()) <= 1e-5
+    # one spelling of the pool key: whichever entry point made a plan, its key is what `_pool_key` builds from its dims
+    steps = torch.full((2,), 0.3, device=dev)
+    plans = [_cabi.plan(sig, xy, col, H, W, 0.3), _cabi.plan_forward(sig, xy, col, torch.zeros(H, W, 3, device=dev), 0.3),
+             _cabi.step_forward(p, steps[:1], H, W, 0.3)[1], _cabi.batch_forward(torch.stack([p, p]), steps, [(H, W), (48, W)], 0.3)[1]]
+    for made in plans:
+        assert made.pool_key is not None
+        assert made.pool_key == _cabi._pool_key(made.dims, made.workspace.numel(), dev, _cabi._stream(dev))
+    assert plans[0].pool_key == plans[1].pool_key       # the same dims through two entry points
 
 
 def _host_prologue_reference(p, H, W, scale_modify, dmax, wgt):
