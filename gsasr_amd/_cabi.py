@@ -46,7 +46,13 @@ class Dims(ctypes.Structure):
                 ("grad_rows", ctypes.c_int), ("list_cap", ctypes.c_int)]
 
 
+class View(ctypes.Structure):
+    """struct gsasr_view: the grid a window is cut from and the window's first row / column on it"""
+    _fields_ = [("full_h", ctypes.c_int), ("full_w", ctypes.c_int), ("y0", ctypes.c_int), ("x0", ctypes.c_int)]
+
+
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
+_vwp = ctypes.POINTER(View)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -85,6 +91,18 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_set_kernel_choice": (_i, [_dp, _u, _i]),
     "gsasr_get_kernel_choice": (_i, [_dp, ctypes.POINTER(_u), ctypes.POINTER(_i)]),
     "gsasr_clear_kernel_choices": (None, []),
+    # a window of the grid (gsasr_view): the view follows the dims in every argument list
+    "gsasr_splat_workspace_bytes_view": (_sz, [_dp, _vwp]),
+    "gsasr_step_workspace_bytes_view": (_sz, [_dp, _vwp]),
+    "gsasr_splat_plan_view": (_i, [_vp, _vp, _vp, _dp, _vwp, _vp, _sz, _vp]),
+    "gsasr_splat_forward_view": (_i, [_dp, _vwp, _vp, _sz, _vp, _vp]),
+    "gsasr_splat_forward_u8_view": (_i, [_dp, _vwp] + _u8_tail[1:]),
+    "gsasr_splat_backward_view": (_i, [_vp] * 7 + [_dp, _vwp, _vp, _sz, _vp]),
+    "gsasr_step_forward_view": (_i, [_vp, _vp, _dp, _vwp] + _step_tail[1:]),
+    "gsasr_step_forward_sm_view": (_i, [_vp, _vp, _i, _f, _vp, _dp, _vwp] + _step_tail[1:]),
+    "gsasr_step_forward_u8_view": (_i, [_vp, _vp, _dp, _vwp] + _u8_tail[1:]),
+    "gsasr_step_forward_sm_u8_view": (_i, [_vp, _vp, _i, _f, _vp, _dp, _vwp] + _u8_tail[1:]),
+    "gsasr_step_backward_view": (_i, [_vp, _vp, _vp, _vp, _dp, _vwp, _vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -236,6 +254,12 @@ class Plan:
     #                                       A caller that re-plans on `workspace` itself (C entry points with its own flags)
     #                                       must set this to None: the pool's "counters clean" bookkeeping no longer holds
     parity: int = 0
+    view: Optional[View] = None           # the window this plan renders (the view of its dims, `make_view`), None for a whole image /
+    #                                       band / canvas: every call on the plan passes it on
+
+    def __post_init__(self):
+        if self.view is None:
+            self.view = self.dims.__dict__.get("_view")
 
     def __del__(self):
         if self.pool_key is not None:
@@ -252,6 +276,28 @@ def make_dims(s: int, h: int, w: int, dmax: Optional[float], rows: Optional[Tupl
              float(cutoff), int(flags))
     d.list_cap = int(list_cap)      # tile lists: 0 = the library's capacity estimate, > 0 entries per tile, < 0 none
     return d
+
+
+# ---- a window of the grid (include/gsasr_splat.h: gsasr_view) ------------------------------------------------
+def make_view(d: Dims, view) -> Dims:
+    """attach `view` = (full_h, full_w, y0, x0) to the dims of the window (`make_dims(s, h, w, ...)` with the WINDOW's h, w):
+    the calls below then go to the `_view` entry points"""
+    if view is not None:
+        d._view = View(*[int(v) for v in view])
+    return d
+
+
+def _view_of(d: Dims) -> Optional[View]:
+    return d.__dict__.get("_view")
+
+
+def _vcall(name: str, d: Dims):
+    """(export, its leading dims arguments) for dims `d`: `name` with the dims, or `name_view` with the dims and their view"""
+    v = d.__dict__.get("_view")
+    if v is None:
+        return getattr(lib(), name), name, (ctypes.byref(d),)
+    name += "_view"
+    return getattr(lib(), name), name, (ctypes.byref(d), ctypes.byref(v))
 
 
 # ---- batched canvas (SURVEY.md 8 row f2): its dims -------------------------------------------------------
@@ -294,7 +340,8 @@ def _new_shape(key, dmax, make, bytes_fn: str):
     """a cache miss of `_image_shape` / `_canvas_shape`: `make(extra_flags)` builds one Dims, the export `bytes_fn` sizes it"""
     _check_dmax(dmax)
     variants = [make(f) for f in (0, FLAG_COUNTERS_CLEAN, FLAG_COUNTERS_CLEAN | FLAG_PARITY)]
-    nbytes = getattr(lib(), bytes_fn)(ctypes.byref(variants[0]))
+    fn, bytes_fn, dargs = _vcall(bytes_fn, variants[0])
+    nbytes = fn(*dargs)
     if nbytes == 0:
         check(-1, bytes_fn)
     if len(_SHAPES) > 512:
@@ -303,9 +350,16 @@ def _new_shape(key, dmax, make, bytes_fn: str):
     return hit
 
 
-def _image_shape(bytes_fn: str, s: int, h: int, w: int, dmax, flags: int, rows=None, cutoff: float = 0.0, list_cap: int = 0):
-    key = (bytes_fn, s, h, w, dmax, flags, rows, cutoff, list_cap)
-    return _SHAPES.get(key) or _new_shape(key, dmax, lambda f: make_dims(s, h, w, dmax, rows, cutoff, int(flags) | f, list_cap), bytes_fn)
+def _image_shape(bytes_fn: str, s: int, h: int, w: int, dmax, flags: int, rows=None, cutoff: float = 0.0, list_cap: int = 0, view=None):
+    """`view` = (full_h, full_w, y0, x0): h, w are a window of that grid (`make_view`)"""
+    if view is None:
+        key = (bytes_fn, s, h, w, dmax, flags, rows, cutoff, list_cap)
+    else:
+        view = tuple(int(v) for v in view)
+        if len(view) != 4:
+            raise RuntimeError("view must be (full_h, full_w, y0, x0)")
+        key = (bytes_fn, s, h, w, dmax, flags, rows, cutoff, list_cap, view)
+    return _SHAPES.get(key) or _new_shape(key, dmax, lambda f: make_view(make_dims(s, h, w, dmax, rows, cutoff, int(flags) | f, list_cap), view), bytes_fn)
 
 
 def _canvas_shape(n_per: int, sizes, dmax, flags: int):
@@ -324,7 +378,9 @@ def _pool_key(d: Dims, nbytes: int, dev, stream: int):
     """Workspaces are interchangeable only between plans of the SAME layout: "the counters of parity p are zero" is a
     statement about where the counter arrays lie and how long they are (grid size), so the key carries everything the
     layout depends on, not just the byte count (two small shapes easily round to the same size)."""
-    return (dev.index, stream, nbytes, d.s, d.h, d.w, d.batch, d.slot, d.flags & _LAYOUT_FLAGS)
+    key = (dev.index, stream, nbytes, d.s, d.h, d.w, d.batch, d.slot, d.flags & _LAYOUT_FLAGS)
+    v = d.__dict__.get("_view")     # (a window's layout also follows the grid it is cut from: the kernel-choice rules read it)
+    return key if v is None else key + (v.full_h, v.full_w, v.y0, v.x0)
 
 
 def _acquire(shape, dev, stream: int):
@@ -342,19 +398,25 @@ def _acquire(shape, dev, stream: int):
 
 def plan(sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tensor, h: int, w: int,
          dmax: Optional[float], rows: Optional[Tuple[int, int]] = None, cutoff: float = 0.0,
-         flags: int = 0, list_cap: int = 0) -> Plan:
+         flags: int = 0, list_cap: int = 0, view=None) -> Plan:
+    """`view` = (full_h, full_w, y0, x0): plan the h x w window of that grid whose first pixel is its (y0, x0); `forward`,
+    `forward_u8` and `backward` on the plan then render / differentiate the window only."""
     ps = _ptr3(sigmas, "sigmas", 3)
     pc = _ptr3(coords, "coords", 2)
     pk = _ptr3(colors, "colors", 3)
     s = sigmas.shape[0]
     if coords.shape[0] != s or colors.shape[0] != s:
         raise RuntimeError("sigmas, coords, colors disagree on the number of Gaussians")
-    shape = _image_shape(_SPLAT_BYTES, s, int(h), int(w), dmax, flags, rows, cutoff, list_cap)
+    shape = _image_shape(_SPLAT_BYTES, s, int(h), int(w), dmax, flags, rows, cutoff, list_cap, view)
     dev = sigmas.device
     with _on(dev):
         stream = _stream(dev)
         d, ws, pool_key, parity = _acquire(shape, dev, stream)
-        check(lib().gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), shape[1], stream), "gsasr_splat_plan")
+        if view is None:
+            check(lib().gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), shape[1], stream), "gsasr_splat_plan")
+        else:
+            check(lib().gsasr_splat_plan_view(ps, pc, pk, ctypes.byref(d), ctypes.byref(_view_of(d)), ws.data_ptr(), shape[1], stream),
+                  "gsasr_splat_plan_view")
     return Plan(d, ws, dev, pool_key, parity)
 
 
@@ -372,6 +434,8 @@ def _dims_with(p: Plan, extra_flags: int) -> Dims:
         d.flags |= extra_flags
         if hasattr(d0, "_keepalive"):
             d._keepalive = d0._keepalive
+        if "_view" in d0.__dict__:
+            d._view = d0._view
         cache[extra_flags] = d
     return d
 
@@ -392,8 +456,12 @@ def forward(p: Plan, img: torch.Tensor, overwrite: bool = False, chw: bool = Fal
     d = _dims_with(p, (FLAG_OVERWRITE_IMAGE if overwrite else 0) | (FLAG_CHW_IMAGE if chw else 0) |
                    (flags & (FLAG_FWD_WIDE | FLAG_FWD_NARROW)))
     with _on(p.device):
-        check(lib().gsasr_splat_forward(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), pi,
-                                        _stream(p.device)), "gsasr_splat_forward")
+        if p.view is None:
+            check(lib().gsasr_splat_forward(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), pi,
+                                            _stream(p.device)), "gsasr_splat_forward")
+        else:
+            check(lib().gsasr_splat_forward_view(ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(), p.workspace.numel(), pi,
+                                                 _stream(p.device)), "gsasr_splat_forward_view")
     return img
 
 
@@ -439,8 +507,13 @@ def forward_u8(p: Plan, crop=None, bgr: bool = False, out: Optional[torch.Tensor
     d = _dims_with(p, flags & (FLAG_FWD_WIDE | FLAG_FWD_NARROW))
     with _on(p.device):
         rows, cols, out, pitch = _u8_target(d, crop, out, p.device)
-        check(lib().gsasr_splat_forward_u8(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), out.data_ptr(), rows, cols,
-                                           pitch, U8_SWAP_RB if bgr else 0, _stream(p.device)), "gsasr_splat_forward_u8")
+        if p.view is None:
+            check(lib().gsasr_splat_forward_u8(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), out.data_ptr(), rows, cols,
+                                               pitch, U8_SWAP_RB if bgr else 0, _stream(p.device)), "gsasr_splat_forward_u8")
+        else:
+            check(lib().gsasr_splat_forward_u8_view(ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(), p.workspace.numel(),
+                                                    out.data_ptr(), rows, cols, pitch, U8_SWAP_RB if bgr else 0, _stream(p.device)),
+                  "gsasr_splat_forward_u8_view")
     return out
 
 
@@ -461,8 +534,12 @@ def _splat_backward(p: Plan, ptrs, extra_flags: int) -> None:
     """gsasr_splat_backward on plan `p`; `ptrs` = the three inputs, the image gradient and the three gradient outputs"""
     d = _dims_with(p, extra_flags)
     with _on(p.device):
-        check(lib().gsasr_splat_backward(*ptrs, ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), _stream(p.device)),
-              "gsasr_splat_backward")
+        if p.view is None:
+            check(lib().gsasr_splat_backward(*ptrs, ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), _stream(p.device)),
+                  "gsasr_splat_backward")
+        else:
+            check(lib().gsasr_splat_backward_view(*ptrs, ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(),
+                                                  p.workspace.numel(), _stream(p.device)), "gsasr_splat_backward_view")
 
 
 _AUTOTUNE = os.environ.get("GSASR_AMD_AUTOTUNE", "0") not in ("", "0")
@@ -682,7 +759,12 @@ def _step_call(names, pp: int, src, d: Dims, ws: torch.Tensor, nbytes: int, *tai
     """prologue + plan + forward with dims `d` on workspace `ws`: the export `names[0]`, or for a scale_modify source
     (`_step_args`) its `_sm` twin `names[1]`; `tail` = the arguments behind the workspace"""
     name = names[len(src) > 1]
-    check(getattr(lib(), name)(pp, *src, ctypes.byref(d), ws.data_ptr(), nbytes, *tail), name)
+    v = d.__dict__.get("_view")
+    if v is None:
+        check(getattr(lib(), name)(pp, *src, ctypes.byref(d), ws.data_ptr(), nbytes, *tail), name)
+    else:
+        name += "_view"
+        check(getattr(lib(), name)(pp, *src, ctypes.byref(d), ctypes.byref(v), ws.data_ptr(), nbytes, *tail), name)
 
 
 def _step_planar(shape, pp: int, src, dev):
@@ -706,24 +788,26 @@ def _step_u8(shape, pp: int, src, crop, bgr: bool, out, dev):
 
 
 def step_forward(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
-                 extra_flags: int = 0, scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+                 extra_flags: int = 0, scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2, view=None):
     """prologue + plan + forward in ONE call: raw `gs_parameters[N,9]` -> planar image `[3,h,w]` (fresh).
     `extra_flags`: FLAG_FORWARD_ONLY (no backward will follow), FLAG_BWD_TILE (plan for the tile-stationary backward).
     The step size is `step` (a `[1]` device tensor), or with `scale_modify` (a `[2]` float32 CUDA tensor) the reference's
-    `default_step_size / scale_modify[0]` formed on the device, its `[0] == [1]` assert reported through `mismatch_flag`."""
+    `default_step_size / scale_modify[0]` formed on the device, its `[0] == [1]` assert reported through `mismatch_flag`.
+    `view` = (full_h, full_w, y0, x0): the h x w window of that grid at (y0, x0) -- the prologue runs for the full grid."""
     pp, src = _step_args(gs_parameters, step, scale_modify, default_step_size)
     shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax,
-                         FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags))
+                         FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags), view=view)
     return _step_planar(shape, pp, src, gs_parameters.device)
 
 
 def step_forward_u8(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
                     crop=None, bgr: bool = False, out: Optional[torch.Tensor] = None, extra_flags: int = 0,
-                    scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+                    scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2, view=None):
     """`step_forward` ending in the 8-bit store: raw `gs_parameters[N,9]` -> uint8 `[rows, cols, 3]` (see `forward_u8`) and
-    the plan, always FLAG_FORWARD_ONLY (an 8-bit image has no backward).  `extra_flags`: FLAG_FWD_WIDE / FLAG_FWD_NARROW."""
+    the plan, always FLAG_FORWARD_ONLY (an 8-bit image has no backward).  `extra_flags`: FLAG_FWD_WIDE / FLAG_FWD_NARROW.
+    `view`: as for `step_forward`; `crop` is then of the window."""
     pp, src = _step_args(gs_parameters, step, scale_modify, default_step_size)
-    shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax, FLAG_FORWARD_ONLY | int(extra_flags))
+    shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax, FLAG_FORWARD_ONLY | int(extra_flags), view=view)
     return _step_u8(shape, pp, src, crop, bgr, out, gs_parameters.device)
 
 
@@ -737,8 +821,12 @@ def step_backward(p: Plan, gs_parameters: torch.Tensor, step: Optional[torch.Ten
     d = _dims_with(p, FLAG_CHW_GRAD if chw else 0)
     with _on(p.device):
         gp = torch.empty_like(gs_parameters)
-        check(lib().gsasr_step_backward(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), p.workspace.data_ptr(),
-                                        p.workspace.numel(), _stream(p.device)), "gsasr_step_backward")
+        if p.view is None:
+            check(lib().gsasr_step_backward(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), p.workspace.data_ptr(),
+                                            p.workspace.numel(), _stream(p.device)), "gsasr_step_backward")
+        else:
+            check(lib().gsasr_step_backward_view(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(),
+                                                 p.workspace.numel(), _stream(p.device)), "gsasr_step_backward_view")
     return gp
 
 

@@ -108,20 +108,27 @@ static unsigned note_slot(const void *ws) { return (unsigned)(((uintptr_t)ws >> 
 constexpr unsigned long long ADDR_MASK = ~0xffffffull;
 static unsigned long long note_addr(const void *ws) { return ((unsigned long long)(uintptr_t)ws & 0x0000ffffffffff00ull) << 16; }
 
-static unsigned long long note_shape(const gsasr_dims *d)
+// (a view is part of the shape: a call with another view, or none, on the workspace finds no plan.  No view hashes as ever)
+static unsigned long long note_shape(const gsasr_dims *d, const gsasr_view *vw)
 {
     unsigned long long x = (unsigned long long)(unsigned)d->s * 0x9E3779B97F4A7C15ull;
     x ^= ((unsigned long long)(unsigned)d->h << 32 | (unsigned)d->w) * 0xC2B2AE3D27D4EB4Full;
     x ^= (unsigned long long)(unsigned)batch_of(d) * 0x27D4EB2F165667C5ull;
+    if (vw) {
+        x ^= (((unsigned long long)(unsigned)vw->full_h << 32 | (unsigned)vw->full_w) + 0x165667B19E3779F9ull) * 0x9E3779B97F4A7C15ull;
+        x = (x ^ x >> 29) * 0xBF58476D1CE4E5B9ull;
+        x ^= ((unsigned long long)(unsigned)vw->y0 << 32 | (unsigned)vw->x0) * 0xC2B2AE3D27D4EB4Full + 0x94D049BB133111EBull;
+        x = (x ^ x >> 32) * 0x94D049BB133111EBull;
+    }
     return (x >> 40) & 0xffffull;
 }
 
 // (payload byte: slots per Gaussian in bits 0..4, the tile lists' tile height in bits 5..6: 0 none, 1 = 16 rows, 2 = 32;
 // the capacity word: the capacity (<= 65536) in bits 0..23)
-void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap)
+void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap, const gsasr_view *vw)
 {
     const unsigned long long a = note_addr(ws);
-    const unsigned long long w = a | note_shape(d) << 8 | (unsigned long long)((part_k & 0x1f) | (tl_hlog ? (tl_hlog - 3) << 5 : 0));
+    const unsigned long long w = a | note_shape(d, vw) << 8 | (unsigned long long)((part_k & 0x1f) | (tl_hlog ? (tl_hlog - 3) << 5 : 0));
     const unsigned long long c = a | ((unsigned long long)(unsigned)tl_cap & 0xffffffull);
     const unsigned i = note_slot(ws);
     std::lock_guard<std::mutex> lk(g_note_mu);
@@ -147,12 +154,12 @@ void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_
 
 // layout of the plan in `ws` from the note its plan left; *noted = false (and the layout of these dims, which nothing may
 // use but for its size) when there is no note of this shape for `ws`
-Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted)
+Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted, const gsasr_view *vw)
 {
     int part_k = -1, tl_hlog = -1, tl_cap = -1;
     bool found = false;
     if (ws) {
-        const unsigned long long a = note_addr(ws), key = a | note_shape(d) << 8;
+        const unsigned long long a = note_addr(ws), key = a | note_shape(d, vw) << 8;
         const unsigned i = note_slot(ws);
         unsigned long long w = g_notes[i].load(std::memory_order_acquire), c = 0ull;
         if ((w & ADDR_MASK) == a) c = g_note_caps[i].load(std::memory_order_acquire);
@@ -181,7 +188,7 @@ Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted)
         }
     }
     if (noted) *noted = found;
-    Layout L = make_layout(d, part_k, tl_hlog, tl_cap);
+    Layout L = make_layout(d, part_k, tl_hlog, tl_cap, vw);
     if (!found) L.tl_ok = false;
     return L;
 }
@@ -203,9 +210,10 @@ int hip_fail(hipError_t e, const char *where)
 
 const char *last_error_message() { return tl_err; }
 
-int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning)
+int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning, const gsasr_view *vw)
 {
     if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims (need c==3, 2<=h,w<=32767, 0<=row0<=row1<=h)");
+    if (!view_ok(dims, vw)) return fail(GSASR_ERR_ARG, VIEW_ERR);
     if (dims->batch > 1 && dims->grad_rows != 0 && (dims->flags & GSASR_FLAG_CHW_GRAD)) {
         // planar gradient of a batched canvas [B, 3, grad_rows, w]: every sample's rows must lie inside its planes
         int hmax = 0;
@@ -215,7 +223,7 @@ int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L,
         return fail(GSASR_ERR_ARG, "grad_rows applies to a batched canvas only (leave it 0)");
     }
     bool noted = true;
-    L = planning ? make_layout(dims) : plan_layout(dims, ws, &noted);
+    L = planning ? make_layout(dims, -1, -1, -1, vw) : plan_layout(dims, ws, &noted, vw);
     if (!ws || ((uintptr_t)ws & 255u)) return fail(GSASR_ERR_WORKSPACE, "workspace null or not 256-byte aligned");
     if (!noted) return fail(GSASR_ERR_PLAN, "the workspace holds no plan of these dims (plan it, or re-plan it, first)");
     if (ws_bytes < L.total) return fail(GSASR_ERR_WORKSPACE, "workspace smaller than gsasr_splat_workspace_bytes()");
@@ -305,6 +313,15 @@ size_t gsasr_splat_workspace_bytes(const gsasr_dims *dims)
         return 0;
     }
     return make_layout(dims).total;
+}
+
+size_t gsasr_splat_workspace_bytes_view(const gsasr_dims *dims, const gsasr_view *view)
+{
+    if (!view_ok(dims, view)) {
+        fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+        return 0;
+    }
+    return make_layout(dims, -1, -1, -1, norm_view(dims, view)).total;
 }
 
 

@@ -628,11 +628,12 @@ int bwd_mode(const gsasr_dims *dims, const Layout &L)
 // (k_prologue_bwd_gather) -- *mode_out tells which kernel ran.
 int splat_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_img, float *g_sigmas,
                    float *g_coords, float *g_colors, const gsasr_dims *dims, const void *workspace, size_t workspace_bytes,
-                   void *stream, bool gather, int *mode_out)
+                   void *stream, bool gather, int *mode_out, const gsasr_view *vw)
 {
     Layout L;
-    if (int rc = check_ws(dims, workspace, workspace_bytes, L)) return rc;
-    const int mode = bwd_mode(dims, L);
+    if (int rc = check_ws(dims, workspace, workspace_bytes, L, false, vw)) return rc;
+    const gsasr_dims pd = policy_dims(dims, vw);      // what the kernel-choice rules read (a window: its expected live Gaussians)
+    const int mode = bwd_mode(&pd, L);
     if (mode_out) *mode_out = mode;
     if (dims->flags & GSASR_FLAG_FORWARD_ONLY) return fail(GSASR_ERR_PLAN, "the plan was made with GSASR_FLAG_FORWARD_ONLY: it holds no backward records");
     if (dims->s == 0) return GSASR_OK;
@@ -640,12 +641,12 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
     if (mode == 0 && (dims->flags & GSASR_FLAG_CHW_GRAD))
         return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward");
     if (mode == 2 && (dims->flags & GSASR_FLAG_CHW_GRAD) && !(dims->flags & (GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_ATOMIC)) &&
-        (registered_choice(dims).flags & (GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_HOME)))
+        (registered_choice(&pd).flags & (GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_HOME)))
         // (a planar gradient on a plan without slots leaves only the atomic kernel: not when the shape's registered choice names a
         // kernel that reads interleaved gradients -- the choice would be dropped for an order-dependent one without a word)
         return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward (the kernel registered for this shape reads [rows, w, 3])");
     hipStream_t st = (hipStream_t)stream;
-    const Params P = make_params(dims, L);
+    const Params P = make_params(dims, L, vw);
     const PlanView V = make_view(L, const_cast<void *>(workspace));
     const int rows = dims->row1 - dims->row0;
     if (rows > 0 && !grad_img) return fail(GSASR_ERR_ARG, "null pointer");
@@ -669,7 +670,7 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
             // holds hundreds of Gaussians (GSASR's 16 per LR pixel), larger tiles with four waves for sparse plans -- a round
             // should find a wave's worth of Gaussians per wave.  development: GSASR_SPLAT_HOME_VARIANT=0|1|2|3
             static const int var_env = dev_switch("GSASR_SPLAT_HOME_VARIANT") ? atoi(dev_switch("GSASR_SPLAT_HOME_VARIANT")) : -1;
-            const double per_cell = (double)dims->s / (double)(L.ncells > 0 ? L.ncells : 1);
+            const double per_cell = (double)pd.s / (double)(L.ncells > 0 ? L.ncells : 1);
             int variant = var_env >= 0 ? var_env : per_cell >= 64.0 ? 0 : per_cell >= 24.0 ? 1 : 2;
             if (var_env < 0 && variant == 0) {
                 // 32 x 16-px tiles run two workgroups of eight waves per CU: 512 at a time.  Where their number leaves the last set
@@ -681,7 +682,7 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
                 const long over = n0 % 512;
                 if (n0 > 512 && over != 0 && over <= 384) variant = 3;      // (up to one set: nothing to even out)
             }
-            return launch_bwd_home(P, V, grad_img, g_sigmas, g_coords, g_colors, variant, st);
+            return launch_bwd_home(P, V, grad_img, g_sigmas, g_coords, g_colors, variant, st, vw);
         }
         // Eight Gaussians per wave (k_render_bwd8): built in round 5, parity-green, and SLOWER than one wave per Gaussian --
         // config 2 39.4 vs 30.7 us, 16 Gaussians per LR pixel 475 vs 401, the config-5 canvas 271 vs 235
@@ -702,7 +703,7 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
         // per SIMD) for windows of many trips, without it (70 VGPRs, 7 waves) for small windows.  The window sizes are on
         // the device; GSASR's Gaussians are LR-pixel sized, so pixels per Gaussian is a good proxy (x4: 16, x8: 64).
         static const int unroll_env = dev_switch("GSASR_SPLAT_BWD_UNROLL") ? atoi(dev_switch("GSASR_SPLAT_BWD_UNROLL")) : -1;   // development: 0 | 1
-        const bool unroll = unroll_env >= 0 ? unroll_env != 0 : (double)rows * (double)dims->w >= BWD_UNROLL_MIN * (double)dims->s;
+        const bool unroll = unroll_env >= 0 ? unroll_env != 0 : (double)rows * (double)dims->w >= BWD_UNROLL_MIN * (double)pd.s;
         // (Measured dead ends, git history: two Gaussians per wave one after the other, side by side in half waves, and --
         // round 3 -- sharing every gradient load over the union of their windows: 44-50 us against 37 us at config 2; rows
         // or a cell's window staged in LDS; a planar-gradient sweep.  A wave's life is its chain of dependent round trips:
@@ -723,13 +724,13 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
         const int tiles_x = (dims->w + BT_W - 1) / BT_W, tiles_y = (rows + bth - 1) / bth;
         dim3 grid((unsigned)tiles_x * (unsigned)tiles_y), block((unsigned)BT_THREADS << (P.bt_hlog - 4));
         // small rounds + five waves per SIMD from 32 HR pixels per Gaussian up (where this kernel is the default)
-        const bool sparse = (double)rows * (double)dims->w >= 32.0 * (double)dims->s;
+        const bool sparse = (double)rows * (double)dims->w >= 32.0 * (double)pd.s;
         // (the plan's tile lists serve this kernel when their tiles are its tiles)
         const bool lists = L.tl_ok && L.tl_hlog == P.bt_hlog;
 #define GSASR_BT(B, C, H) do { if (lists) hipLaunchKernelGGL((k_render_bwd_tile<B, C, H, true>), grid, block, 0, st, P, V, grad_img, tiles_x, mode == 2); \
                                else hipLaunchKernelGGL((k_render_bwd_tile<B, C, H, false>), grid, block, 0, st, P, V, grad_img, tiles_x, mode == 2); } while (0)
 #define GSASR_BT2(B, C) do { if (P.bt_hlog == 5) GSASR_BT(B, ((C) / 2 > 0 ? (C) / 2 : 1), 5); else GSASR_BT(B, C, 4); } while (0)
-        if (lists && !sparse && P.bt_hlog == 4 && tl_dense(dims)) {   // dense plans from lists: four waves per tile (rounds of 512 entries)
+        if (lists && !sparse && P.bt_hlog == 4 && tl_dense(&pd)) {   // dense plans from lists: four waves per tile (rounds of 512 entries)
             block = dim3(256);
             if (P.bounded) hipLaunchKernelGGL((k_render_bwd_tile<true, 2, 4, true, 4>), grid, block, 0, st, P, V, grad_img, tiles_x, mode == 2);
             else hipLaunchKernelGGL((k_render_bwd_tile<false, 2, 4, true, 4>), grid, block, 0, st, P, V, grad_img, tiles_x, mode == 2);
@@ -764,6 +765,17 @@ int gsasr_splat_backward(const float *sigmas, const float *coords, const float *
         return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward (GSASR_FLAG_BWD_HOME reads [rows, w, 3])");
     return splat_backward(sigmas, coords, colors, grad_img, g_sigmas, g_coords, g_colors, dims, workspace, workspace_bytes,
                           stream, true, nullptr);
+}
+
+int gsasr_splat_backward_view(const float *sigmas, const float *coords, const float *colors, const float *grad_img,
+                              float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
+                              const gsasr_view *view, const void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    if ((dims->flags & GSASR_FLAG_BWD_HOME) && (dims->flags & GSASR_FLAG_CHW_GRAD))
+        return fail(GSASR_ERR_ARG, "GSASR_FLAG_CHW_GRAD needs the tile-stationary backward (GSASR_FLAG_BWD_HOME reads [rows, w, 3])");
+    return splat_backward(sigmas, coords, colors, grad_img, g_sigmas, g_coords, g_colors, dims, workspace, workspace_bytes,
+                          stream, true, nullptr, norm_view(dims, view));
 }
 
 }  // extern "C"

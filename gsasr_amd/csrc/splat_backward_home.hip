@@ -149,10 +149,11 @@ __device__ __forceinline__ void hm_write(float v, int k, unsigned i, const Param
     else atomicAdd(dst, v);
 }
 
-template <bool BOUNDED, int TCX, int TCY, int WAVES>
+// (VIEW: the plan of a window, gsasr_view -- its Gaussians' pixel positions scale with the full grid: view_scale)
+template <bool BOUNDED, int TCX, int TCY, int WAVES, bool VIEW>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == 8 ? 4 : (TCX * TCY >= 8 ? 1 : 2)))) void k_render_bwd_home(Params P, PlanView V, const float *__restrict__ grad,
                                                                 float *__restrict__ g_sigmas, float *__restrict__ g_coords,
-                                                                float *__restrict__ g_colors, int tiles_x, int tps, int cps)
+                                                                float *__restrict__ g_colors, int tiles_x, int tps, int cps, ViewArg VW)
 {
     constexpr int THREADS = 64 * WAVES;
     constexpr int TW = CELL * TCX, TH = CELL * TCY, RW = TW + 2 * HM_HALO, RH = TH + 2 * HM_HALO;
@@ -223,7 +224,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
         // (GSASR_SPLAT_GRAD_TAU: a gradient sums over its own pixels only)
         float kw = __uint_as_float(V.hdr[3]);
         if (P.kb_max > 0.f && kw > P.kb_max) kw = P.kb_max;
-        const float hx = 0.5f * (float)(g.w - 1), hy = 0.5f * (float)(g.h - 1);
+        const Scale sc = view_scale<VIEW>(VW, g);
+        const float hx = 0.5f * (float)(sc.gw - 1), hy = 0.5f * (float)(sc.gh - 1);
         __syncthreads();
 
         for (unsigned base = 0u; base < n; base += (unsigned)ROUND) {
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
                         // the ellipse {qa u^2 + qb u v + qc v^2 <= tau'} reaches on the rows the window has in that quadrant row
                         const float rho = fa.z, omr = fa.y;
                         const float spx = hx * __builtin_amdgcn_rcpf(fa.w), spy = hy * __builtin_amdgcn_rcpf(fb.x);     // sigmas in pixels
-                        const float cxp = (ra.x + 1.f) * hx, cyp = (ra.y + 1.f) * hy + (float)g.base;
+                        const float cxp = (ra.x + 1.f) * hx - (float)sc.ox, cyp = (ra.y + 1.f) * hy + (float)g.base - (float)sc.oy;
                         const float tau = 0.5f * kw * kw;
                         const float iq = 1.f / (omr * spx * spy);
                         const float qa = 0.5f * iq * (spy / spx), qb = -rho * iq, qc = 0.5f * iq * (spx / spy);
@@ -479,19 +481,24 @@ namespace gsasr_detail {
 // their workgroups only take part in the tails).  variant: 0 = 32 x 16-px tiles, eight waves (dense plans); 1 = 32 x 32, four
 // waves; 2 = 64 x 32, four waves (sparse plans).
 int launch_bwd_home(const Params &P, const PlanView &V, const float *grad_img, float *g_sigmas, float *g_coords, float *g_colors,
-                    int variant, hipStream_t st)
+                    int variant, hipStream_t st, const gsasr_view *vw)
 {
+    const ViewArg VW = view_arg(vw);
     const int cps = P.batch > 1 ? P.slot / CELL : P.ncy;
+#define GSASR_HOME_V(TCX, TCY, W, ISVIEW) do { \
+        if (P.bounded) hipLaunchKernelGGL((k_render_bwd_home<true, TCX, TCY, W, ISVIEW>), grid, block, 0, st, P, V, grad_img, g_sigmas, g_coords, g_colors, tiles_x, tps, cps, VW); \
+        else hipLaunchKernelGGL((k_render_bwd_home<false, TCX, TCY, W, ISVIEW>), grid, block, 0, st, P, V, grad_img, g_sigmas, g_coords, g_colors, tiles_x, tps, cps, VW); } while (0)
 #define GSASR_HOME(TCX, TCY, W) do { \
         const int tiles_x = (P.ncx + (TCX) - 1) / (TCX), tps = (cps + (TCY) - 1) / (TCY); \
         const dim3 grid((unsigned)tiles_x * (unsigned)tps * (unsigned)P.batch), block(64 * (W)); \
-        if (P.bounded) hipLaunchKernelGGL((k_render_bwd_home<true, TCX, TCY, W>), grid, block, 0, st, P, V, grad_img, g_sigmas, g_coords, g_colors, tiles_x, tps, cps); \
-        else hipLaunchKernelGGL((k_render_bwd_home<false, TCX, TCY, W>), grid, block, 0, st, P, V, grad_img, g_sigmas, g_coords, g_colors, tiles_x, tps, cps); } while (0)
+        if (vw) GSASR_HOME_V(TCX, TCY, W, true); \
+        else GSASR_HOME_V(TCX, TCY, W, false); } while (0)
     if (variant == 0) GSASR_HOME(2, 1, 8);
     else if (variant == 1) GSASR_HOME(2, 2, 4);
     else if (variant == 3) GSASR_HOME(1, 1, 4);
     else GSASR_HOME(4, 2, 4);
 #undef GSASR_HOME
+#undef GSASR_HOME_V
     HIP_TRY(hipGetLastError());
     return GSASR_OK;
 }

@@ -124,6 +124,16 @@ struct Params {
     size_t u8_pitch;         // bytes per output row (>= 3 * u8_cols)
 };
 
+// Window of a larger grid (gsasr_view): Params::h, w are then the WINDOW's size -- all the render kernels see -- and the kernels
+// that turn a Gaussian's normalised coordinate into a pixel position (k_classify, k_bin, the home-tile backward; instantiated
+// with VIEW = true) map it with the full grid's scale, minus the window's origin (view_scale).  Their LAST kernel argument, so
+// that Params and every argument offset of the other kernels stay what they were; all zero without a view.
+struct ViewArg {
+    int fh, fw;              // the full grid
+    int y0, x0;              // the window's first row / column on it
+};
+inline ViewArg view_arg(const gsasr_view *vw) { return vw ? ViewArg{vw->full_h, vw->full_w, vw->y0, vw->x0} : ViewArg{0, 0, 0, 0}; }
+
 // One sample of a batched canvas: its own pixel-grid size, its first canvas row and its px-table offset.
 // A single image is the sample {h, w, 0, 0}.
 struct Geo {
@@ -175,6 +185,18 @@ __device__ __forceinline__ Geo sample_geo(const Params &P, const PlanView &V, in
     return Geo{g.x, g.y, g.z, g.w};
 }
 
+// Where normalised coordinates land in pixels: pixel = (coordinate + 1) * 0.5 * (gw - 1) - ox (rows: gh, oy).  A sample's own
+// grid and no offset, or -- VIEW, single images only -- the full grid a window is cut from and the window's origin.
+struct Scale {
+    int gh, gw, oy, ox;
+};
+template <bool VIEW>
+__device__ __forceinline__ Scale view_scale(const ViewArg &vw, const Geo &g)
+{
+    if (VIEW) return Scale{vw.fh, vw.fw, vw.y0, vw.x0};
+    return Scale{g.h, g.w, 0, 0};
+}
+
 struct Layout {
     size_t off_geo, off_hdr, off_count, off_start, off_px, off_py, off_key, off_rank, off_bmax, off_stot, off_rec, off_fin, off_sums, off_done, off_bbox, off_win, off_part, off_qspan;
     size_t off_tlc, off_tle;     // tile lists (at the END of the workspace: every other offset is the same with and without them)
@@ -207,6 +229,39 @@ inline bool dims_ok(const gsasr_dims *d)
 }
 
 inline int batch_of(const gsasr_dims *d) { return d->batch > 1 ? d->batch : 1; }
+
+constexpr const char *VIEW_ERR = "bad view (a window is one whole image: row0 = 0, row1 = h, batch = 0; 2<=full_h,full_w<=32767, 0<=y0<=full_h-h, 0<=x0<=full_w-w)";
+// dims + view of a `_view` entry point: one whole image of the window's size, cut from a grid within the whole-image limits
+inline bool view_ok(const gsasr_dims *d, const gsasr_view *v)
+{
+    if (!dims_ok(d)) return false;
+    if (!v) return true;
+    return d->batch <= 1 && d->row0 == 0 && d->row1 == d->h && v->full_h >= 2 && v->full_w >= 2 && v->full_h <= 32767 &&
+           v->full_w <= 32767 && v->y0 >= 0 && v->x0 >= 0 && v->y0 <= v->full_h - d->h && v->x0 <= v->full_w - d->w;
+}
+
+// a view that is the whole grid is no view: such a call takes the whole-image path, bit for bit
+inline const gsasr_view *norm_view(const gsasr_dims *d, const gsasr_view *v)
+{
+    return (d && v && v->y0 == 0 && v->x0 == 0 && v->full_h == d->h && v->full_w == d->w) ? nullptr : v;
+}
+
+// The dims the kernel-choice rules below are evaluated with (fwd_wants_wide, bwd_wants_tile / _home, bwd_part_k, bt_tall,
+// tl_dense, tl_hlog_for, tl_cap_for and the density tests of the launchers): they read density as h * w / s, and the s of a
+// window counts the Gaussians of the WHOLE grid -- so a window is judged with the live count it can expect,
+// s * (h * w) / (full_h * full_w), at least 1.  Choices registered per shape (gsasr_set_kernel_choice) are keyed on
+// whole-image shapes and are not looked up for a window: its policy dims carry a NaN cutoff, which no registered shape
+// equals (none of the rules reads the cutoff).  Layout sizes, grids and loops keep the caller's dims.
+inline gsasr_dims policy_dims(const gsasr_dims *d, const gsasr_view *v)
+{
+    gsasr_dims p = *d;
+    if (v) {
+        const double live = (double)d->s * ((double)d->h * (double)d->w) / ((double)v->full_h * (double)v->full_w);
+        p.s = d->s > 0 ? (int)std::fmax(1.0, std::floor(live)) : 0;
+        p.cutoff = NAN;
+    }
+    return p;
+}
 
 inline int classify_blocks(const gsasr_dims *d)
 {
@@ -435,9 +490,10 @@ inline int tl_cap_for(const gsasr_dims *d, int hlog)
 
 // part_k / tl_hlog / tl_cap >= 0: the values the PLAN of this workspace was made with (its note, plan_layout) -- a forward or
 // backward must lay the workspace out as its plan did, whatever kernel choice has been registered or cleared for the shape since
-inline Layout make_layout(const gsasr_dims *d, int part_k = -1, int tl_hlog = -1, int tl_cap = -1)
+inline Layout make_layout(const gsasr_dims *d, int part_k = -1, int tl_hlog = -1, int tl_cap = -1, const gsasr_view *vw = nullptr)
 {
     Layout L{};
+    const gsasr_dims pd = policy_dims(d, vw);
     L.ncx = (d->w + CELL - 1) / CELL;
     L.ncy = (d->h + CELL - 1) / CELL;
     L.ncells = L.ncx * L.ncy;
@@ -465,13 +521,13 @@ inline Layout make_layout(const gsasr_dims *d, int part_k = -1, int tl_hlog = -1
     L.off_done = o;   o += align_up(bw * 4, 256);
     L.off_bbox = o;   o += align_up(s * 32, 256);
     L.off_win = o;    o += align_up(s * 8, 256);
-    L.part_k = part_k >= 0 ? part_k : bwd_part_k(d);
+    L.part_k = part_k >= 0 ? part_k : bwd_part_k(&pd);
     L.off_part = o;   o += align_up(s * 32 * (size_t)L.part_k, 256);
     L.off_qspan = o;  o += L.part_k ? align_up(s * 16, 256) : 0;
     // tile lists LAST: a caller whose flags differ from the plan's (GSASR_FLAG_FWD_WIDE at forward time) lays out everything
     // else identically; whether the workspace carries lists, and of which tile height, is the plan's note (plan_layout)
-    L.tl_hlog = tl_hlog >= 0 ? tl_hlog : tl_hlog_for(d);
-    L.tl_cap = (tl_cap >= 0 && L.tl_hlog) ? tl_cap : tl_cap_for(d, L.tl_hlog);
+    L.tl_hlog = tl_hlog >= 0 ? tl_hlog : tl_hlog_for(&pd);
+    L.tl_cap = (tl_cap >= 0 && L.tl_hlog) ? tl_cap : tl_cap_for(&pd, L.tl_hlog);
     L.tl_ntx = (d->w + TL_W - 1) / TL_W;
     L.tl_ntiles = L.tl_hlog ? L.tl_ntx * ((d->row1 - d->row0 + (1 << L.tl_hlog) - 1) >> L.tl_hlog) : 0;
     L.off_tlc = o;    o += align_up((size_t)L.tl_ntiles * TL_STRIDE * 4, 256);
@@ -543,9 +599,12 @@ inline bool batch_uniform(const gsasr_dims *d, int &h, int &w)
     return true;
 }
 
-inline Params make_params(const gsasr_dims *d, const Layout &L)
+inline Params make_params(const gsasr_dims *d, const Layout &L, const gsasr_view *vw = nullptr)
 {
     Params P;
+    const gsasr_dims pd = policy_dims(d, vw);
+    // (sizes that set a SCALE -- the dmax box in pixels, the cells it covers -- are the full grid's under a view)
+    const double scale_w = vw ? (double)vw->full_w : (double)d->w, scale_h = vw ? (double)vw->full_h : (double)d->h;
     P.s = d->s; P.h = d->h; P.w = d->w; P.row0 = d->row0; P.row1 = d->row1;
     P.bounded = d->dmax >= 0.f;
     P.dmax = P.bounded ? d->dmax : INFINITY;
@@ -560,7 +619,7 @@ inline Params make_params(const gsasr_dims *d, const Layout &L)
     P.ext_groups = L.ext_groups;
     P.dead_off = (int)L.dead_off_words;
     {
-        double wmin = d->w, hmin = d->h;
+        double wmin = scale_w, hmin = scale_h;
         if (d->batch > 1) {
             for (int b = 0; b < d->batch; ++b) {
                 hmin = std::fmin(hmin, (double)d->sample_hw[2 * b]);
@@ -577,11 +636,12 @@ inline Params make_params(const gsasr_dims *d, const Layout &L)
     // (whole images only: "complete to 1e-5 of the Gaussian's own mass" is a statement about all of its pixels -- on a row band
     // that holds nothing but a Gaussian's tail the same truncation is a large part of THAT band's share, and a band's gradient
     // is compared and reduced on its own)
-    const bool whole = d->row0 == 0 && d->row1 == d->h;
+    // (nor under a view: a window is a band of its grid in both directions)
+    const bool whole = d->row0 == 0 && d->row1 == d->h && !vw;
     P.kb_max = (adapt && gradtau_on && whole) ? (float)(std::sqrt(2.0 * (double)GSASR_SPLAT_GRAD_TAU) * (1.0 + 1e-6)) : 0.f;
     if (P.bounded && adapt) {
         const int B = batch_of(d);
-        const double dpx = (double)d->dmax * 0.5 * (double)(d->w - 1), dpy = (double)d->dmax * 0.5 * (double)((B > 1 ? d->slot : d->h) - 1);
+        const double dpx = (double)d->dmax * 0.5 * (scale_w - 1.0), dpy = (double)d->dmax * 0.5 * ((B > 1 ? (double)d->slot : scale_h) - 1.0);
         const double cx = std::ceil(2.0 * std::floor(dpx + 1.02) / (double)CELL) + 1.0, cy = std::ceil(2.0 * std::floor(dpy + 1.02) / (double)CELL) + 1.0;
         const double cells = std::fmin(cx, (double)L.ncx) * std::fmin(cy, (double)L.ncy);
         P.adapt_cells = (float)std::fmin(cells, 1.0e9) * (1.f + 1e-6f);
@@ -596,14 +656,14 @@ inline Params make_params(const gsasr_dims *d, const Layout &L)
     P.flags = d->flags;
     constexpr unsigned BWD_ANY = GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_ATOMIC | GSASR_FLAG_BWD_HOME;
     if (!(P.flags & BWD_ANY))   // (the registered choice; the development A/B switch)
-        P.flags |= registered_choice(d).flags & (GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_HOME);
+        P.flags |= registered_choice(&pd).flags & (GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_TILE | GSASR_FLAG_BWD_HOME);
     if (!(P.flags & BWD_ANY))
         P.flags |= bwd_env() == 2 ? GSASR_FLAG_BWD_TILE : bwd_env() == 3 ? GSASR_FLAG_BWD_ATOMIC : bwd_env() == 4 ? GSASR_FLAG_BWD_HOME : 0u;
     P.batch = batch_of(d);
     P.slot = d->batch > 1 ? d->slot : d->h;
     P.nper = d->batch > 1 ? d->s / d->batch : d->s;
     P.part_k = L.part_k;
-    P.bt_hlog = bt_tall(d) ? 5 : 4;
+    P.bt_hlog = bt_tall(&pd) ? 5 : 4;
     batch_uniform(d, P.geo_h, P.geo_w);
     P.grad_rows = d->grad_rows > 0 ? d->grad_rows : P.slot;
     P.tl_hlog = L.tl_hlog; P.tl_cap = L.tl_cap; P.tl_ntx = L.tl_ntx; P.tl_ntiles = L.tl_ntiles;
@@ -612,11 +672,13 @@ inline Params make_params(const gsasr_dims *d, const Layout &L)
 }
 
 // ---- plan notes (splat_api.hip) ----
-void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap);
+void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap, const gsasr_view *vw = nullptr);
 // layout of the plan in `ws`, from the note its plan left; *noted = false when `ws` holds no plan of these dims (the layout is
 // then the dims' own, for its size only)
-Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted = nullptr);
-int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning = false);
+Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted = nullptr, const gsasr_view *vw = nullptr);
+// (vw: the view of a `_view` entry point, already through norm_view; the plan's note carries it, so a call with another view
+// -- or none -- on that workspace is GSASR_ERR_PLAN)
+int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning = false, const gsasr_view *vw = nullptr);
 
 // arguments of the 8-bit forwards (gsasr_splat_forward_u8 and the step forms, which check them before they enqueue anything)
 int u8_args_check(const gsasr_dims *dims, const unsigned char *out, int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags);
@@ -639,7 +701,10 @@ struct Box {
 
 constexpr double WINDOW_EPS = 0.02;  // px; covers every rounding between these windows and the kernels' float tests
 
-__device__ __forceinline__ Box gaussian_box(float sx, float sy, float x, float y, const Params &P, const Geo &g, float kcut)
+// (VIEW: g is the window -- what the box is clipped to -- and the pixel scale is the full grid's, view_scale)
+template <bool VIEW = false>
+__device__ __forceinline__ Box gaussian_box(float sx, float sy, float x, float y, const Params &P, const Geo &g, float kcut,
+                                            const ViewArg &vw = ViewArg{0, 0, 0, 0})
 {
     Box b;
     float ext_x = P.dmax, ext_y = P.dmax;
@@ -653,8 +718,10 @@ __device__ __forceinline__ Box gaussian_box(float sx, float sy, float x, float y
     // Evaluated in double (once per Gaussian); the float pixel table differs from the exact grid by
     // < 1e-2 px even at w = 32767, which WINDOW_EPS covers, so the window is tight to the pixel.
     // (g = the sample's own grid; its rows start at canvas row g.base.)
-    const double hx = 0.5 * (double)(g.w - 1), hy = 0.5 * (double)(g.h - 1);
-    const double cxp = ((double)x + 1.0) * hx, cyp = ((double)y + 1.0) * hy + (double)g.base;
+    const Scale sc = view_scale<VIEW>(vw, g);
+    const double hx = 0.5 * (double)(sc.gw - 1), hy = 0.5 * (double)(sc.gh - 1);
+    double cxp = ((double)x + 1.0) * hx, cyp = ((double)y + 1.0) * hy + (double)g.base;
+    if (VIEW) { cxp -= (double)sc.ox; cyp -= (double)sc.oy; }
     const double ex = (double)ext_x * hx, ey = (double)ext_y * hy;
     b.ex = (float)ex;
     b.ey = (float)ey;
@@ -956,21 +1023,21 @@ __device__ __forceinline__ unsigned bwd_gather(const Params &P, const PlanView &
 // splat_plan.hip
 int launch_batch_geo(const gsasr_dims *dims, const PlanView &V, hipStream_t st);
 int plan_impl(const float *sigmas, const float *coords, const float *colors, const gsasr_dims *dims, void *workspace,
-              size_t workspace_bytes, void *stream, const float *raw, const StepSrc &SS);
+              size_t workspace_bytes, void *stream, const float *raw, const StepSrc &SS, const gsasr_view *vw = nullptr);
 // splat_backward.hip
 int splat_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_img, float *g_sigmas,
                    float *g_coords, float *g_colors, const gsasr_dims *dims, const void *workspace, size_t workspace_bytes,
-                   void *stream, bool gather, int *mode_out);
+                   void *stream, bool gather, int *mode_out, const gsasr_view *vw = nullptr);
 // splat_backward_home.hip
 int launch_bwd_home(const Params &P, const PlanView &V, const float *grad_img, float *g_sigmas, float *g_coords, float *g_colors,
-                    int variant, hipStream_t st);
+                    int variant, hipStream_t st, const gsasr_view *vw = nullptr);
 // splat_step.hip
 struct StepLayout {
     size_t plan_bytes, off_step, off_sig, off_xy, off_col, off_gsig, off_gxy, off_gcol, off_ghwc, total;
 };
-StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws = nullptr, bool *noted = nullptr);
+StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws = nullptr, bool *noted = nullptr, const gsasr_view *vw = nullptr);
 int step_prologue_plan(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims, void *workspace,
-                       size_t workspace_bytes, void *stream, StepLayout &S);
+                       size_t workspace_bytes, void *stream, StepLayout &S, const gsasr_view *vw = nullptr);
 int prologue_backward_batched(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
                               const float *gs, const float *gc, const float *gk, float *g_parameters, void *stream);
 

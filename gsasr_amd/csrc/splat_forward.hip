@@ -1247,17 +1247,20 @@ struct U8Out {
 
 // The forward of both image forms: ONE kernel choice, so that the float and the 8-bit entry point can never render the same
 // dims with different kernels.
+// (vw: the view the plan was made with, through norm_view; null everywhere but in the `_view` entry points.  The kernels are
+// the same: a window's plan hands them what looks like a whole image of the window's size.)
 static int forward_launch(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, float *img, const U8Out *u8,
-                          void *stream)
+                          void *stream, const gsasr_view *vw = nullptr)
 {
     // (before the workspace: argument errors are reported whatever the workspace holds)
     if (u8) if (int rc = u8_args_check(dims, u8->out, u8->rows, u8->cols, u8->pitch, u8->flags)) return rc;
     Layout L;
-    if (int rc = check_ws(dims, workspace, workspace_bytes, L)) return rc;
+    if (int rc = check_ws(dims, workspace, workspace_bytes, L, false, vw)) return rc;
     const int rows = dims->row1 - dims->row0;
     if (rows == 0) return GSASR_OK;
     if (!u8 && !img) return fail(GSASR_ERR_ARG, "null image pointer");
-    Params P = make_params(dims, L);
+    Params P = make_params(dims, L, vw);
+    const gsasr_dims pd = policy_dims(dims, vw);      // what the kernel-choice rules read
     if (u8) {   // always a store, interleaved: the two image flags of the dims do not apply
         P.flags = (P.flags | GSASR_FLAG_OVERWRITE_IMAGE) & ~GSASR_FLAG_CHW_IMAGE;
         P.u8 = u8->out; P.u8_rows = u8->rows; P.u8_cols = u8->cols; P.u8_pitch = u8->pitch;
@@ -1270,9 +1273,9 @@ static int forward_launch(const gsasr_dims *dims, const void *workspace, size_t 
 #ifdef FWD_PAIR
     const bool pair = FWD_PAIR != 0;
 #else
-    const bool pair = tl_dense(dims);     // record-pair packed evaluation for dense plans (fwd_eval_pair)
+    const bool pair = tl_dense(&pd);     // record-pair packed evaluation for dense plans (fwd_eval_pair)
 #endif
-    if (fwd_wants_wide(dims)) {
+    if (fwd_wants_wide(&pd)) {
         const int wx = (dims->w + 2 * WIDE - 1) / (2 * WIDE), wy = (rows + 2 * WIDE - 1) / (2 * WIDE);
         const dim3 grid((unsigned)wx * (unsigned)wy), block(256);
         if (L.tl_ok && L.tl_hlog == 5) {    // the plan's tile lists (32 x 32-px tiles)
@@ -1280,7 +1283,7 @@ static int forward_launch(const gsasr_dims *dims, const void *workspace, size_t 
             else hipLaunchKernelGGL(k_render_fwd16_list<false>, grid, block, 0, st, P, V, img, wx);
         } else if (P.bounded) hipLaunchKernelGGL(k_render_fwd16<true>, grid, block, 0, st, P, V, img, wx);
         else hipLaunchKernelGGL(k_render_fwd16<false>, grid, block, 0, st, P, V, img, wx);
-    } else if (nsub < 4096 && !(L.tl_ok && L.tl_hlog == 4) && tl_dense(dims) && fwd_split_env()) {
+    } else if (nsub < 4096 && !(L.tl_ok && L.tl_hlog == 4) && tl_dense(&pd) && fwd_split_env()) {
         // fewer sub-tiles than half the chip's 8192 wave slots on a DENSE plan (a 192^2 training crop at 16 Gaussians per LR
         // pixel: thousands of candidates per sub-tile): split each sub-tile's Gaussian list over 2..16 waves so that about one
         // full set of waves is in flight.  Sparse small images (one Gaussian per LR pixel: a sub-tile has a few dozen hits, and
@@ -1372,6 +1375,21 @@ int gsasr_splat_forward_u8(const gsasr_dims *dims, const void *workspace, size_t
 {
     const U8Out u8{out, crop_rows, crop_cols, pitch, u8_flags};
     return forward_launch(dims, workspace, workspace_bytes, nullptr, &u8, stream);
+}
+
+int gsasr_splat_forward_view(const gsasr_dims *dims, const gsasr_view *view, const void *workspace, size_t workspace_bytes,
+                             float *img, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    return forward_launch(dims, workspace, workspace_bytes, img, nullptr, stream, norm_view(dims, view));
+}
+
+int gsasr_splat_forward_u8_view(const gsasr_dims *dims, const gsasr_view *view, const void *workspace, size_t workspace_bytes,
+                                unsigned char *out, int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    const U8Out u8{out, crop_rows, crop_cols, pitch, u8_flags};
+    return forward_launch(dims, workspace, workspace_bytes, nullptr, &u8, stream, norm_view(dims, view));
 }
 
 int gsasr_forward_subtile_width(const gsasr_dims *dims)

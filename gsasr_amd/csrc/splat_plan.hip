@@ -15,11 +15,13 @@ __global__ __launch_bounds__(64) void k_batch_geo(BatchSizes S, int batch, int s
     if (b < batch) geo[b] = make_int4((int)S.h[b], (int)S.w[b], b * slot, b * w);
 }
 
-template <bool PROLOGUE>
+// (VIEW: the plan of a window, gsasr_view -- P.h, P.w are the window, coordinates scale with the full grid: view_scale)
+template <bool PROLOGUE, bool VIEW>
 __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restrict__ sigmas,
                                                   const float *__restrict__ coords, PlanView V,
                                                   const float *__restrict__ raw, StepSrc SS,
-                                                  float *__restrict__ o_sig, float *__restrict__ o_xy, float *__restrict__ o_col)
+                                                  float *__restrict__ o_sig, float *__restrict__ o_xy, float *__restrict__ o_col,
+                                                  ViewArg VW)
 {
     __shared__ unsigned s_rx[4], s_ry[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -30,7 +32,10 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
     for (int k = i; k < P.tl_ntiles; k += (int)(gridDim.x * blockDim.x)) V.tl_cursor[(size_t)k * TL_STRIDE] = 0u;
     if (i == 0) V.hdr[2] = V.hdr[6] = V.hdr[7] = V.hdr[8] = V.hdr[9] = 0u;   // largest cell / block count: raised with atomicMax by k_scan_local / block_count_max
     // pixel-centre tables: the reference's double expression, rounded to float (gs_cuda/gs.cu:27-28)
-    if (P.batch <= 1) {
+    if (VIEW) {   // the window's slice of the full grid's tables: the same floats
+        if (i < P.w) V.px[i] = (float)(2.0 * (double)(VW.x0 + i) / (double)(VW.fw - 1) - 1.0);
+        if (i < P.h) V.py[i] = (float)(2.0 * (double)(VW.y0 + i) / (double)(VW.fh - 1) - 1.0);
+    } else if (P.batch <= 1) {
         if (i < P.w) V.px[i] = (float)(2.0 * (double)i / (double)(P.w - 1) - 1.0);
         if (i < P.h) V.py[i] = (float)(2.0 * (double)i / (double)(P.h - 1) - 1.0);
     } else {  // one px table per sample, py over the canvas rows: each sample's own grid (padding continues it)
@@ -40,6 +45,7 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
     unsigned rx = 0, ry = 0, key = 0xffffffffu;
     if (i < P.s) {
         const Geo g = sample_geo(P, V, P.batch > 1 ? i / P.nper : 0);
+        const Scale sc = view_scale<VIEW>(VW, g);
         float sx, sy, x, y;
         if (PROLOGUE) {
             float o[8];
@@ -58,7 +64,7 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
                 step = SS.step[smp];
                 if (i == smp * P.nper) SS.keep[smp] = step;
             }
-            prologue_one(raw + (size_t)i * 9, step, g.h, g.w, o);
+            prologue_one(raw + (size_t)i * 9, step, sc.gh, sc.gw, o);
             o_sig[i * 3 + 0] = o[0]; o_sig[i * 3 + 1] = o[1]; o_sig[i * 3 + 2] = o[2];
             o_xy[i * 2 + 0] = o[3]; o_xy[i * 2 + 1] = o[4];
             o_col[i * 3 + 0] = o[5]; o_col[i * 3 + 1] = o[6]; o_col[i * 3 + 2] = o[7];
@@ -68,7 +74,7 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
             sx = sigmas[i3 + 0]; sy = sigmas[i3 + 1];
             x = coords[i2 + 0]; y = coords[i2 + 1];
         }
-        const Box b = gaussian_box(sx, sy, x, y, P, g, P.kcut);
+        const Box b = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kcut, VW);
         if (b.cls == 2) {
             // NDEAD counters instead of one: a row band of a large image sees most of the Gaussians here, and one
             // returning atomic per wave on a single word serialises (203 us for 1 M Gaussians, 7/8 dead)
@@ -76,9 +82,10 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
         } else if (b.cls == 1) {
             key = (unsigned)P.ncells;
         } else {
-            const float hx = 0.5f * (float)(g.w - 1), hy = 0.5f * (float)(g.h - 1);
-            int cx = (int)fminf(fmaxf(floorf((x + 1.f) * hx), 0.f), (float)(g.w - 1)) >> CELL_SHIFT;
-            int cy = ((int)fminf(fmaxf(floorf((y + 1.f) * hy), 0.f), (float)(g.h - 1)) + g.base) >> CELL_SHIFT;
+            const float hx = 0.5f * (float)(sc.gw - 1), hy = 0.5f * (float)(sc.gh - 1);
+            // (a centre outside the grid -- or, VIEW, outside the window -- is binned in the border cell)
+            int cx = (int)fminf(fmaxf(floorf((x + 1.f) * hx) - (float)sc.ox, 0.f), (float)(g.w - 1)) >> CELL_SHIFT;
+            int cy = ((int)fminf(fmaxf(floorf((y + 1.f) * hy) - (float)sc.oy, 0.f), (float)(g.h - 1)) + g.base) >> CELL_SHIFT;
             key = (unsigned)(cy * P.ncx + cx);
             rx = (unsigned)ceilf(b.ex) + 2u;
             ry = (unsigned)ceilf(b.ey) + 2u;
@@ -432,10 +439,10 @@ constexpr int FUSED_PER_THREAD = 17, FUSED_CELLS = 256 * FUSED_PER_THREAD;
 static_assert(FUSED_CELLS == FUSED_CELLS_HOST, "make_params decides with FUSED_CELLS_HOST which plans run a scan kernel");
 
 // TLH: the plan's tile lists -- 0 none, else log2 of the tile height (4 / 5)
-template <bool FUSED_SCAN, int TLH>
+template <bool FUSED_SCAN, int TLH, bool VIEW>
 __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__ sigmas,
                                              const float *__restrict__ coords,
-                                             const float *__restrict__ colors, PlanView V, int nblk)
+                                             const float *__restrict__ colors, PlanView V, int nblk, ViewArg VW)
 {
     __shared__ unsigned s_start[FUSED_SCAN ? FUSED_CELLS + 1 : 1];
     __shared__ unsigned s_part[FUSED_SCAN ? 256 : 1];
@@ -532,13 +539,14 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
     if (valid) {
         const int smp = P.batch > 1 ? i / P.nper : 0;
         const Geo g = sample_geo(P, V, smp);
-        Box b = gaussian_box(sx, sy, x, y, P, g, kc);
+        const Scale sc = view_scale<VIEW>(VW, g);
+        Box b = gaussian_box<VIEW>(sx, sy, x, y, P, g, kc, VW);
         // A Gaussian k_classify kept (with the conservative cutoff) whose window under the smaller cutoff holds no pixel keeps
         // its conservative window: every consumer finds a non-empty window behind a live key, and the classes' extents
         // (header words 0, 1: the conservative ones) cover it.
         float kw = kc;
         if (b.cls == 2 && key <= (unsigned)P.ncells && kc != P.kcut) {
-            b = gaussian_box(sx, sy, x, y, P, g, P.kcut);
+            b = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kcut, VW);
             kw = P.kcut;
             if (key < (unsigned)P.ncells) {   // (normal class: the tiles must search as far as this conservative window reaches)
                 fb_rx = (unsigned)ceilf(b.ex) + 2u;
@@ -574,7 +582,7 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
                            __uint_as_float((unsigned)i));
         // does a pixel of a tile this Gaussian is binned to ever need the dmax test?  Not if its support box
         // lies inside its dmax box: pixels beyond the support box carry < exp(-tau) whether tested or not.
-        const float hx = 0.5f * (float)(g.w - 1), hy = 0.5f * (float)(g.h - 1);
+        const float hx = 0.5f * (float)(sc.gw - 1), hy = 0.5f * (float)(sc.gh - 1);
         const bool needs_test = P.bounded && !(kw > 0.f && kw * fabsf(sx) * hx + 1.f <= P.dmax * hx &&
                                                kw * fabsf(sy) * hy + 1.f <= P.dmax * hy);
         if (b.cls == 2) {
@@ -593,7 +601,8 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
                 // chain is k_bin's run time; an ulp of a <= 128 px offset is far inside WINDOW_EPS.  Only the absolute
                 // pixel coordinates stay in double.)
                 const float spx = sx * hx, spy = sy * hy;                     // sigmas in pixels
-                const double cxp = ((double)x + 1.0) * (double)hx, cyp = ((double)y + 1.0) * (double)hy + (double)g.base;
+                double cxp = ((double)x + 1.0) * (double)hx, cyp = ((double)y + 1.0) * (double)hy + (double)g.base;
+                if (VIEW) { cxp -= (double)sc.ox; cyp -= (double)sc.oy; }
                 const float tau = 0.5f * kw * kw;
                 const float omr = (float)(1.0 - dr * dr);
                 const float iq = 1.f / (omr * spx * spy);
@@ -654,7 +663,7 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
                 Box w = b;
                 bool test_b = needs_test;
                 if (P.kb_max > 0.f && kw > P.kb_max) {
-                    const Box t = gaussian_box(sx, sy, x, y, P, g, P.kb_max);
+                    const Box t = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kb_max, VW);
                     if (t.cls != 2) {
                         w = t;
                         test_b = P.bounded && !(P.kb_max * fabsf(sx) * hx + 1.f <= P.dmax * hx && P.kb_max * fabsf(sy) * hy + 1.f <= P.dmax * hy);
@@ -791,35 +800,41 @@ int launch_batch_geo(const gsasr_dims *dims, const PlanView &V, hipStream_t st)
 // The plan: [memset of this parity's counters unless the caller vouches for them] -> classify (with the host prologue
 // fused in when `raw` is given: sigmas/coords/colors are then OUTPUTS) -> [scan] -> bin.
 int plan_impl(const float *sigmas, const float *coords, const float *colors, const gsasr_dims *dims, void *workspace,
-              size_t workspace_bytes, void *stream, const float *raw, const StepSrc &SS)
+              size_t workspace_bytes, void *stream, const float *raw, const StepSrc &SS, const gsasr_view *vw)
 {
     Layout L;
-    if (int rc = check_ws(dims, workspace, workspace_bytes, L, true)) return rc;
-    note_plan(workspace, dims, L.total, L.part_k, L.tl_hlog, L.tl_cap);
+    if (int rc = check_ws(dims, workspace, workspace_bytes, L, true, vw)) return rc;
+    note_plan(workspace, dims, L.total, L.part_k, L.tl_hlog, L.tl_cap, vw);
     if (dims->s > 0 && (!sigmas || !coords || !colors)) return fail(GSASR_ERR_ARG, "null input pointer");
     hipStream_t st = (hipStream_t)stream;
-    const Params P = make_params(dims, L);
+    const Params P = make_params(dims, L, vw);
     const PlanView V = make_view(L, workspace, dims->flags);
+    const ViewArg VW = view_arg(vw);
     if (!(dims->flags & GSASR_FLAG_COUNTERS_CLEAN)) HIP_TRY(hipMemsetAsync(V.cell_count, 0, L.count_bytes, st));
     if (!raw)
         if (int rc = launch_batch_geo(dims, V, st)) return rc;   // (a step call has published the geometry already)
     const int nblk = classify_blocks(dims);
-    if (raw)
-        hipLaunchKernelGGL(k_classify<true>, dim3(nblk), dim3(256), 0, st, P, sigmas, coords, V, raw, SS,
-                           const_cast<float *>(sigmas), const_cast<float *>(coords), const_cast<float *>(colors));
-    else
-        hipLaunchKernelGGL(k_classify<false>, dim3(nblk), dim3(256), 0, st, P, sigmas, coords, V, (const float *)nullptr,
-                           SS, (float *)nullptr, (float *)nullptr, (float *)nullptr);
+#define GSASR_CLASSIFY(ISVIEW) do { \
+    if (raw) \
+        hipLaunchKernelGGL((k_classify<true, ISVIEW>), dim3(nblk), dim3(256), 0, st, P, sigmas, coords, V, raw, SS, \
+                           const_cast<float *>(sigmas), const_cast<float *>(coords), const_cast<float *>(colors), VW); \
+    else \
+        hipLaunchKernelGGL((k_classify<false, ISVIEW>), dim3(nblk), dim3(256), 0, st, P, sigmas, coords, V, (const float *)nullptr, \
+                           SS, (float *)nullptr, (float *)nullptr, (float *)nullptr, VW); } while (0)
+    if (vw) GSASR_CLASSIFY(true);
+    else GSASR_CLASSIFY(false);
+#undef GSASR_CLASSIFY
     const int ncls = L.ncells + 1 + NDEAD;
     const unsigned nbin = (unsigned)((dims->s + 255) / 256);
     static const int fused_max_blocks = dev_switch("GSASR_SPLAT_FUSED_MAX") ? atoi(dev_switch("GSASR_SPLAT_FUSED_MAX")) : FUSED_MAX_BLOCKS;
     if (ncls <= FUSED_CELLS && dims->s > 0 && (int)nbin <= fused_max_blocks) {
         // small grid, not too many blocks: k_bin rebuilds the scan per block (no separate scan launch)
-#define GSASR_BIN(F) do { \
+#define GSASR_BIN_V(F, ISVIEW) do { \
         const int tlh = P.tl_hlog; \
-        if (tlh == 5) hipLaunchKernelGGL((k_bin<F, 5>), dim3(nbin), dim3(256), 0, st, P, sigmas, coords, colors, V, L.ext_groups); \
-        else if (tlh == 4) hipLaunchKernelGGL((k_bin<F, 4>), dim3(nbin), dim3(256), 0, st, P, sigmas, coords, colors, V, L.ext_groups); \
-        else hipLaunchKernelGGL((k_bin<F, 0>), dim3(nbin), dim3(256), 0, st, P, sigmas, coords, colors, V, L.ext_groups); } while (0)
+        if (tlh == 5) hipLaunchKernelGGL((k_bin<F, 5, ISVIEW>), dim3(nbin), dim3(256), 0, st, P, sigmas, coords, colors, V, L.ext_groups, VW); \
+        else if (tlh == 4) hipLaunchKernelGGL((k_bin<F, 4, ISVIEW>), dim3(nbin), dim3(256), 0, st, P, sigmas, coords, colors, V, L.ext_groups, VW); \
+        else hipLaunchKernelGGL((k_bin<F, 0, ISVIEW>), dim3(nbin), dim3(256), 0, st, P, sigmas, coords, colors, V, L.ext_groups, VW); } while (0)
+#define GSASR_BIN(F) do { if (vw) GSASR_BIN_V(F, true); else GSASR_BIN_V(F, false); } while (0)
         GSASR_BIN(true);
     } else {
         if (ncls <= 2 * SCAN_CHUNK) {
@@ -834,6 +849,7 @@ int plan_impl(const float *sigmas, const float *coords, const float *colors, con
         }
         if (dims->s > 0) GSASR_BIN(false);
 #undef GSASR_BIN
+#undef GSASR_BIN_V
     }
     HIP_TRY(hipGetLastError());
     return GSASR_OK;
@@ -847,6 +863,12 @@ int gsasr_splat_plan(const float *sigmas, const float *coords, const float *colo
                      void *workspace, size_t workspace_bytes, void *stream)
 {
     return plan_impl(sigmas, coords, colors, dims, workspace, workspace_bytes, stream, nullptr, StepSrc{});
+}
+
+int gsasr_splat_plan_view(const float *sigmas, const float *coords, const float *colors, const gsasr_dims *dims,
+                          const gsasr_view *view, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return plan_impl(sigmas, coords, colors, dims, workspace, workspace_bytes, stream, nullptr, StepSrc{}, norm_view(dims, view));
 }
 
 }  // extern "C"

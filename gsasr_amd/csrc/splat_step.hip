@@ -142,13 +142,13 @@ int gsasr_prologue_backward(const float *gs_parameters, const float *step_size, 
 }  // extern "C"
 
 namespace gsasr_detail {
-StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws, bool *noted)
+StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws, bool *noted, const gsasr_view *vw)
 {
     StepLayout S;
     const size_t n = (size_t)d->s;
     // (the plan's own slot count and lists: plan_layout -- the scratch behind them stays where the step's plan put it, whatever
     // the registry holds now)
-    S.plan_bytes = (planned_ws ? plan_layout(d, planned_ws, noted) : make_layout(d)).total;
+    S.plan_bytes = (planned_ws ? plan_layout(d, planned_ws, noted, vw) : make_layout(d, -1, -1, -1, vw)).total;
     size_t o = S.plan_bytes;
     S.off_step = o; o += align_up(GSASR_MAX_BATCH * 4, 256);   // the step size of every sample, as the prologue used it
     S.off_sig = o;  o += align_up(n * 12, 256);
@@ -192,16 +192,26 @@ size_t gsasr_step_workspace_bytes(const gsasr_dims *dims)
     return make_step_layout(dims).total;
 }
 
+size_t gsasr_step_workspace_bytes_view(const gsasr_dims *dims, const gsasr_view *view)
+{
+    if (!view_ok(dims, view)) {
+        fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+        return 0;
+    }
+    return make_step_layout(dims, nullptr, nullptr, norm_view(dims, view)).total;
+}
+
 }  // extern "C"
 
 namespace gsasr_detail {
 // prologue (per-sample sizes and step sizes on a batched canvas) + plan of a whole-step call
 int step_prologue_plan(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims, void *workspace,
-                       size_t workspace_bytes, void *stream, StepLayout &S)
+                       size_t workspace_bytes, void *stream, StepLayout &S, const gsasr_view *vw)
 {
     if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims");
+    if (!view_ok(dims, vw)) return fail(GSASR_ERR_ARG, VIEW_ERR);
     if (dims->flags & GSASR_FLAG_STRIDE8) return fail(GSASR_ERR_ARG, "GSASR_FLAG_STRIDE8 does not apply to the step entry points");
-    S = make_step_layout(dims);
+    S = make_step_layout(dims, nullptr, nullptr, vw);
     if (!workspace || ((uintptr_t)workspace & 255u) || workspace_bytes < S.total)
         return fail(GSASR_ERR_WORKSPACE, "workspace null, misaligned or smaller than gsasr_step_workspace_bytes()");
     char *b = (char *)workspace;
@@ -214,32 +224,70 @@ int step_prologue_plan(const float *gs_parameters, StepSrc SS, const gsasr_dims 
         if (int rc = launch_batch_geo(dims, V, (hipStream_t)stream)) return rc;
     }
     // (the prologue runs inside the plan's first kernel: k_classify<true>)
-    return plan_impl(sig, xy, col, dims, workspace, S.plan_bytes, stream, dims->s > 0 ? gs_parameters : nullptr, SS);
+    return plan_impl(sig, xy, col, dims, workspace, S.plan_bytes, stream, dims->s > 0 ? gs_parameters : nullptr, SS, vw);
 }
 }  // namespace gsasr_detail
+
+extern "C" {
+
+}  // extern "C"
+
+namespace {
+
+// The step forwards, all forms: step size from a device float or (sm) from the caller's scale_modify pairs; float image or (u8 =
+// true) the 8-bit one; of a whole image / band / canvas or (view, through norm_view) of a window of its grid.
+struct StepU8 { bool on; unsigned char *out; int rows, cols; size_t pitch; unsigned flags; };
+
+int step_forward(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims, const gsasr_view *vw, void *workspace,
+                 size_t workspace_bytes, float *img, const StepU8 &u8, void *stream)
+{
+    if (u8.on) if (int rc = u8_args_check(dims, u8.out, u8.rows, u8.cols, u8.pitch, u8.flags)) return rc;
+    StepLayout S;
+    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S, vw)) return rc;
+    if (vw) {
+        if (u8.on) return gsasr_splat_forward_u8_view(dims, vw, workspace, S.plan_bytes, u8.out, u8.rows, u8.cols, u8.pitch, u8.flags, stream);
+        return gsasr_splat_forward_view(dims, vw, workspace, S.plan_bytes, img, stream);
+    }
+    if (u8.on) return gsasr_splat_forward_u8(dims, workspace, S.plan_bytes, u8.out, u8.rows, u8.cols, u8.pitch, u8.flags, stream);
+    return gsasr_splat_forward(dims, workspace, S.plan_bytes, img, stream);
+}
+
+StepSrc step_src(const float *step_size)
+{
+    StepSrc SS{};
+    SS.step = step_size;
+    return SS;
+}
+
+StepSrc step_src_sm(const float *scale_modify, int sm_stride, float default_step_size, int *mismatch)
+{
+    StepSrc SS{};
+    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
+    return SS;
+}
+
+constexpr StepU8 NO_U8{false, nullptr, 0, 0, 0, 0u};
+
+int step_backward(const float *gs_parameters, const float *step_size, const float *grad_img, float *g_parameters,
+                  const gsasr_dims *dims, const gsasr_view *vw, void *workspace, size_t workspace_bytes, void *stream);
+
+}  // namespace
 
 extern "C" {
 
 int gsasr_step_forward(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
                        size_t workspace_bytes, float *img, void *stream)
 {
-    StepLayout S;
-    StepSrc SS{};
-    SS.step = step_size;
-    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S)) return rc;
-    return gsasr_splat_forward(dims, workspace, S.plan_bytes, img, stream);
+    return step_forward(gs_parameters, step_src(step_size), dims, nullptr, workspace, workspace_bytes, img, NO_U8, stream);
 }
 
 int gsasr_step_forward_sm(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
                           int *mismatch, const gsasr_dims *dims, void *workspace, size_t workspace_bytes, float *img,
                           void *stream)
 {
-    StepLayout S;
-    StepSrc SS{};
-    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
     if (!scale_modify && dims && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
-    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S)) return rc;
-    return gsasr_splat_forward(dims, workspace, S.plan_bytes, img, stream);
+    return step_forward(gs_parameters, step_src_sm(scale_modify, sm_stride, default_step_size, mismatch), dims, nullptr, workspace,
+                        workspace_bytes, img, NO_U8, stream);
 }
 
 // the 8-bit forms: the same prologue + plan, ending in gsasr_splat_forward_u8
@@ -247,12 +295,8 @@ int gsasr_step_forward_u8(const float *gs_parameters, const float *step_size, co
                           size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
                           unsigned u8_flags, void *stream)
 {
-    if (int rc = u8_args_check(dims, out, crop_rows, crop_cols, pitch, u8_flags)) return rc;
-    StepLayout S;
-    StepSrc SS{};
-    SS.step = step_size;
-    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S)) return rc;
-    return gsasr_splat_forward_u8(dims, workspace, S.plan_bytes, out, crop_rows, crop_cols, pitch, u8_flags, stream);
+    return step_forward(gs_parameters, step_src(step_size), dims, nullptr, workspace, workspace_bytes, nullptr,
+                        StepU8{true, out, crop_rows, crop_cols, pitch, u8_flags}, stream);
 }
 
 int gsasr_step_forward_sm_u8(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
@@ -260,22 +304,76 @@ int gsasr_step_forward_sm_u8(const float *gs_parameters, const float *scale_modi
                              unsigned char *out, int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags, void *stream)
 {
     if (int rc = u8_args_check(dims, out, crop_rows, crop_cols, pitch, u8_flags)) return rc;
-    StepLayout S;
-    StepSrc SS{};
-    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
     if (!scale_modify && dims && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
-    if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S)) return rc;
-    return gsasr_splat_forward_u8(dims, workspace, S.plan_bytes, out, crop_rows, crop_cols, pitch, u8_flags, stream);
+    return step_forward(gs_parameters, step_src_sm(scale_modify, sm_stride, default_step_size, mismatch), dims, nullptr, workspace,
+                        workspace_bytes, nullptr, StepU8{true, out, crop_rows, crop_cols, pitch, u8_flags}, stream);
+}
+
+// the same of a window of the grid (include/gsasr_splat.h: gsasr_view)
+int gsasr_step_forward_view(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, const gsasr_view *view,
+                            void *workspace, size_t workspace_bytes, float *img, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    return step_forward(gs_parameters, step_src(step_size), dims, norm_view(dims, view), workspace, workspace_bytes, img, NO_U8, stream);
+}
+
+int gsasr_step_forward_sm_view(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
+                               int *mismatch, const gsasr_dims *dims, const gsasr_view *view, void *workspace,
+                               size_t workspace_bytes, float *img, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    if (!scale_modify && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
+    return step_forward(gs_parameters, step_src_sm(scale_modify, sm_stride, default_step_size, mismatch), dims, norm_view(dims, view),
+                        workspace, workspace_bytes, img, NO_U8, stream);
+}
+
+int gsasr_step_forward_u8_view(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, const gsasr_view *view,
+                               void *workspace, size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols,
+                               size_t pitch, unsigned u8_flags, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    return step_forward(gs_parameters, step_src(step_size), dims, norm_view(dims, view), workspace, workspace_bytes, nullptr,
+                        StepU8{true, out, crop_rows, crop_cols, pitch, u8_flags}, stream);
+}
+
+int gsasr_step_forward_sm_u8_view(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
+                                  int *mismatch, const gsasr_dims *dims, const gsasr_view *view, void *workspace,
+                                  size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
+                                  unsigned u8_flags, void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    if (int rc = u8_args_check(dims, out, crop_rows, crop_cols, pitch, u8_flags)) return rc;
+    if (!scale_modify && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
+    return step_forward(gs_parameters, step_src_sm(scale_modify, sm_stride, default_step_size, mismatch), dims, norm_view(dims, view),
+                        workspace, workspace_bytes, nullptr, StepU8{true, out, crop_rows, crop_cols, pitch, u8_flags}, stream);
 }
 
 int gsasr_step_backward(const float *gs_parameters, const float *step_size, const float *grad_img,
                         float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
                         void *stream)
 {
+    return step_backward(gs_parameters, step_size, grad_img, g_parameters, dims, nullptr, workspace, workspace_bytes, stream);
+}
+
+int gsasr_step_backward_view(const float *gs_parameters, const float *step_size, const float *grad_img, float *g_parameters,
+                             const gsasr_dims *dims, const gsasr_view *view, void *workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    if (!view_ok(dims, view)) return fail(GSASR_ERR_ARG, dims_ok(dims) ? VIEW_ERR : "bad dims");
+    return step_backward(gs_parameters, step_size, grad_img, g_parameters, dims, norm_view(dims, view), workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int step_backward(const float *gs_parameters, const float *step_size, const float *grad_img, float *g_parameters,
+                  const gsasr_dims *dims, const gsasr_view *vw, void *workspace, size_t workspace_bytes, void *stream)
+{
     if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims");
     if (dims->flags & GSASR_FLAG_STRIDE8) return fail(GSASR_ERR_ARG, "GSASR_FLAG_STRIDE8 does not apply to the step entry points");
     bool noted = false;
-    const StepLayout S = make_step_layout(dims, workspace, &noted);
+    const StepLayout S = make_step_layout(dims, workspace, &noted, vw);
     if (!workspace || ((uintptr_t)workspace & 255u) || workspace_bytes < S.total)
         return fail(GSASR_ERR_WORKSPACE, "workspace null, misaligned or smaller than gsasr_step_workspace_bytes()");
     if (!noted) return fail(GSASR_ERR_PLAN, "the workspace holds no step forward of these dims (run it, or run it again, first)");
@@ -299,14 +397,16 @@ int gsasr_step_backward(const float *gs_parameters, const float *step_size, cons
         if (!(d.flags & GSASR_FLAG_BWD_HOME)) d.flags |= GSASR_FLAG_BWD_GAUSSIAN;      // (the home-tile kernel sweeps interleaved gradients too)
     }
     int mode = 0;
-    if (int rc = splat_backward(sig, xy, col, grad_img, gs, gc, gk, &d, workspace, S.plan_bytes, stream, false, &mode)) return rc;
+    if (int rc = splat_backward(sig, xy, col, grad_img, gs, gc, gk, &d, workspace, S.plan_bytes, stream, false, &mode, vw)) return rc;
     if (dims->s == 0) return GSASR_OK;
     if (!gs_parameters || !step_size || !g_parameters) return fail(GSASR_ERR_ARG, "null pointer");
     const dim3 grid((unsigned)((dims->s + 255) / 256)), block(256);
     if (mode == 1 || mode == 2) {   // tile-stationary: gather of the slots + chain rule in one kernel
-        const Layout L = plan_layout(dims, workspace);
+        const Layout L = plan_layout(dims, workspace, nullptr, vw);
         const PlanView V = make_view(L, workspace);
-        hipLaunchKernelGGL(k_prologue_bwd_gather, grid, block, 0, (hipStream_t)stream, make_params(&d, L), V, (int)(mode == 2 || d.row1 == d.row0),
+        Params Pg = make_params(&d, L, vw);
+        if (vw) { Pg.h = vw->full_h; Pg.w = vw->full_w; }      // (the chain rule's align-corners factors: the full grid's; the gather reads no size)
+        hipLaunchKernelGGL(k_prologue_bwd_gather, grid, block, 0, (hipStream_t)stream, Pg, V, (int)(mode == 2 || d.row1 == d.row0),
                            gs_parameters, step_size, g_parameters);
         HIP_TRY(hipGetLastError());
         return GSASR_OK;
@@ -314,7 +414,8 @@ int gsasr_step_backward(const float *gs_parameters, const float *step_size, cons
     if (dims->batch > 1) {
         return prologue_backward_batched(gs_parameters, step_size, dims, workspace, gs, gc, gk, g_parameters, stream);
     }
-    return gsasr_prologue_backward(gs_parameters, step_size, dims->s, dims->h, dims->w, gs, gc, gk, g_parameters, stream);
+    return gsasr_prologue_backward(gs_parameters, step_size, dims->s, vw ? vw->full_h : dims->h, vw ? vw->full_w : dims->w, gs, gc, gk,
+                                   g_parameters, stream);
 }
 
-}  // extern "C"
+}  // namespace

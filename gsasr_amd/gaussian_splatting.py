@@ -213,8 +213,17 @@ class _FusedStep(torch.autograd.Function):
 
     @staticmethod
     @fp32_boundary_fwd
-    def forward(ctx, gs_parameters, step, H, W, dmax, scale_modify=None, default_step=1.2, extra_flags=0):
+    def forward(ctx, gs_parameters, step, H, W, dmax, scale_modify=None, default_step=1.2, extra_flags=0, window=None):
         from . import _cabi
+        if window is not None:      # the h x w window at (y0, x0) of the H x W grid (generate_2D_gaussian_splatting_view)
+            y0, x0, h, w = window
+            # (the backward kernel for the Gaussians the window can expect, as the library judges a view; no registered choice)
+            live = max(1, gs_parameters.shape[0] * (h * w) // (H * W))
+            flags = _plan_flags(ctx.needs_input_grad[0], _backward_kernel(h * w, live)) | int(extra_flags)
+            img, plan = _cabi.step_forward(gs_parameters, step, h, w, dmax, flags, scale_modify, default_step, view=(H, W, y0, x0))
+            ctx.save_for_backward(gs_parameters, step)
+            ctx.plan = plan
+            return img
         # the planar gradient autograd hands back goes to the C call as it is (GSASR_FLAG_CHW_GRAD): the
         # tile-stationary backward stages the planes directly, the Gaussian-stationary one behind one interleaving
         # kernel inside the same call -- no torch permute / allocation on the host path either way
@@ -231,7 +240,7 @@ class _FusedStep(torch.autograd.Function):
         from . import _cabi
         gs_parameters, step = ctx.saved_tensors
         g = _cabi.step_backward(ctx.plan, gs_parameters, step, grad_output.contiguous(), chw=True)
-        return g, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None
 
 
 class _FusedStepSampled(torch.autograd.Function):
@@ -549,20 +558,24 @@ def quantise_uint8(image, crop=None, bgr=False):
 
 
 def generate_2D_gaussian_splatting_step_uint8(sr_size, gs_parameters, scale, scale_modify, default_step_size=1.2,
-                                              mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, crop=None, bgr=False):
+                                              mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, crop=None, bgr=False,
+                                              window=None):
     """`generate_2D_gaussian_splatting_step` for inference, handing over the picture instead of the tensor: uint8
     `[crop_h, crop_w, 3]` = `quantise_uint8` of the `[3,H,W]` image, i.e. the reference's
     `x[:, :, :gt_h, :gt_w] -> clamp_(0, 1) -> HWC -> (x * 255.0).round().astype(uint8)` in the call itself.  On CUDA tensors
     the forward kernels store the bytes directly (gsasr_step_forward_u8: no float image, a forward-only plan, no autograd
     graph) and there is no other path: anything the fused call cannot take raises.  On CPU tensors the image of
     `rendering_python` is quantised with torch ops.  `crop` = (rows, cols) of the top-left corner (default: everything),
-    `bgr`: b, g, r byte order (cv2.imwrite)."""
+    `bgr`: b, g, r byte order (cv2.imwrite).  `window` = (y0, x0, h, w): that window of the `sr_size` grid only
+    (`generate_2D_gaussian_splatting_view`); `crop` and `bgr` then apply to the window."""
     if gs_parameters.dtype != torch.float32:
         gs_parameters = gs_parameters.float()
     H, W = _hw(sr_size)
-    crop = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
-    if not (1 <= crop[0] <= H and 1 <= crop[1] <= W):
-        raise ValueError(f"crop-{crop} must lie inside sr_size-{(H, W)}")
+    y0, x0, h, w = (0, 0, H, W) if window is None else _window(window, H, W)
+    view = None if window is None else (H, W, y0, x0)
+    crop = (h, w) if crop is None else (int(crop[0]), int(crop[1]))
+    if not (1 <= crop[0] <= h and 1 <= crop[1] <= w):
+        raise ValueError(f"crop-{crop} must lie inside " + (f"sr_size-{(H, W)}" if window is None else f"window-{(y0, x0, h, w)}"))
     if gs_parameters.is_cuda:
         if not _fused_ok(gs_parameters):
             raise RuntimeError("generate_2D_gaussian_splatting_step_uint8 needs gs_parameters [N,9] on the GPU (no fallback)")
@@ -570,16 +583,58 @@ def generate_2D_gaussian_splatting_step_uint8(sr_size, gs_parameters, scale, sca
         step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=True)
         dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
         dm = None if dmax_eff is None else float(dmax_eff)
-        gp, flags = gs_parameters.detach().contiguous(), _forward_flag(scale, H, W)
+        gp, flags = gs_parameters.detach().contiguous(), _forward_flag(scale, h, w)
         if step_size.__class__ is _StepSource:
-            out, _ = _cabi.step_forward_u8(gp, None, H, W, dm, crop, bgr, None, flags, step_size.scale_modify, step_size.default_step)
+            out, _ = _cabi.step_forward_u8(gp, None, h, w, dm, crop, bgr, None, flags, step_size.scale_modify, step_size.default_step, view)
             deferred_asserts.watch(gp.device)      # (after the launch: a look covers this call's own pair)
             return out
-        return _cabi.step_forward_u8(gp, _step_tensor(step_size, gp.device), H, W, dm, crop, bgr, None, flags)[0]
+        return _cabi.step_forward_u8(gp, _step_tensor(step_size, gp.device), h, w, dm, crop, bgr, None, flags, view=view)[0]
     step_size = _step_size(scale, scale_modify, default_step_size, mode)
     sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
     image = rendering_python(sigma_x, sigma_y, rho, coords, colours_with_alpha, sr_size, step_size, device=sigma_x.device)
-    return quantise_uint8(image, crop, bgr)
+    return quantise_uint8(image[:, y0:y0 + h, x0:x0 + w], crop, bgr)
+
+
+def _window(window, H: int, W: int):
+    """`window` = (y0, x0, h, w) on the H x W grid, checked: at least 2 x 2 pixels, inside the grid"""
+    try:
+        y0, x0, h, w = (int(v) for v in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"window-{window} must be (y0, x0, h, w)") from None
+    if not (h >= 2 and w >= 2 and 0 <= y0 and y0 + h <= H and 0 <= x0 and x0 + w <= W):
+        raise ValueError(f"window-{(y0, x0, h, w)} must be at least 2 x 2 pixels and lie inside sr_size-{(H, W)}")
+    return y0, x0, h, w
+
+
+def generate_2D_gaussian_splatting_view(sr_size, gs_parameters, scale, scale_modify, window, default_step_size=1.2,
+                                        cuda_rendering=True, mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25):
+    """`generate_2D_gaussian_splatting_step(...)[:, y0:y0+h, x0:x0+w]` for `window` = (y0, x0, h, w) on the `sr_size` grid,
+    without the rest of the image: `[3, h, w]`, differentiable.  GSASR is arbitrary-scale -- a 1024 x 1024 look into a x30
+    grid should cost what the window costs.  On CUDA tensors the fused step plans, renders and differentiates the window only
+    (gsasr_step_forward_view: every pixel sits at its full-grid coordinate, same box test and cutoff rules; the plan still
+    classifies all the Gaussians) and there is no other path; `dmax_mode` resolves against `sr_size`, not the window.  On CPU
+    tensors, or with `cuda_rendering=False`, the slice of `rendering_python`'s image is returned."""
+    if gs_parameters.dtype != torch.float32:
+        gs_parameters = gs_parameters.float()
+    H, W = _hw(sr_size)
+    y0, x0, h, w = _window(window, H, W)
+    fused = cuda_rendering and gs_parameters.is_cuda
+    if fused and not _fused_ok(gs_parameters):
+        raise RuntimeError("generate_2D_gaussian_splatting_view needs gs_parameters [N,9] on the GPU (no fallback)")
+    step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=fused)
+    if not fused:
+        sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
+        image = rendering_python(sigma_x, sigma_y, rho, coords, colours_with_alpha, sr_size, step_size, device=sigma_x.device)
+        return image[:, y0:y0 + h, x0:x0 + w]
+    dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
+    dm = None if dmax_eff is None else float(dmax_eff)
+    gp, win = gs_parameters.contiguous(), (y0, x0, h, w)
+    # (the scale hint of the forward kernel reads the window's size: that is the image the kernels render)
+    if step_size.__class__ is _StepSource:
+        out = _FusedStep.apply(gp, None, H, W, dm, step_size.scale_modify, step_size.default_step, _forward_flag(scale, h, w), win)
+        deferred_asserts.watch(gp.device)      # (after the launch: a look covers this call's own pair)
+        return out
+    return _FusedStep.apply(gp, _step_tensor(step_size, gp.device), H, W, dm, None, 1.2, _forward_flag(scale, h, w), win)
 
 
 class _FusedBatch(torch.autograd.Function):

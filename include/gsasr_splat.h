@@ -279,6 +279,62 @@ GSASR_API int gsasr_step_backward(const float *gs_parameters, const float *step_
                         float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
                         void *stream);
 
+/* A rectangular window of the HR grid.  GSASR is arbitrary-scale: the reference's demo offers scale factors up to x30, and a
+ * caller who looks at part of such a grid should pay for that part.  The `_view` entry points render -- and differentiate
+ * through -- the dims.h x dims.w pixels whose first one is pixel (y0, x0) of a full_h x full_w grid:
+ *
+ *   dims      the WINDOW as one whole image: h, w >= 2 its size, row0 = 0, row1 = h, batch = 0; s, dmax, cutoff, flags,
+ *             list_cap as always.  Image, gradient and 8-bit layouts, GSASR_FLAG_OVERWRITE_* / CHW_* / STRIDE8 /
+ *             FORWARD_ONLY, the kernel-choice flags, crop / pitch / swap of the 8-bit store: those of a whole image of
+ *             the window's size.
+ *   view      the grid it is cut from, 2 <= full_h, full_w <= 32767, and its origin: 0 <= y0, y0 + h <= full_h, likewise
+ *             columns.  Anything else (a row band, a batched canvas, a window that leaves the grid) is GSASR_ERR_ARG /
+ *             a workspace size of 0, before anything is enqueued.  view = NULL: the plain entry point.
+ *
+ * Output pixel (i, j) IS pixel (y0 + i, x0 + j) of the full grid: the same float coordinates
+ * ((float)(2.0 * (x0 + j) / (full_w - 1) - 1.0)), the same dmax box test, the same cutoff rules; the step forms run the host
+ * prologue for the full grid's size.  The dmax box in pixels and the adaptive cutoff's cell counts follow the full grid's
+ * scale, everything the workspace sizes the window.  The plan still classifies all s Gaussians (those whose support misses
+ * the window are dead to it); forward and backward touch the window only.  The backward is the gradient of
+ * sum(grad_img * window), and -- a window being a band of its grid -- sweeps the forward's windows like a row band's does
+ * (no GSASR_SPLAT_GRAD_TAU: a Gaussian's share inside the window may be all tail).
+ * The view belongs to the plan: forward / backward with another view, or none, on that workspace is GSASR_ERR_PLAN.  The
+ * kernel-choice rules see the Gaussians the window can expect, s * (h * w) / (full_h * full_w), not s; choices registered
+ * with gsasr_set_kernel_choice are keyed on whole-image shapes and are not looked up for a window (explicit flags in the
+ * dims hold as always).  A view that is the whole grid (y0 = x0 = 0, full = dims) is the plain call, bit for bit. */
+typedef struct gsasr_view {
+    int full_h, full_w;   /* the grid the window is cut from: pixel (Y, X) of it sits at 2*X/(full_w-1)-1, 2*Y/(full_h-1)-1 */
+    int y0, x0;           /* the window's first row / column on that grid; its size is dims.h x dims.w               */
+} gsasr_view;
+GSASR_API size_t gsasr_splat_workspace_bytes_view(const gsasr_dims *dims, const gsasr_view *view);
+GSASR_API size_t gsasr_step_workspace_bytes_view(const gsasr_dims *dims, const gsasr_view *view);
+GSASR_API int gsasr_splat_plan_view(const float *sigmas, const float *coords, const float *colors, const gsasr_dims *dims,
+                          const gsasr_view *view, void *workspace, size_t workspace_bytes, void *stream);
+GSASR_API int gsasr_splat_forward_view(const gsasr_dims *dims, const gsasr_view *view, const void *workspace,
+                             size_t workspace_bytes, float *img, void *stream);
+GSASR_API int gsasr_splat_forward_u8_view(const gsasr_dims *dims, const gsasr_view *view, const void *workspace,
+                                size_t workspace_bytes, unsigned char *out, int crop_rows, int crop_cols, size_t pitch,
+                                unsigned u8_flags, void *stream);
+GSASR_API int gsasr_splat_backward_view(const float *sigmas, const float *coords, const float *colors, const float *grad_img,
+                              float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
+                              const gsasr_view *view, const void *workspace, size_t workspace_bytes, void *stream);
+/* (step_size / scale_modify: of the FULL grid's scale factor, as for the whole image) */
+GSASR_API int gsasr_step_forward_view(const float *gs_parameters, const float *step_size, const gsasr_dims *dims,
+                            const gsasr_view *view, void *workspace, size_t workspace_bytes, float *img, void *stream);
+GSASR_API int gsasr_step_forward_sm_view(const float *gs_parameters, const float *scale_modify, int sm_stride,
+                               float default_step_size, int *mismatch, const gsasr_dims *dims, const gsasr_view *view,
+                               void *workspace, size_t workspace_bytes, float *img, void *stream);
+GSASR_API int gsasr_step_forward_u8_view(const float *gs_parameters, const float *step_size, const gsasr_dims *dims,
+                               const gsasr_view *view, void *workspace, size_t workspace_bytes, unsigned char *out,
+                               int crop_rows, int crop_cols, size_t pitch, unsigned u8_flags, void *stream);
+GSASR_API int gsasr_step_forward_sm_u8_view(const float *gs_parameters, const float *scale_modify, int sm_stride,
+                                  float default_step_size, int *mismatch, const gsasr_dims *dims, const gsasr_view *view,
+                                  void *workspace, size_t workspace_bytes, unsigned char *out, int crop_rows,
+                                  int crop_cols, size_t pitch, unsigned u8_flags, void *stream);
+GSASR_API int gsasr_step_backward_view(const float *gs_parameters, const float *step_size, const float *grad_img,
+                             float *g_parameters, const gsasr_dims *dims, const gsasr_view *view, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate
