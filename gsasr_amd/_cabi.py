@@ -32,6 +32,7 @@ FLAG_COUNTERS_CLEAN = 1024 # GSASR_FLAG_COUNTERS_CLEAN
 FLAG_PARITY = 2048         # GSASR_FLAG_PARITY
 FLAG_CUTOFF_CAP = 4096     # GSASR_FLAG_CUTOFF_CAP
 FLAG_FWD_WIDE, FLAG_FWD_NARROW = 8192, 16384      # forward kernel choice (development A/B, tests): 16x16 / 8x16 sub-tiles
+FLAG_CONTINUOUS = 65536    # GSASR_FLAG_CONTINUOUS: a plan for queries between the pixel centres (query_forward / query_backward)
 U8_SWAP_RB = 1             # GSASR_U8_SWAP_RB (u8_flags of the 8-bit forwards)
 EXACT_CUTOFF = 104.0    # GSASR_SPLAT_EXACT_CUTOFF
 NO_CUTOFF = -1.0
@@ -83,6 +84,11 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_step_sample_forward": (_i, [_vp, _vp] + _sample_tail),
     "gsasr_step_sample_forward_sm": (_i, [_vp, _vp, _i, _f, _vp] + _sample_tail),
     "gsasr_step_sample_backward": (_i, [_vp, _vp, _vp, _vp, _dp, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "gsasr_splat_query_forward": (_i, _sample_tail),
+    "gsasr_splat_query_backward": (_i, [_vp] * 7 + [_dp, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "gsasr_step_query_forward": (_i, [_vp, _vp] + _sample_tail),
+    "gsasr_step_query_forward_sm": (_i, [_vp, _vp, _i, _f, _vp] + _sample_tail),
+    "gsasr_step_query_backward": (_i, [_vp, _vp, _vp, _vp, _dp, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
     "gsasr_set_default_cutoff": (None, [_f]),
     "gsasr_get_default_cutoff": (_f, []),
     "gsasr_resolve_cutoff": (_f, [_f, _i]),
@@ -753,6 +759,7 @@ def _step_args(gs_parameters: torch.Tensor, step, scale_modify, default_step_siz
 _STEP_FWD = ("gsasr_step_forward", "gsasr_step_forward_sm")
 _STEP_FWD_U8 = ("gsasr_step_forward_u8", "gsasr_step_forward_sm_u8")
 _STEP_SAMPLE = ("gsasr_step_sample_forward", "gsasr_step_sample_forward_sm")
+_STEP_QUERY = ("gsasr_step_query_forward", "gsasr_step_query_forward_sm")
 
 
 def _step_call(names, pp: int, src, d: Dims, ws: torch.Tensor, nbytes: int, *tail) -> None:
@@ -887,6 +894,15 @@ def _points(points: torch.Tensor, batch: int, device) -> Tuple[torch.Tensor, int
     return points.to(device=device, dtype=torch.int32).contiguous(), int(points.shape[-2])
 
 
+def _query_points(points: torch.Tensor, batch: int, device) -> Tuple[torch.Tensor, int]:
+    """`[S,2]` (one image) or `[B,S,2]` (batched canvas) floating-point (r, c) pairs -> contiguous float32 on `device`."""
+    if not (isinstance(points, torch.Tensor) and points.dtype.is_floating_point
+            and points.shape[-1:] == (2,) and points.dim() == (3 if batch > 1 else 2)
+            and (batch <= 1 or points.shape[0] == batch)):
+        raise RuntimeError("query points must be a floating-point tensor [S,2] (or [B,S,2] for a batched canvas)")
+    return points.detach().to(device=device, dtype=torch.float32).contiguous(), int(points.shape[-2])
+
+
 def _sample_ws(d: Dims, n_points: int, dev) -> torch.Tensor:
     nbytes = lib().gsasr_sample_workspace_bytes(ctypes.byref(d), n_points)
     if nbytes == 0:
@@ -894,21 +910,34 @@ def _sample_ws(d: Dims, n_points: int, dev) -> torch.Tensor:
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
 
-def sample_forward(p: Plan, points: torch.Tensor):
+def sample_forward(p: Plan, points: torch.Tensor, _query: bool = False):
     """values of the splat at `points` only: `[3,S]` (`[B,3,S]` on a batched canvas) + the state for `sample_backward`."""
     B = max(int(p.dims.batch), 1)
-    pts, n = _points(points, B, p.device)
+    pts, n = (_query_points if _query else _points)(points, B, p.device)
+    name = "gsasr_splat_query_forward" if _query else "gsasr_splat_sample_forward"
     with _on(p.device):
         sws = _sample_ws(p.dims, n, p.device)
         out = torch.empty((B, 3, n) if B > 1 else (3, n), dtype=torch.float32, device=p.device)
-        check(lib().gsasr_splat_sample_forward(ctypes.byref(p.dims), p.workspace.data_ptr(), p.workspace.numel(),
-                                               pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(),
-                                               _stream(p.device)), "gsasr_splat_sample_forward")
+        check(getattr(lib(), name)(ctypes.byref(p.dims), p.workspace.data_ptr(), p.workspace.numel(),
+                                   pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(),
+                                   _stream(p.device)), name)
     return out, (pts, n, sws)
 
 
+def query_forward(p: Plan, points: torch.Tensor):
+    """values of the splat at fractional pixel positions: `points` float `[S,2]` (r, c) on the image's own grid (`[B,S,2]` on a
+    batched canvas) -> `[3,S]` (`[B,3,S]`) + the state for `query_backward`.  `p`: a plan made with `flags=FLAG_CONTINUOUS`."""
+    return sample_forward(p, points, _query=True)
+
+
+def query_backward(p: Plan, state, sigmas, coords, colors, grad_out, g_sigmas, g_coords, g_colors,
+                   overwrite: bool = False, resort: bool = False) -> None:
+    """g_* (+)= gradient of sum(grad_out * query_forward(...)) w.r.t. the Gaussians; `state` is what `query_forward` returned."""
+    sample_backward(p, state, sigmas, coords, colors, grad_out, g_sigmas, g_coords, g_colors, overwrite, resort, _query=True)
+
+
 def sample_backward(p: Plan, state, sigmas, coords, colors, grad_out, g_sigmas, g_coords, g_colors,
-                    overwrite: bool = False, resort: bool = False) -> None:
+                    overwrite: bool = False, resort: bool = False, _query: bool = False) -> None:
     """g_* (+)= gradient of sum(grad_out * sample_forward(...)); `state` is what `sample_forward` returned."""
     pts, n, sws = state
     B = max(int(p.dims.batch), 1)
@@ -918,10 +947,11 @@ def sample_backward(p: Plan, state, sigmas, coords, colors, grad_out, g_sigmas, 
     if grad_out.numel() != B * 3 * n:
         raise RuntimeError("grad_out does not match the points")
     d = _dims_with(p, FLAG_OVERWRITE_GRADS if overwrite else 0)
+    name = "gsasr_splat_query_backward" if _query else "gsasr_splat_sample_backward"
     with _on(p.device):
-        check(lib().gsasr_splat_sample_backward(*ptrs, ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(),
-                                                pts.data_ptr() if resort else None, n, sws.data_ptr(), sws.numel(),
-                                                _stream(p.device)), "gsasr_splat_sample_backward")
+        check(getattr(lib(), name)(*ptrs, ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(),
+                                   pts.data_ptr() if resort else None, n, sws.data_ptr(), sws.numel(),
+                                   _stream(p.device)), name)
 
 
 def step_sample_forward(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
@@ -939,21 +969,43 @@ def batch_sample_forward(gs_parameters: torch.Tensor, steps: torch.Tensor, sizes
     return _step_sampled(_canvas_shape(gs_parameters.shape[1], sizes, dmax, 0), pp, src, points, gs_parameters.device)
 
 
-def _step_sampled(shape, pp: int, src, points: torch.Tensor, dev):
+def step_query_forward(gs_parameters: torch.Tensor, step: Optional[torch.Tensor], h: int, w: int, dmax: Optional[float],
+                       points: torch.Tensor, scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+    """`step_sample_forward` at fractional pixel positions: `points` float `[S,2]` (r, c) -> `[3,S]` (the library plans with
+    GSASR_FLAG_CONTINUOUS itself)."""
+    pp, src = _step_args(gs_parameters, step, scale_modify, default_step_size)
+    shape = _image_shape(_STEP_BYTES, gs_parameters.shape[0], int(h), int(w), dmax, 0)
+    return _step_sampled(shape, pp, src, points, gs_parameters.device, _STEP_QUERY)
+
+
+def batch_query_forward(gs_parameters: torch.Tensor, steps: torch.Tensor, sizes, dmax: Optional[float],
+                        points: torch.Tensor):
+    """the same for a whole batch: `gs_parameters` [B,N,9], `points` float [B,S,2] on each sample's own grid -> `[B,3,S]`."""
+    pp, src = _step_args(gs_parameters, steps, None, 1.2, sizes)
+    return _step_sampled(_canvas_shape(gs_parameters.shape[1], sizes, dmax, 0), pp, src, points, gs_parameters.device, _STEP_QUERY)
+
+
+def _step_sampled(shape, pp: int, src, points: torch.Tensor, dev, names=None):
     """prologue + plan + sampled forward (`_step_planar`'s sibling; these plans take a fresh workspace each)"""
     d, nbytes = shape[0][0], shape[1]
     B = max(int(d.batch), 1)
-    pts, n = _points(points, B, dev)
+    names = names or _STEP_SAMPLE
+    pts, n = (_query_points if names is _STEP_QUERY else _points)(points, B, dev)
     with _on(dev):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         sws = _sample_ws(d, n, dev)
         out = torch.empty((B, 3, n) if B > 1 else (3, n), dtype=torch.float32, device=dev)
-        _step_call(_STEP_SAMPLE, pp, src, d, ws, nbytes, pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(), _stream(dev))
+        _step_call(names, pp, src, d, ws, nbytes, pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(), _stream(dev))
     return out, Plan(d, ws, dev), (pts, n, sws)
 
 
+def step_query_backward(p: Plan, state, gs_parameters: torch.Tensor, step: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+    """query backward + prologue backward in ONE call (`step_sample_backward`'s twin for `step_query_forward` / `batch_query_forward`)"""
+    return step_sample_backward(p, state, gs_parameters, step, grad_out, _name="gsasr_step_query_backward")
+
+
 def step_sample_backward(p: Plan, state, gs_parameters: torch.Tensor, step: torch.Tensor,
-                         grad_out: torch.Tensor) -> torch.Tensor:
+                         grad_out: torch.Tensor, _name: str = "gsasr_step_sample_backward") -> torch.Tensor:
     """sampled backward + prologue backward in ONE call; returns d/d gs_parameters (`[N,9]` or `[B,N,9]`)."""
     pts, n, sws = state
     pp = _chk(gs_parameters, "gs_parameters", (9,))
@@ -963,9 +1015,9 @@ def step_sample_backward(p: Plan, state, gs_parameters: torch.Tensor, step: torc
         raise RuntimeError("grad_out does not match the points")
     with _on(p.device):
         gp = torch.empty_like(gs_parameters)
-        check(lib().gsasr_step_sample_backward(pp, ps, pg, gp.data_ptr(), ctypes.byref(p.dims), p.workspace.data_ptr(),
-                                               p.workspace.numel(), None, n, sws.data_ptr(), sws.numel(),
-                                               _stream(p.device)), "gsasr_step_sample_backward")
+        check(getattr(lib(), _name)(pp, ps, pg, gp.data_ptr(), ctypes.byref(p.dims), p.workspace.data_ptr(),
+                                    p.workspace.numel(), None, n, sws.data_ptr(), sws.numel(),
+                                    _stream(p.device)), _name)
     return gp
 
 

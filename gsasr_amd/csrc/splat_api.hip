@@ -124,11 +124,13 @@ static unsigned long long note_shape(const gsasr_dims *d, const gsasr_view *vw)
 }
 
 // (payload byte: slots per Gaussian in bits 0..4, the tile lists' tile height in bits 5..6: 0 none, 1 = 16 rows, 2 = 32;
+// bit 7: the plan was made with GSASR_FLAG_CONTINUOUS -- matched like the shape: a call whose dims disagree finds no plan;
 // the capacity word: the capacity (<= 65536) in bits 0..23)
 void note_plan(const void *ws, const gsasr_dims *d, size_t plan_bytes, int part_k, int tl_hlog, int tl_cap, const gsasr_view *vw)
 {
     const unsigned long long a = note_addr(ws);
-    const unsigned long long w = a | note_shape(d, vw) << 8 | (unsigned long long)((part_k & 0x1f) | (tl_hlog ? (tl_hlog - 3) << 5 : 0));
+    const unsigned long long w = a | note_shape(d, vw) << 8 | (unsigned long long)((part_k & 0x1f) | (tl_hlog ? (tl_hlog - 3) << 5 : 0) |
+                                                                                           ((d->flags & GSASR_FLAG_CONTINUOUS) ? 0x80 : 0));
     const unsigned long long c = a | ((unsigned long long)(unsigned)tl_cap & 0xffffffull);
     const unsigned i = note_slot(ws);
     std::lock_guard<std::mutex> lk(g_note_mu);
@@ -159,7 +161,7 @@ Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted, const gsasr
     int part_k = -1, tl_hlog = -1, tl_cap = -1;
     bool found = false;
     if (ws) {
-        const unsigned long long a = note_addr(ws), key = a | note_shape(d, vw) << 8;
+        const unsigned long long a = note_addr(ws), key = a | note_shape(d, vw) << 8 | ((d->flags & GSASR_FLAG_CONTINUOUS) ? 0x80ull : 0ull);
         const unsigned i = note_slot(ws);
         unsigned long long w = g_notes[i].load(std::memory_order_acquire), c = 0ull;
         if ((w & ADDR_MASK) == a) c = g_note_caps[i].load(std::memory_order_acquire);
@@ -180,7 +182,7 @@ Layout plan_layout(const gsasr_dims *d, const void *ws, bool *noted, const gsasr
             }
         }
         // (a capacity word of another workspace never passes: no list region sized by a guessed capacity)
-        found = (w & ~0xffull) == key && (c & ADDR_MASK) == a;
+        found = (w & ~0x7full) == key && (c & ADDR_MASK) == a;
         if (found) {
             part_k = (int)(w & 0x1full);
             tl_hlog = (int)((w >> 5) & 3ull) ? (int)((w >> 5) & 3ull) + 3 : 0;
@@ -212,7 +214,7 @@ const char *last_error_message() { return tl_err; }
 
 int check_ws(const gsasr_dims *dims, const void *ws, size_t ws_bytes, Layout &L, bool planning, const gsasr_view *vw)
 {
-    if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims (need c==3, 2<=h,w<=32767, 0<=row0<=row1<=h)");
+    if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims (need c==3, 2<=h,w<=32767, 0<=row0<=row1<=h; GSASR_FLAG_CONTINUOUS: the whole image, no kernel-choice flag, list_cap <= 0)");
     if (!view_ok(dims, vw)) return fail(GSASR_ERR_ARG, VIEW_ERR);
     if (dims->batch > 1 && dims->grad_rows != 0 && (dims->flags & GSASR_FLAG_CHW_GRAD)) {
         // planar gradient of a batched canvas [B, 3, grad_rows, w]: every sample's rows must lie inside its planes

@@ -632,6 +632,7 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
 {
     Layout L;
     if (int rc = check_ws(dims, workspace, workspace_bytes, L, false, vw)) return rc;
+    if (dims->flags & GSASR_FLAG_CONTINUOUS) return fail(GSASR_ERR_PLAN, CONTINUOUS_ERR);
     const gsasr_dims pd = policy_dims(dims, vw);      // what the kernel-choice rules read (a window: its expected live Gaussians)
     const int mode = bwd_mode(&pd, L);
     if (mode_out) *mode_out = mode;

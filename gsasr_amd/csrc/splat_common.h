@@ -211,10 +211,16 @@ struct Layout {
     int ncx, ncy, ncells;
 };
 
+constexpr unsigned CONTINUOUS_EXCLUDES = GSASR_FLAG_FWD_WIDE | GSASR_FLAG_FWD_NARROW | GSASR_FLAG_BWD_GAUSSIAN | GSASR_FLAG_BWD_TILE |
+                                         GSASR_FLAG_BWD_ATOMIC | GSASR_FLAG_BWD_HOME;
 inline bool dims_ok(const gsasr_dims *d)
 {
     if (!(d && d->s >= 0 && d->h >= 2 && d->w >= 2 && d->h <= 32767 && d->w <= 32767 && d->c == 3 &&
           d->row0 >= 0 && d->row0 <= d->row1 && d->row1 <= d->h && !(d->dmax != d->dmax)))
+        return false;
+    // a continuous plan (GSASR_FLAG_CONTINUOUS) is the whole image and carries no lists or slots: no explicit kernel choice goes with it
+    if ((d->flags & GSASR_FLAG_CONTINUOUS) &&
+        ((d->flags & CONTINUOUS_EXCLUDES) || d->list_cap > 0 || d->row0 != 0 || d->row1 != d->h))
         return false;
     if (d->batch <= 1) return true;
     // batched canvas: B slots of `slot` rows, whole canvas, uniform Gaussian count, per-sample sizes inside the slot
@@ -231,11 +237,13 @@ inline bool dims_ok(const gsasr_dims *d)
 inline int batch_of(const gsasr_dims *d) { return d->batch > 1 ? d->batch : 1; }
 
 constexpr const char *VIEW_ERR = "bad view (a window is one whole image: row0 = 0, row1 = h, batch = 0; 2<=full_h,full_w<=32767, 0<=y0<=full_h-h, 0<=x0<=full_w-w)";
+constexpr const char *CONTINUOUS_ERR = "a plan made with GSASR_FLAG_CONTINUOUS serves the query and sampled-pixel entry points only (its windows are padded: no row spans, tile lists or slots for the image kernels)";
 // dims + view of a `_view` entry point: one whole image of the window's size, cut from a grid within the whole-image limits
 inline bool view_ok(const gsasr_dims *d, const gsasr_view *v)
 {
     if (!dims_ok(d)) return false;
     if (!v) return true;
+    if (d->flags & GSASR_FLAG_CONTINUOUS) return false;      // (queries are not combinable with a view)
     return d->batch <= 1 && d->row0 == 0 && d->row1 == d->h && v->full_h >= 2 && v->full_w >= 2 && v->full_h <= 32767 &&
            v->full_w <= 32767 && v->y0 >= 0 && v->x0 >= 0 && v->y0 <= v->full_h - d->h && v->x0 <= v->full_w - d->w;
 }
@@ -255,6 +263,10 @@ inline const gsasr_view *norm_view(const gsasr_dims *d, const gsasr_view *v)
 inline gsasr_dims policy_dims(const gsasr_dims *d, const gsasr_view *v)
 {
     gsasr_dims p = *d;
+    if (d->flags & GSASR_FLAG_CONTINUOUS) {   // a continuous plan: no lists, and (the NaN cutoff, as for a window) no registered choice
+        p.list_cap = -1;
+        p.cutoff = NAN;
+    }
     if (v) {
         const double live = (double)d->s * ((double)d->h * (double)d->w) / ((double)v->full_h * (double)v->full_w);
         p.s = d->s > 0 ? (int)std::fmax(1.0, std::floor(live)) : 0;
@@ -521,12 +533,13 @@ inline Layout make_layout(const gsasr_dims *d, int part_k = -1, int tl_hlog = -1
     L.off_done = o;   o += align_up(bw * 4, 256);
     L.off_bbox = o;   o += align_up(s * 32, 256);
     L.off_win = o;    o += align_up(s * 8, 256);
-    L.part_k = part_k >= 0 ? part_k : bwd_part_k(&pd);
+    const bool cont = (d->flags & GSASR_FLAG_CONTINUOUS) != 0u;      // no slots, no lists: laid out as with list_cap < 0
+    L.part_k = cont ? 0 : part_k >= 0 ? part_k : bwd_part_k(&pd);
     L.off_part = o;   o += align_up(s * 32 * (size_t)L.part_k, 256);
     L.off_qspan = o;  o += L.part_k ? align_up(s * 16, 256) : 0;
     // tile lists LAST: a caller whose flags differ from the plan's (GSASR_FLAG_FWD_WIDE at forward time) lays out everything
     // else identically; whether the workspace carries lists, and of which tile height, is the plan's note (plan_layout)
-    L.tl_hlog = tl_hlog >= 0 ? tl_hlog : tl_hlog_for(&pd);
+    L.tl_hlog = cont ? 0 : tl_hlog >= 0 ? tl_hlog : tl_hlog_for(&pd);
     L.tl_cap = (tl_cap >= 0 && L.tl_hlog) ? tl_cap : tl_cap_for(&pd, L.tl_hlog);
     L.tl_ntx = (d->w + TL_W - 1) / TL_W;
     L.tl_ntiles = L.tl_hlog ? L.tl_ntx * ((d->row1 - d->row0 + (1 << L.tl_hlog) - 1) >> L.tl_hlog) : 0;
@@ -642,13 +655,17 @@ inline Params make_params(const gsasr_dims *d, const Layout &L, const gsasr_view
     if (P.bounded && adapt) {
         const int B = batch_of(d);
         const double dpx = (double)d->dmax * 0.5 * (scale_w - 1.0), dpy = (double)d->dmax * 0.5 * ((B > 1 ? (double)d->slot : scale_h) - 1.0);
-        const double cx = std::ceil(2.0 * std::floor(dpx + 1.02) / (double)CELL) + 1.0, cy = std::ceil(2.0 * std::floor(dpy + 1.02) / (double)CELL) + 1.0;
+        // (a continuous plan counts for a point up to half a pixel off its nearest pixel p: a Gaussian whose box covers it is
+        // binned within floor(dmax_px + 1.02) + 1 pixels of p -- adapt_kcut, "box")
+        const double half = (d->flags & GSASR_FLAG_CONTINUOUS) ? 1.0 : 0.0;
+        const double mx = std::floor(dpx + 1.02) + half, my = std::floor(dpy + 1.02) + half;
+        const double cx = std::ceil(2.0 * mx / (double)CELL) + 1.0, cy = std::ceil(2.0 * my / (double)CELL) + 1.0;
         const double cells = std::fmin(cx, (double)L.ncx) * std::fmin(cy, (double)L.ncy);
         P.adapt_cells = (float)std::fmin(cells, 1.0e9) * (1.f + 1e-6f);
         // Sparse cells (fewer than 8 Gaussians per cell on average: x8 and up) on a grid with a scan pass of its own: the
         // largest single cell is several times the mean there, the largest 64 x 64-px block is not -- count in blocks too
         if ((double)d->s < 8.0 * (double)L.ncells && L.ncells + 1 + NDEAD > FUSED_CELLS_HOST) {
-            const double bx = std::ceil(2.0 * std::floor(dpx + 1.02) / (4.0 * CELL)) + 1.0, by = std::ceil(2.0 * std::floor(dpy + 1.02) / (4.0 * CELL)) + 1.0;
+            const double bx = std::ceil(2.0 * mx / (4.0 * CELL)) + 1.0, by = std::ceil(2.0 * my / (4.0 * CELL)) + 1.0;
             P.adapt_cells4 = (float)std::fmin(std::fmin(bx, std::ceil(L.ncx / 4.0)) * std::fmin(by, std::ceil(L.ncy / 4.0)), 1.0e9) * (1.f + 1e-6f);
         }
     }
@@ -725,8 +742,19 @@ __device__ __forceinline__ Box gaussian_box(float sx, float sy, float x, float y
     const double ex = (double)ext_x * hx, ey = (double)ext_y * hy;
     b.ex = (float)ex;
     b.ey = (float)ey;
-    const double lox = ceil(cxp - ex - WINDOW_EPS), hix = floor(cxp + ex + WINDOW_EPS);
-    const double loy = ceil(cyp - ey - WINDOW_EPS), hiy = floor(cyp + ey + WINDOW_EPS);
+    // GSASR_FLAG_CONTINUOUS: one pixel more on each side, BEFORE the window is found empty or clipped.  The plan is then valid
+    // for a point anywhere within half a pixel of the pixel X = rint(c) it is assigned to: if the support interval [lo, hi]
+    // (pixel units) contains c, then ceil(lo) <= ceil(c) <= rint(c) + 1 and floor(hi) >= floor(c) >= rint(c) - 1, i.e.
+    // ceil(lo) - 1 <= rint(c) <= floor(hi) + 1.  lo <= hi makes ceil(lo) - 1 <= floor(hi) + 1, so no finite Gaussian is dead
+    // for being narrow (sigma = 0.05 px between four centres: its unpadded window is empty), only for lying off the grid.
+    // The near-dead test below needs no change: the closed grid rectangle has the pixel grid's own extremes, and its + 1 px
+    // is spare.  The search reach ceil(ex) + 2 (k_classify, reach_of) is then exactly used up: a padded window that meets a
+    // block [bx0, bx1] has floor(cxp + ex + eps) + 1 >= bx0, so floor(cxp) >= floor(bx0 - ex - 1 - eps) >= bx0 - ceil(ex) - 2
+    // (eps < 1), and ceil(cxp - ex - eps) - 1 <= bx1 gives floor(cxp) <= bx1 + ceil(ex) + 1: the centre's cell lies within
+    // the reach on both sides (one pixel for the floor the centre is binned by, one for the padding).
+    const double pad = (P.flags & GSASR_FLAG_CONTINUOUS) ? 1.0 : 0.0;
+    const double lox = ceil(cxp - ex - WINDOW_EPS) - pad, hix = floor(cxp + ex + WINDOW_EPS) + pad;
+    const double loy = ceil(cyp - ey - WINDOW_EPS) - pad, hiy = floor(cyp + ey + WINDOW_EPS) + pad;
     const bool finite = (sx - sx == 0.f) && (sy - sy == 0.f) && (x - x == 0.f) && (y - y == 0.f);
     b.c0 = (int)fmax(lox, 0.0);
     b.c1 = (int)fmin(hix, (double)(g.w - 1));
@@ -794,6 +822,8 @@ __device__ __forceinline__ float wave_sum(float v)
 //            Gaussian is binned by the cell of its (clamped, floored) centre and covers p only from the cells that the
 //            2m + 1 pixels around p touch, m = floor(dmax_px + 1.02): Cx * Cy cells, C = ceil(2m / 16) + 1
 //            [adapt_cells; on large sparse grids the same count in aligned 4 x 4-cell blocks, adapt_cells4];
+//            GSASR_FLAG_CONTINUOUS: the point is p + f, |f| <= 1/2, and a centre within dmax_px of it has its floor within
+//            ceil(dmax_px + 1/2) <= floor(dmax_px + 1.02) + 1 of p: m is one larger (make_params);
 //       ring (either op): with E = the class' largest half-extent under tau in x / in y (header words 0, 1: <= 130 px),
 //            the CORE = the Cx * Cy cells that the 2 m + 1 pixels around p touch, m = E + 1, C = ceil(2m / 16) + 1: every
 //            Gaussian within E pixels of p is binned there.  A Gaussian binned r >= 1 cells beyond the core along an axis is
@@ -801,6 +831,10 @@ __device__ __forceinline__ float wave_sum(float v)
 //            q = exp(-32 tau / E) <= 0.02 (marginal of the bivariate normal; a window capped by the dmax box adds exactly
 //            nothing beyond the cap).  Ring r holds 2 (Cx + Cy) + 8 r - 4 cells; summed over r >= 1 they add at most
 //            2.1 (Cx + Cy) + 5 cells' worth of terms below exp(-tau) -- the CONSERVATIVE tau: they are paid from the budget
+//            [GSASR_FLAG_CONTINUOUS, a point p + f: E here is header word 0 / 1 = ceil(extent) + 2, so a centre within the true
+//            extent of p + f has its floor within ceil(extent) + 1 <= m of p, and a cell r beyond the core starts at
+//            p + E + 2 + 16 (r - 1) above or ends below p - E - 1 - 16 (r - 1): >= E + 1/2 + 16 (r - 1) from p + f on either
+//            side -- the core and the tail hold as they stand, the half pixel comes out of the + 1 of m.]
 //            like (3), not counted at exp(-tau').  At x8 the core is 49 cells against the 2 809 of the box; at x4 16 against 64.
 //   (2) the LARGE class (extent > 128 px): counted in full.
 //   (3) NEAR-DEAD ones: classified dead because their support (under tau) does not reach the rows, though the op would

@@ -1256,6 +1256,7 @@ static int forward_launch(const gsasr_dims *dims, const void *workspace, size_t 
     if (u8) if (int rc = u8_args_check(dims, u8->out, u8->rows, u8->cols, u8->pitch, u8->flags)) return rc;
     Layout L;
     if (int rc = check_ws(dims, workspace, workspace_bytes, L, false, vw)) return rc;
+    if (dims->flags & GSASR_FLAG_CONTINUOUS) return fail(GSASR_ERR_PLAN, CONTINUOUS_ERR);
     const int rows = dims->row1 - dims->row0;
     if (rows == 0) return GSASR_OK;
     if (!u8 && !img) return fail(GSASR_ERR_ARG, "null image pointer");

@@ -582,6 +582,8 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
                            __uint_as_float((unsigned)i));
         // does a pixel of a tile this Gaussian is binned to ever need the dmax test?  Not if its support box
         // lies inside its dmax box: pixels beyond the support box carry < exp(-tau) whether tested or not.
+        // (A statement about the two CONTINUOUS boxes -- support box + 1 px inside the dmax box -- not about pixel centres: it
+        // holds as it stands for the fractional points of a GSASR_FLAG_CONTINUOUS plan.)
         const float hx = 0.5f * (float)(sc.gw - 1), hy = 0.5f * (float)(sc.gh - 1);
         const bool needs_test = P.bounded && !(kw > 0.f && kw * fabsf(sx) * hx + 1.f <= P.dmax * hx &&
                                                kw * fabsf(sy) * hy + 1.f <= P.dmax * hy);
@@ -595,6 +597,10 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
             // the range of 8-px tile columns that the ellipse {exponent >= -tau} actually reaches.  The
             // window's corners are empty for every Gaussian (and most of it for a correlated one), so this
             // removes ~30% of the forward's (tile, Gaussian) visits that the rectangular window admits.
+            // (GSASR_FLAG_CONTINUOUS pads the window by a pixel, so a band may lie wholly beyond the ellipse -- never before.
+            // Nothing reads the spans of such a plan, and they stay finite: a band with v0 > vmax or v1 < -vmax is left empty
+            // before any root is taken, and inside, vr and vl are clamped to [-vmax, vmax] where the discriminant is >= 0 up to
+            // rounding, which the fmaxf(.., 0) under each sqrtf absorbs.)
             const int ty0 = (b.r0 - P.row0) >> SUBY_SHIFT, ty1 = (b.r1 - P.row0) >> SUBY_SHIFT;
             if (kw > 0.f && ty1 - ty0 < 8 && (b.c1 >> SUBX_SHIFT) - (b.c0 >> SUBX_SHIFT) <= 255) {
                 // (fp32 relative to the centre: the plan runs one wave per SIMD, so the length of this dependent

@@ -12,6 +12,8 @@ namespace {
 //   k_pts_count / k_pts_scan / k_pts_place   counting sort of the points into point-cells (8x8 px; coarser when the
 //                 image has more than PT_CELLS of those); a sorted point carries its px, py; out-of-range points go to
 //                 a last bucket.  k_pts_grads (backward) gathers the upstream gradient into the same order.
+//                 FLOAT points (gsasr_splat_query_*: fractional pixel indices on a GSASR_FLAG_CONTINUOUS plan) are sorted by
+//                 their NEAREST pixel and carry the px, py of their real position; everything after the sort is the same.
 //   k_sample_fwd  POINT-stationary two-level walk: one workgroup = the points of a 16x16-px block; level 1 lists the
 //                 Gaussians whose window meets the block, level 2 evaluates each of them (one per lane, loaded once) at
 //                 all the block's points; no atomics on the output.
@@ -38,23 +40,40 @@ __device__ __forceinline__ int2 point_rc(int2 raw, const Geo &g)
 }
 
 // The counting sort as three launches (the histogram is zeroed by a memset): count, scan (one workgroup), place.
-__device__ __forceinline__ int point_cell(const Params &P, const PlanView &V, const PtView &S, const int *__restrict__ pts,
-                                          int i, int n_per, int &X, int &Y, int &pxo)
+// FLOAT: the points are float (r, c) pairs, fractional pixel indices.  Valid on the closed rectangle 0 <= r <= h - 1,
+// 0 <= c <= w - 1 (the test is on the float values: NaN and infinities fail it; no wrap-around); X, Y = the NEAREST pixel,
+// which the domain keeps inside the grid, so the point is at most half a pixel from the pixel its cell and its word name.
+// `rc` returns the position for k_pts_place.
+template <bool FLOAT>
+__device__ __forceinline__ int point_cell(const Params &P, const PlanView &V, const PtView &S, const void *__restrict__ pts,
+                                          int i, int n_per, int &X, int &Y, int &pxo, float2 &rc_f, Geo &g)
 {
-    const Geo g = sample_geo(P, V, i / n_per);
-    const int2 rc = point_rc(reinterpret_cast<const int2 *>(pts)[i], g);
-    const bool ok = rc.x >= 0 && rc.x < g.h && rc.y >= 0 && rc.y < g.w;
-    X = rc.y; Y = g.base + rc.x; pxo = g.pxo;
+    g = sample_geo(P, V, i / n_per);
+    bool ok;
+    if (FLOAT) {
+        rc_f = reinterpret_cast<const float2 *>(pts)[i];
+        ok = rc_f.x >= 0.f && rc_f.x <= (float)(g.h - 1) && rc_f.y >= 0.f && rc_f.y <= (float)(g.w - 1);
+        X = ok ? (int)rintf(rc_f.y) : 0;
+        Y = g.base + (ok ? (int)rintf(rc_f.x) : 0);
+    } else {
+        const int2 rc = point_rc(reinterpret_cast<const int2 *>(pts)[i], g);
+        ok = rc.x >= 0 && rc.x < g.h && rc.y >= 0 && rc.y < g.w;
+        X = rc.y; Y = g.base + rc.x;
+    }
+    pxo = g.pxo;
     return ok ? (Y >> S.shy) * S.ncx + (X >> S.shx) : S.ncx * S.ncy;
 }
 
-__global__ __launch_bounds__(256) void k_pts_count(Params P, PlanView V, PtView S, const int *__restrict__ pts,
+template <bool FLOAT>
+__global__ __launch_bounds__(256) void k_pts_count(Params P, PlanView V, PtView S, const void *__restrict__ pts,
                                                    int n_total, int n_per)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_total) return;
     int X, Y, pxo;
-    atomicAdd(&S.start[point_cell(P, V, S, pts, i, n_per, X, Y, pxo)], 1u);
+    float2 rc;
+    Geo g;
+    atomicAdd(&S.start[point_cell<FLOAT>(P, V, S, pts, i, n_per, X, Y, pxo, rc, g)], 1u);
 }
 
 __global__ __launch_bounds__(1024) void k_pts_scan(PtView S, int n_total)
@@ -98,15 +117,27 @@ __global__ __launch_bounds__(1024) void k_pts_scan(PtView S, int n_total)
     if (tid == 0) S.start[npc + 1] = (unsigned)n_total;
 }
 
-__global__ __launch_bounds__(256) void k_pts_place(Params P, PlanView V, PtView S, const int *__restrict__ pts,
+template <bool FLOAT>
+__global__ __launch_bounds__(256) void k_pts_place(Params P, PlanView V, PtView S, const void *__restrict__ pts,
                                                    int n_total, int n_per)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_total) return;
     int X, Y, pxo;
-    const int cell = point_cell(P, V, S, pts, i, n_per, X, Y, pxo);
+    float2 rc;
+    Geo g;
+    const int cell = point_cell<FLOAT>(P, V, S, pts, i, n_per, X, Y, pxo, rc, g);
     const bool ok = cell < S.ncx * S.ncy;
-    const float px = ok ? V.px[pxo + X] : 0.f, py = ok ? V.py[Y] : 0.f;
+    float px = 0.f, py = 0.f;
+    if (FLOAT) {   // the pixel tables' own expression (k_classify) with a real index: an integer-valued one gives the table's float
+        if (ok) {
+            px = (float)(2.0 * (double)rc.y / (double)(g.w - 1) - 1.0);
+            py = (float)(2.0 * (double)rc.x / (double)(g.h - 1) - 1.0);
+        }
+    } else if (ok) {
+        px = V.px[pxo + X];
+        py = V.py[Y];
+    }
     const unsigned pos = atomicAdd(&S.cursor[cell], 1u);
     S.sorted[pos] = make_float4(px, py, ok ? __uint_as_float((unsigned)X | ((unsigned)Y << 16)) : 0.f, __uint_as_float((unsigned)i));
 }
@@ -142,6 +173,13 @@ __device__ __forceinline__ float wave_sum_dpp(float v)
 // accumulators that live in registers across the whole walk; one DPP reduction over the wave and an LDS combine over
 // the waves at the end.  128 VGPRs (the accumulators), 33 KB of LDS (the list): four workgroups per CU.  The last
 // workgroup zeroes the outputs of the out-of-range points.
+// Fractional points (GSASR_FLAG_CONTINUOUS plan): a point is in this workgroup's block when its NEAREST pixel is, and a
+// continuous plan's windows hold the nearest pixel of every point inside the Gaussian's support (gaussian_box).  So each place
+// below that reasons in whole pixels stays correct for a point within half a pixel of its pixel: the rectangle test of
+// [bx0, bx1] x [by0, by1] against V.win admits every Gaussian whose support holds one of the block's points; the segment
+// table reaches every cell such a Gaussian can be binned in (hdr[8], hdr[9] = ceil(extent) + 2 cover the padding:
+// gaussian_box); level 2 tests no window per point at all.  A point of the block outside a survivor's support adds a term
+// below exp(-tau) as it always did.  The kernel runs unchanged.
 constexpr int SAMPLE_WAVES = 4;
 constexpr int SAMPLE_CHUNKS = 8;      // candidate windows in flight per lane (level 1)
 constexpr int SAMPLE_LIST = 8192;     // capacity of the survivor list = candidates tested between two level-2 passes
@@ -377,6 +415,9 @@ __global__ __launch_bounds__(256) void k_sample_bwd(Params P, PlanView V, PtView
     // The candidates: every point of the point-cells the window touches, SB_ROWS rows of cells at a time as ONE run
     // of indices (no per-row padding).  No window test per point: a point of a touched cell outside the window
     // carries a term below exp(-tau), and cells never straddle two samples of a batched canvas (make_pt_view).
+    // Fractional points: a point is filed in the point-cell of its nearest pixel, and a continuous plan's window (bbox
+    // words 0, 1: padded by a pixel) holds the nearest pixel of every point inside the support, so pcx0..pcx1 x rows
+    // r0..r1 of point-cells hold every such point.  Nothing else here reasons in pixels: the kernel runs unchanged.
     const int pcx0 = c0 >> S.shx, pcx1 = c1 >> S.shx, pcy1 = dead ? -1 : r1 >> S.shy;
     for (int row = dead ? 0 : r0 >> S.shy; row <= pcy1; row += SB_ROWS) {
         unsigned beg[SB_ROWS], cum[SB_ROWS];   // first point of row k; points in rows 0..k
@@ -468,15 +509,19 @@ PtView make_pt_view(const gsasr_dims *d, void *ws, long n_total)
     }
     return S;
 }
-int sort_points(const Params &P, const PlanView &V, const PtView &S, const int *points, int n_total, int n_per, hipStream_t st)
+// (fl: float (r, c) points of the query entry points; else the int32 ones of the sampled pixels)
+int sort_points(const Params &P, const PlanView &V, const PtView &S, const void *points, bool fl, int n_total, int n_per, hipStream_t st)
 {
     HIP_TRY(hipMemsetAsync(S.start, 0, (size_t)(S.ncx * S.ncy + 2) * 4, st));
     const dim3 grid((unsigned)((n_total + 255) / 256)), block(256);
-    hipLaunchKernelGGL(k_pts_count, grid, block, 0, st, P, V, S, points, n_total, n_per);
+    if (fl) hipLaunchKernelGGL(k_pts_count<true>, grid, block, 0, st, P, V, S, points, n_total, n_per);
+    else hipLaunchKernelGGL(k_pts_count<false>, grid, block, 0, st, P, V, S, points, n_total, n_per);
     hipLaunchKernelGGL(k_pts_scan, dim3(1), dim3(1024), 0, st, S, n_total);
-    hipLaunchKernelGGL(k_pts_place, grid, block, 0, st, P, V, S, points, n_total, n_per);
+    if (fl) hipLaunchKernelGGL(k_pts_place<true>, grid, block, 0, st, P, V, S, points, n_total, n_per);
+    else hipLaunchKernelGGL(k_pts_place<false>, grid, block, 0, st, P, V, S, points, n_total, n_per);
     return GSASR_OK;
 }
+constexpr const char *QUERY_PLAN_ERR = "queries at fractional positions need a plan made with GSASR_FLAG_CONTINUOUS (a plain plan's windows hold pixel centres only)";
 int check_points(const gsasr_dims *dims, int n_points, const void *sample_ws, size_t sample_ws_bytes, long &n_total)
 {
     if (dims->row0 != 0 || dims->row1 != dims->h) return fail(GSASR_ERR_ARG, "sampled pixels need the whole image (row0 = 0, row1 = h)");
@@ -502,20 +547,22 @@ size_t gsasr_sample_workspace_bytes(const gsasr_dims *dims, int n_points)
     return make_pt_layout((long)n_points * batch_of(dims)).total;
 }
 
-int gsasr_splat_sample_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const int *points,
-                               int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
+namespace {
+int sample_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const void *points, bool fl,
+                   int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
 {
     Layout L;
     if (int rc = check_ws(dims, workspace, workspace_bytes, L)) return rc;
     long n_total = 0;
     if (int rc = check_points(dims, n_points, sample_ws, sample_ws_bytes, n_total)) return rc;
+    if (fl && !(dims->flags & GSASR_FLAG_CONTINUOUS)) return fail(GSASR_ERR_PLAN, QUERY_PLAN_ERR);
     if (n_total == 0) return GSASR_OK;
     if (!points || !out) return fail(GSASR_ERR_ARG, "null pointer");
     const Params P = make_params(dims, L);
     const PlanView V = make_view(L, const_cast<void *>(workspace));
     const PtView S = make_pt_view(dims, sample_ws, n_total);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = sort_points(P, V, S, points, (int)n_total, n_points, st)) return rc;
+    if (int rc = sort_points(P, V, S, points, fl, (int)n_total, n_points, st)) return rc;
     // one workgroup per 16x16-px block of point-cells (or per coarser cell) + one for the out-of-range bucket
     const int fsx = S.shx > CELL_SHIFT ? S.shx : CELL_SHIFT, fsy = S.shy > CELL_SHIFT ? S.shy : CELL_SHIFT;
     const dim3 grid((unsigned)((((dims->w - 1) >> fsx) + 1) * (((dims->h - 1) >> fsy) + 1) + 1)), block(64 * SAMPLE_WAVES);
@@ -525,15 +572,16 @@ int gsasr_splat_sample_forward(const gsasr_dims *dims, const void *workspace, si
     return GSASR_OK;
 }
 
-int gsasr_splat_sample_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_out,
-                                float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
-                                const void *workspace, size_t workspace_bytes, const int *points, int n_points,
-                                void *sample_ws, size_t sample_ws_bytes, void *stream)
+int sample_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_out,
+                    float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
+                    const void *workspace, size_t workspace_bytes, const void *points, bool fl, int n_points,
+                    void *sample_ws, size_t sample_ws_bytes, void *stream)
 {
     Layout L;
     if (int rc = check_ws(dims, workspace, workspace_bytes, L)) return rc;
     long n_total = 0;
     if (int rc = check_points(dims, n_points, sample_ws, sample_ws_bytes, n_total)) return rc;
+    if (fl && !(dims->flags & GSASR_FLAG_CONTINUOUS)) return fail(GSASR_ERR_PLAN, QUERY_PLAN_ERR);
     if (dims->flags & GSASR_FLAG_FORWARD_ONLY) return fail(GSASR_ERR_PLAN, "the plan was made with GSASR_FLAG_FORWARD_ONLY: it holds no backward records");
     if (dims->s == 0) return GSASR_OK;
     if (!g_sigmas || !g_coords || !g_colors) return fail(GSASR_ERR_ARG, "null pointer");
@@ -547,7 +595,7 @@ int gsasr_splat_sample_backward(const float *sigmas, const float *coords, const 
         HIP_TRY(hipMemsetAsync(S.start, 0, (size_t)(S.ncx * S.ncy + 2) * 4, st));
     } else {
         if (points)   // NULL: sample_ws still holds the sorted points of the forward call
-            if (int rc = sort_points(P, V, S, points, (int)n_total, n_points, st)) return rc;
+            if (int rc = sort_points(P, V, S, points, fl, (int)n_total, n_points, st)) return rc;
         hipLaunchKernelGGL(k_pts_grads, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, st, S, grad_out, (int)n_total, n_points);
     }
     const dim3 grid((unsigned)(((size_t)dims->s * SB_LANES + 255) / 256)), block(256);   // SB_LANES lanes per Gaussian
@@ -557,45 +605,32 @@ int gsasr_splat_sample_backward(const float *sigmas, const float *coords, const 
     return GSASR_OK;
 }
 
-int gsasr_step_sample_forward(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
-                              size_t workspace_bytes, const int *points, int n_points, float *out, void *sample_ws,
-                              size_t sample_ws_bytes, void *stream)
+// the step forms, sampled pixels and (fl) queries: the prologue + plan of a whole-step call, then the plan-API form
+int step_sample_forward(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                        const void *points, bool fl, int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
 {
     StepLayout S;
-    StepSrc SS{};
-    SS.step = step_size;
     if (!dims) return fail(GSASR_ERR_ARG, "bad dims");
-    // (the sampled kernels walk the cells around their points: a plan made for them carries no tile lists.  All three sampled
-    // step entry points lay the workspace out the same way; gsasr_step_workspace_bytes(dims) is never smaller)
+    // (the sampled kernels walk the cells around their points: a plan made for them carries no tile lists.  All the sampled and
+    // query step entry points lay the workspace out the same way; gsasr_step_workspace_bytes(dims) is never smaller.  A query's
+    // plan is a continuous one)
     gsasr_dims dn = *dims;
     dn.list_cap = -1;
+    if (fl) dn.flags |= GSASR_FLAG_CONTINUOUS;
     if (int rc = step_prologue_plan(gs_parameters, SS, &dn, workspace, workspace_bytes, stream, S)) return rc;
-    return gsasr_splat_sample_forward(&dn, workspace, S.plan_bytes, points, n_points, out, sample_ws, sample_ws_bytes, stream);
+    return sample_forward(&dn, workspace, S.plan_bytes, points, fl, n_points, out, sample_ws, sample_ws_bytes, stream);
 }
 
-int gsasr_step_sample_forward_sm(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
-                                 int *mismatch, const gsasr_dims *dims, void *workspace, size_t workspace_bytes, const int *points,
-                                 int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
-{
-    StepLayout S;
-    StepSrc SS{};
-    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
-    if (!scale_modify && dims && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
-    if (!dims) return fail(GSASR_ERR_ARG, "bad dims");
-    gsasr_dims dn = *dims;      // (no tile lists for the sampled kernels: gsasr_step_sample_forward)
-    dn.list_cap = -1;
-    if (int rc = step_prologue_plan(gs_parameters, SS, &dn, workspace, workspace_bytes, stream, S)) return rc;
-    return gsasr_splat_sample_forward(&dn, workspace, S.plan_bytes, points, n_points, out, sample_ws, sample_ws_bytes, stream);
-}
-
-int gsasr_step_sample_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
-                               float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
-                               const int *points, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream)
+int step_sample_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
+                         float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                         const void *points, bool fl, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream)
 {
     if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims");
     if (dims->flags & GSASR_FLAG_STRIDE8) return fail(GSASR_ERR_ARG, "GSASR_FLAG_STRIDE8 does not apply to the step entry points");
     gsasr_dims dn = *dims;      // (the layout the sampled forward planned with: no tile lists)
     dn.list_cap = -1;
+    if (fl) dn.flags |= GSASR_FLAG_CONTINUOUS;
+    if (!dims_ok(&dn)) return fail(GSASR_ERR_ARG, "bad dims");
     dims = &dn;
     bool noted = false;
     const StepLayout S = make_step_layout(dims, workspace, &noted);
@@ -608,8 +643,8 @@ int gsasr_step_sample_backward(const float *gs_parameters, const float *step_siz
     if (!step_size) step_size = (const float *)(b + S.off_step);   // what the forward's prologue used
     gsasr_dims d = *dims;
     d.flags |= GSASR_FLAG_OVERWRITE_GRADS;
-    if (int rc = gsasr_splat_sample_backward(sig, xy, col, grad_out, gs, gc, gk, &d, workspace, S.plan_bytes, points, n_points,
-                                             sample_ws, sample_ws_bytes, stream))
+    if (int rc = sample_backward(sig, xy, col, grad_out, gs, gc, gk, &d, workspace, S.plan_bytes, points, fl, n_points,
+                                 sample_ws, sample_ws_bytes, stream))
         return rc;
     if (dims->s == 0) return GSASR_OK;
     if (!gs_parameters || !step_size || !g_parameters) return fail(GSASR_ERR_ARG, "null pointer");
@@ -617,6 +652,96 @@ int gsasr_step_sample_backward(const float *gs_parameters, const float *step_siz
         return prologue_backward_batched(gs_parameters, step_size, dims, workspace, gs, gc, gk, g_parameters, stream);
     }
     return gsasr_prologue_backward(gs_parameters, step_size, dims->s, dims->h, dims->w, gs, gc, gk, g_parameters, stream);
+}
+}  // namespace
+
+int gsasr_splat_sample_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const int *points,
+                               int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    return sample_forward(dims, workspace, workspace_bytes, points, false, n_points, out, sample_ws, sample_ws_bytes, stream);
+}
+
+int gsasr_splat_sample_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_out,
+                                float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
+                                const void *workspace, size_t workspace_bytes, const int *points, int n_points,
+                                void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    return sample_backward(sigmas, coords, colors, grad_out, g_sigmas, g_coords, g_colors, dims, workspace, workspace_bytes, points,
+                           false, n_points, sample_ws, sample_ws_bytes, stream);
+}
+
+int gsasr_step_sample_forward(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
+                              size_t workspace_bytes, const int *points, int n_points, float *out, void *sample_ws,
+                              size_t sample_ws_bytes, void *stream)
+{
+    StepSrc SS{};
+    SS.step = step_size;
+    return step_sample_forward(gs_parameters, SS, dims, workspace, workspace_bytes, points, false, n_points, out, sample_ws,
+                               sample_ws_bytes, stream);
+}
+
+int gsasr_step_sample_forward_sm(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
+                                 int *mismatch, const gsasr_dims *dims, void *workspace, size_t workspace_bytes, const int *points,
+                                 int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    StepSrc SS{};
+    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
+    if (!scale_modify && dims && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
+    return step_sample_forward(gs_parameters, SS, dims, workspace, workspace_bytes, points, false, n_points, out, sample_ws,
+                               sample_ws_bytes, stream);
+}
+
+int gsasr_step_sample_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
+                               float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                               const int *points, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    return step_sample_backward(gs_parameters, step_size, grad_out, g_parameters, dims, workspace, workspace_bytes, points, false,
+                                n_points, sample_ws, sample_ws_bytes, stream);
+}
+
+// ---- queries at fractional pixel positions (include/gsasr_splat.h): the same kernels behind a sort of float points ----
+int gsasr_splat_query_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const float *points,
+                              int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    return sample_forward(dims, workspace, workspace_bytes, points, true, n_points, out, sample_ws, sample_ws_bytes, stream);
+}
+
+int gsasr_splat_query_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_out,
+                               float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
+                               const void *workspace, size_t workspace_bytes, const float *points, int n_points,
+                               void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    return sample_backward(sigmas, coords, colors, grad_out, g_sigmas, g_coords, g_colors, dims, workspace, workspace_bytes, points,
+                           true, n_points, sample_ws, sample_ws_bytes, stream);
+}
+
+int gsasr_step_query_forward(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
+                             size_t workspace_bytes, const float *points, int n_points, float *out, void *sample_ws,
+                             size_t sample_ws_bytes, void *stream)
+{
+    StepSrc SS{};
+    SS.step = step_size;
+    return step_sample_forward(gs_parameters, SS, dims, workspace, workspace_bytes, points, true, n_points, out, sample_ws,
+                               sample_ws_bytes, stream);
+}
+
+int gsasr_step_query_forward_sm(const float *gs_parameters, const float *scale_modify, int sm_stride, float default_step_size,
+                                int *mismatch, const gsasr_dims *dims, void *workspace, size_t workspace_bytes, const float *points,
+                                int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    StepSrc SS{};
+    SS.sm = scale_modify; SS.stride = sm_stride; SS.def_step = default_step_size; SS.mismatch = mismatch;
+    if (!scale_modify && dims && dims->s > 0) return fail(GSASR_ERR_ARG, "null pointer");
+    return step_sample_forward(gs_parameters, SS, dims, workspace, workspace_bytes, points, true, n_points, out, sample_ws,
+                               sample_ws_bytes, stream);
+}
+
+int gsasr_step_query_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
+                              float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                              const float *points, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    return step_sample_backward(gs_parameters, step_size, grad_out, g_parameters, dims, workspace, workspace_bytes, points, true,
+                                n_points, sample_ws, sample_ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -242,6 +242,7 @@ int step_forward(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims,
                  size_t workspace_bytes, float *img, const StepU8 &u8, void *stream)
 {
     if (u8.on) if (int rc = u8_args_check(dims, u8.out, u8.rows, u8.cols, u8.pitch, u8.flags)) return rc;
+    if (dims && (dims->flags & GSASR_FLAG_CONTINUOUS)) return fail(GSASR_ERR_PLAN, CONTINUOUS_ERR);      // (before anything is planned)
     StepLayout S;
     if (int rc = step_prologue_plan(gs_parameters, SS, dims, workspace, workspace_bytes, stream, S, vw)) return rc;
     if (vw) {

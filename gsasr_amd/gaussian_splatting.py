@@ -5,6 +5,9 @@ arguments, defaults and error behaviour), with the CUDA ops replaced by the HIP 
         default_step_size=1.2, cuda_rendering=True, mode='scale_modify', if_dmax=True,
         dmax_mode='fix', dmax=25) -> [3,H,W]                      (reference :158-217)
     generate_2D_gaussian_splatting_step_buffer(..., buffer_size=4000000)   (reference :219-265)
+    generate_2D_gaussian_splatting_query(sr_size, gs_parameters, scale, scale_modify, query_coords, ...) -> [3,S]
+                                                                  (no reference counterpart: the splat evaluated at
+                                                                   fractional pixel positions (r, c) of the sr_size grid)
     rendering_cuda / rendering_cuda_dmax / rendering_cuda_buffer / rendering_cuda_dmax_buffer
                                                                   (reference :86-155)
     rendering_python                                               (reference :11-84)
@@ -289,6 +292,51 @@ class _FusedBatchSampled(torch.autograd.Function):
                 None, None, None, None)
 
 
+class _FusedStepQuery(torch.autograd.Function):
+    """`_FusedStepSampled` at fractional pixel positions: float `(r, c)` points on a continuous plan (`[3,S]`); the gradient
+    goes to `gs_parameters` only."""
+
+    @staticmethod
+    @fp32_boundary_fwd
+    def forward(ctx, gs_parameters, step, H, W, dmax, points, scale_modify=None, default_step=1.2):
+        from . import _cabi
+        out, plan, state = _cabi.step_query_forward(gs_parameters, step, H, W, dmax, points, scale_modify, default_step)
+        ctx.save_for_backward(gs_parameters, step)
+        ctx.plan, ctx.state = plan, state
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @fp32_boundary_bwd
+    def backward(ctx, grad_output):
+        from . import _cabi
+        gs_parameters, step = ctx.saved_tensors
+        return (_cabi.step_query_backward(ctx.plan, ctx.state, gs_parameters, step, grad_output.contiguous()),
+                None, None, None, None, None, None, None)
+
+
+class _FusedBatchQuery(torch.autograd.Function):
+    """`_FusedBatchSampled` for `query_coords[B,S,2]` (float) -> `[B,3,S]`."""
+
+    @staticmethod
+    @fp32_boundary_fwd
+    def forward(ctx, gs_parameters, steps, sizes, dmax, points):
+        from . import _cabi
+        out, plan, state = _cabi.batch_query_forward(gs_parameters, steps, sizes, dmax, points)
+        ctx.save_for_backward(gs_parameters, steps)
+        ctx.plan, ctx.state = plan, state
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @fp32_boundary_bwd
+    def backward(ctx, grad_output):
+        from . import _cabi
+        gs_parameters, steps = ctx.saved_tensors
+        return (_cabi.step_query_backward(ctx.plan, ctx.state, gs_parameters, steps, grad_output.contiguous()),
+                None, None, None, None)
+
+
 # Kernel time of the sampled path equals the full render's at about a quarter of the pixels, but the alternative ends
 # in a torch advanced-indexing gather whose backward (index_put_ with accumulate) takes longer than either rasterizer
 # (DESIGN.md 3b): the sampled kernels are used unless the points outnumber the pixels.
@@ -544,6 +592,74 @@ def generate_2D_gaussian_splatting_step(sr_size, gs_parameters, scale, scale_mod
     return _sample(final_image, sample_coords)
 
 
+def _as_query(query_coords, batched=False):
+    """`query_coords` as a floating-point `[S,2]` (`batched`: `[B,S,2]`) tensor of (r, c); the argument errors of the query API"""
+    qc = query_coords if torch.is_tensor(query_coords) else torch.as_tensor(query_coords)
+    if not qc.dtype.is_floating_point:
+        raise ValueError("query_coords must be floating point (fractional pixel indices (r, c)); integer pixel indices go to sample_coords")
+    if qc.dim() != (3 if batched else 2) or qc.shape[-1] != 2:
+        raise ValueError("query_coords must be [B,S,2]" if batched else "query_coords must be [S,2]")
+    if qc.requires_grad:
+        raise ValueError("query_coords.requires_grad: the gradient with respect to the positions is not implemented (detach them)")
+    return qc
+
+
+def query_dense(sigmas, xy, col, H, W, dmax, query_coords):
+    """The definition of a query, in plain differentiable torch (`[S,N]` terms): the point (r, c) sits at the pixel tables' own
+    expression with a real index, px = float(2 c / (W - 1) - 1) formed in double, and is worth the op's sum there -- the
+    reference kernels' exponent (gs_cuda/gs.cu:33-56) and, bounded op, their float32 box test |dx|, |dy| <= dmax per term.
+    Outside 0 <= r <= H - 1, 0 <= c <= W - 1 (NaN and infinities included): 0, and no gradient.  `sigmas, xy, col`: the
+    kernel-frame tensors (`_to_kernel_frame`).  The maths runs in float64; the result is `[3,S]` in the inputs' dtype."""
+    qc = query_coords.to(device=sigmas.device, dtype=torch.float32)
+    r, c = qc[:, 0], qc[:, 1]
+    valid = (r >= 0) & (r <= H - 1) & (c >= 0) & (c <= W - 1)
+    r, c = torch.where(valid, r, torch.zeros_like(r)), torch.where(valid, c, torch.zeros_like(c))
+    px = (2.0 * c.double() / (W - 1) - 1.0).float()
+    py = (2.0 * r.double() / (H - 1) - 1.0).float()
+    inside = valid[:, None].expand(-1, sigmas.shape[0])
+    if dmax is not None:   # the kernels' decision: float32 differences against the float32 dmax
+        dm = torch.tensor(float(dmax), dtype=torch.float32, device=sigmas.device)
+        dxf, dyf = px[:, None] - xy[:, 0].detach().float()[None, :], py[:, None] - xy[:, 1].detach().float()[None, :]
+        inside = inside & (dxf.abs() <= dm) & (dyf.abs() <= dm)
+    dx, dy = px.double()[:, None] - xy[:, 0].double()[None, :], py.double()[:, None] - xy[:, 1].double()[None, :]
+    sx, sy, rho = sigmas[:, 0].double()[None, :], sigmas[:, 1].double()[None, :], sigmas[:, 2].double()[None, :]
+    d = dx * dx / (sx * sx) - 2 * rho * dx * dy / (sx * sy) + dy * dy / (sy * sy)
+    v = torch.where(inside, torch.exp(-0.5 / (1 - rho * rho) * d), torch.zeros((), dtype=torch.float64, device=sigmas.device))
+    return (v @ col.double()).t().to(col.dtype)
+
+
+def generate_2D_gaussian_splatting_query(sr_size, gs_parameters, scale, scale_modify, query_coords, default_step_size=1.2,
+                                         cuda_rendering=True, mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25):
+    """The splatted image at fractional pixel positions: `query_coords` float `[S,2]` (tensor or nested list) of (r, c) on the
+    `sr_size` grid -> `[3,S]`, differentiable in `gs_parameters`.  The Gaussians are a continuous image; pixel (i, j) of
+    `generate_2D_gaussian_splatting_step` is the query (i, j), and (i + 0.5, j) lies halfway to the next row.  Domain:
+    0 <= r <= H - 1, 0 <= c <= W - 1, ends included; a point outside it, or with a NaN / infinite component, gives 0 and no
+    gradient.  Repeated points are independent outputs whose gradients add.  Not differentiable in the positions
+    (`query_coords.requires_grad` raises).  CUDA tensors: the HIP query kernels (fused prologue, fp32 under autocast); CPU
+    tensors or `cuda_rendering=False`: the dense torch evaluation `query_dense`, never a fallback for the kernels."""
+    qc = _as_query(query_coords)
+    if gs_parameters.dtype != torch.float32:
+        gs_parameters = gs_parameters.float()
+    if gs_parameters.dim() != 2 or gs_parameters.shape[1] != 9:
+        raise ValueError("gs_parameters must be [N,9]")
+    H, W = _hw(sr_size)
+    dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
+    dm = None if dmax_eff is None else float(dmax_eff)
+    fused = cuda_rendering and gs_parameters.is_cuda
+    step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=fused)
+    if fused:
+        if qc.shape[0] == 0:
+            return gs_parameters.new_zeros((3, 0)) + 0.0 * gs_parameters.sum()
+        if step_size.__class__ is _StepSource:
+            out = _FusedStepQuery.apply(gs_parameters.contiguous(), None, H, W, dm, qc, step_size.scale_modify, step_size.default_step)
+            deferred_asserts.watch(gs_parameters.device)
+            return out
+        return _FusedStepQuery.apply(gs_parameters.contiguous(), _step_tensor(step_size, gs_parameters.device), H, W, dm, qc)
+    sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
+    sigmas, xy, col, H, W = _to_kernel_frame(sigma_x, sigma_y, rho, coords, colours_with_alpha, (H, W), step_size)
+    return query_dense(sigmas, xy, col, H, W, dm, qc)
+
+
 def quantise_uint8(image, crop=None, bgr=False):
     """The reference's inference epilogue (inference_paper.py:134-140, basicsr/utils/img_util.py:73-96) with torch ops: planar
     float `[3,H,W]` -> uint8 `[crop_h, crop_w, 3]` = `(clamp(x[:, :crop_h, :crop_w], 0, 1) * 255).round()` (half to even, like
@@ -710,13 +826,21 @@ def max_canvas_batch(h_max: int) -> int:
 
 
 def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_modifies, default_step_size=1.2,
-                                         mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, sample_coords=None):
+                                         mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, sample_coords=None,
+                                         query_coords=None):
     """Batched `generate_2D_gaussian_splatting_step`: `gs_parameters` `[B,N,9]`, per-sample
     `sr_sizes[b]`, `scales[b]`, `scale_modifies[b]`; returns `[B,3,Hmax,Wmax]` with every sample zero-padded to
     the largest size -- exactly `torch.stack([F.pad(step(...), ...)])` of the reference's loop.  With
     `sample_coords` `[B,S,2]` (row, column on each sample's own grid; gsasr_model.py:196-197) it returns the
-    `[B,3,S]` stack of the per-sample `[3,S]` results instead."""
+    `[B,3,S]` stack of the per-sample `[3,S]` results instead.  With `query_coords` float `[B,S,2]` (fractional (r, c) on each
+    sample's own grid: `generate_2D_gaussian_splatting_query`) likewise `[B,3,S]`; passing both is a ValueError."""
     B = gs_parameters.shape[0]
+    if query_coords is not None:
+        if sample_coords is not None:
+            raise ValueError("pass sample_coords (integer pixels) or query_coords (fractional positions), not both")
+        query_coords = _as_query(query_coords, batched=True)
+        if query_coords.shape[0] != B:
+            raise ValueError("query_coords must be [B,S,2]")
     if torch.is_tensor(sr_sizes) and sr_sizes.dim() == 2:      # e.g. the [B,2] GPU tensor of gsasr_model.py:147: ONE copy to the host
         sizes = [(int(r[0]), int(r[1])) for r in sr_sizes.tolist()]
     else:
@@ -732,9 +856,10 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
         # one possibly a single sample (which takes the per-sample path below)
         parts = [generate_2D_gaussian_splatting_batch(sr_sizes[a: a + cap], gs_parameters[a: a + cap], scales[a: a + cap],
                                                       scale_modifies[a: a + cap], default_step_size, mode, if_dmax, dmax_mode,
-                                                      dmax, None if sample_coords is None else sample_coords[a: a + cap])
+                                                      dmax, None if sample_coords is None else sample_coords[a: a + cap],
+                                                      None if query_coords is None else query_coords[a: a + cap])
                  for a in range(0, B, cap)]
-        if sample_coords is None:
+        if sample_coords is None and query_coords is None:
             h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
             parts = [F.pad(o, (0, w_max - o.shape[3], 0, h_max - o.shape[2])) for o in parts]
         return torch.cat(parts)
@@ -742,7 +867,7 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
         dev = gs_parameters.device
         dmax_eff = _resolve_dmax(dmax, dmax_mode, sizes[0]) if if_dmax else None
         dm = None if dmax_eff is None else float(dmax_eff)
-        if sample_coords is None and mode == 'scale_modify':
+        if sample_coords is None and query_coords is None and mode == 'scale_modify':
             # scale_modify pairs that are already on the device go to the plan's first kernel as they are (one [B,2]
             # tensor: no kernel at all; a list of [2] tensors: one torch.stack): no division, comparison or copy here
             sm = None
@@ -758,16 +883,23 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
                 deferred_asserts.watch(dev)
                 return out
         steps = _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev)
-        if sample_coords is None:
+        if query_coords is not None and query_coords.shape[1] > 0:
+            return _FusedBatchQuery.apply(gs_parameters.contiguous(), steps, tuple(sizes), dm, query_coords)
+        if sample_coords is None and query_coords is None:
             return _fused_batch(gs_parameters.contiguous(), steps, tuple(sizes), dm)
-        pts = sample_coords if torch.is_tensor(sample_coords) else torch.as_tensor(sample_coords)
-        if pts.dim() == 3 and pts.shape[0] == B and pts.shape[2] == 2 and not pts.dtype.is_floating_point \
+        pts = None if sample_coords is None else sample_coords if torch.is_tensor(sample_coords) else torch.as_tensor(sample_coords)
+        if pts is not None and pts.dim() == 3 and pts.shape[0] == B and pts.shape[2] == 2 and not pts.dtype.is_floating_point \
                 and 0 < pts.shape[1] <= SAMPLED_MAX_FRACTION * min(h * w for h, w in sizes):
             return _FusedBatchSampled.apply(gs_parameters.contiguous(), steps, tuple(sizes), dm, pts)
     # per-sample path (single sample, > 64 samples, or a per-sample dmax): same kernels, one sample at a time
     h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
     outs = []
     for b in range(B):
+        if query_coords is not None:
+            outs.append(generate_2D_gaussian_splatting_query(sr_sizes[b], gs_parameters[b], scales[b], scale_modifies[b], query_coords[b],
+                                                             default_step_size=default_step_size, mode=mode, if_dmax=if_dmax,
+                                                             dmax_mode=dmax_mode, dmax=dmax))
+            continue
         o = generate_2D_gaussian_splatting_step(sr_sizes[b], gs_parameters[b], scales[b], scale_modifies[b],
                                                 sample_coords=None if sample_coords is None else sample_coords[b],
                                                 default_step_size=default_step_size, mode=mode, if_dmax=if_dmax,

@@ -116,6 +116,15 @@ enum gsasr_status {
                                          is the same).  _WIDE forces the 16 x 16 kernel on ANY single image (tests, A/B runs),
                                          a batched canvas ignores it; _NARROW leaves the choice among the 8 x 16 kernels to the
                                          image size.  Same sums in a different order: results agree to fp32 rounding */
+#define GSASR_FLAG_CONTINUOUS 65536u   /* plan for queries BETWEEN the pixel centres (gsasr_splat_query_*, below): every Gaussian's
+                                         window is widened by one pixel on each side before it is found empty or clipped, so
+                                         that a point within half a pixel of a pixel centre finds every Gaussian whose support
+                                         holds it -- a plain plan drops a Gaussian whose support lies between the centres.
+                                         Such a plan serves the query and the sampled-pixel entry points only: it carries no
+                                         tile lists and no slots (laid out as with list_cap < 0), looks up no registered kernel
+                                         choice, and the image forwards / backwards on it are GSASR_ERR_PLAN.  With a
+                                         kernel-choice flag, list_cap > 0, a row band or a view: GSASR_ERR_ARG / a workspace
+                                         size of 0.  Part of what the plan IS: every call on the workspace passes it too */
 
 typedef struct gsasr_dims {
     int s;        /* number of Gaussians                                              */
@@ -370,6 +379,41 @@ GSASR_API int gsasr_step_sample_forward_sm(const float *gs_parameters, const flo
 GSASR_API int gsasr_step_sample_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
                                float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
                                const int *points, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream);
+
+/* Queries at fractional pixel positions: the set of Gaussians is a continuous image, evaluated anywhere on the closed grid
+ * rectangle.  The five entry points mirror the sampled-pixel ones argument for argument, with float points:
+ *
+ *   points    device float32 [n_points, 2] = fractional pixel indices (r, c) on the image's own h x w grid (batched canvas:
+ *             [B, n_points, 2] on sample b's own h_b x w_b).  The point sits at
+ *                 px = (float)(2.0 * (double)c / (double)(w - 1) - 1.0),  py = (float)(2.0 * (double)r / (double)(h - 1) - 1.0)
+ *             -- the pixel tables' own expression with a real index: integer-valued (r, c) give the tables' floats bit for
+ *             bit, and the value there IS pixel (r, c).  The value at a point is the op's own sum at (px, py): same exponent,
+ *             same |dx|, |dy| <= dmax test per term (bounded op), same cutoff rules and the same 1e-5 * max|colour| bound of
+ *             the adaptive cutoff.  Domain: 0 <= r <= h - 1 and 0 <= c <= w - 1, both ends included; a point outside it or
+ *             with a NaN / infinite component yields 0 and takes no part in the backward (no wrap-around).  Repeated points
+ *             are independent outputs whose gradients add.
+ *   workspace a plan made with GSASR_FLAG_CONTINUOUS (gsasr_splat_plan; the step forms set the flag and list_cap = -1
+ *             themselves).  The plan-API forms on a workspace whose plan lacks the flag: GSASR_ERR_PLAN -- never a silently
+ *             incomplete sum.  The integer sampled points may be evaluated on a continuous plan too (same terms).
+ *   out, grad_out, sample_ws (gsasr_sample_workspace_bytes serves both kinds), points = NULL in the backward, flags, errors:
+ *             as for the sampled pixels.
+ * The backward is the gradient of sum(grad_out * out) with respect to the Gaussians; the positions themselves get none. */
+GSASR_API int gsasr_splat_query_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const float *points,
+                              int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream);
+GSASR_API int gsasr_splat_query_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_out,
+                               float *g_sigmas, float *g_coords, float *g_colors, const gsasr_dims *dims,
+                               const void *workspace, size_t workspace_bytes, const float *points, int n_points,
+                               void *sample_ws, size_t sample_ws_bytes, void *stream);
+GSASR_API int gsasr_step_query_forward(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
+                             size_t workspace_bytes, const float *points, int n_points, float *out, void *sample_ws,
+                             size_t sample_ws_bytes, void *stream);
+GSASR_API int gsasr_step_query_forward_sm(const float *gs_parameters, const float *scale_modify, int sm_stride,
+                                float default_step_size, int *mismatch, const gsasr_dims *dims, void *workspace,
+                                size_t workspace_bytes, const float *points, int n_points, float *out, void *sample_ws,
+                                size_t sample_ws_bytes, void *stream);
+GSASR_API int gsasr_step_query_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
+                              float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                              const float *points, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream);
 
 /* Reference-shaped launchers: the argument lists of `_gs_render` / `_gs_render_backward` in utils/gs_cuda/gs.h:4-24 and
  * utils/gs_cuda_dmax/gs.h:4-26 (+ the stream, + a status instead of void).  The reference's launchers take no workspace,
