@@ -32,7 +32,7 @@ FLAG_COUNTERS_CLEAN = 1024 # GSASR_FLAG_COUNTERS_CLEAN
 FLAG_PARITY = 2048         # GSASR_FLAG_PARITY
 FLAG_CUTOFF_CAP = 4096     # GSASR_FLAG_CUTOFF_CAP
 FLAG_FWD_WIDE, FLAG_FWD_NARROW = 8192, 16384      # forward kernel choice (development A/B, tests): 16x16 / 8x16 sub-tiles
-FLAG_CONTINUOUS = 65536    # GSASR_FLAG_CONTINUOUS: a plan for queries between the pixel centres (query_forward / query_backward)
+FLAG_CONTINUOUS = 65536    # GSASR_FLAG_CONTINUOUS: a plan for queries between the pixel centres (query_forward / query_backward[_points])
 U8_SWAP_RB = 1             # GSASR_U8_SWAP_RB (u8_flags of the 8-bit forwards)
 EXACT_CUTOFF = 104.0    # GSASR_SPLAT_EXACT_CUTOFF
 NO_CUTOFF = -1.0
@@ -89,6 +89,8 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_step_query_forward": (_i, [_vp, _vp] + _sample_tail),
     "gsasr_step_query_forward_sm": (_i, [_vp, _vp, _i, _f, _vp] + _sample_tail),
     "gsasr_step_query_backward": (_i, [_vp, _vp, _vp, _vp, _dp, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "gsasr_splat_query_backward_points": (_i, [_dp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "gsasr_step_query_backward_points": (_i, [_dp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "gsasr_set_default_cutoff": (None, [_f]),
     "gsasr_get_default_cutoff": (_f, []),
     "gsasr_resolve_cutoff": (_f, [_f, _i]),
@@ -1019,6 +1021,28 @@ def step_sample_backward(p: Plan, state, gs_parameters: torch.Tensor, step: torc
                                     p.workspace.numel(), None, n, sws.data_ptr(), sws.numel(),
                                     _stream(p.device)), _name)
     return gp
+
+
+def query_backward_points(p: Plan, state, grad_out: torch.Tensor, resort: bool = False,
+                          _name: str = "gsasr_splat_query_backward_points") -> torch.Tensor:
+    """gradient of sum(grad_out * query_forward(...)) w.r.t. the POSITIONS: float32 `[S,2]` (`[B,S,2]`) of (d/dr, d/dc), every row
+    written (a point outside the domain: zeros).  `state` is what `query_forward` returned; `p` may be a FLAG_FORWARD_ONLY plan."""
+    pts, n, sws = state
+    B = max(int(p.dims.batch), 1)
+    pg = _chk(grad_out, "grad_out", (3, n))
+    if grad_out.numel() != B * 3 * n:
+        raise RuntimeError("grad_out does not match the points")
+    with _on(p.device):
+        gpts = torch.empty((B, n, 2) if B > 1 else (n, 2), dtype=torch.float32, device=p.device)
+        check(getattr(lib(), _name)(ctypes.byref(p.dims), p.workspace.data_ptr(), p.workspace.numel(), pg,
+                                    pts.data_ptr() if resort else None, n, gpts.data_ptr(), sws.data_ptr(), sws.numel(),
+                                    _stream(p.device)), _name)
+    return gpts
+
+
+def step_query_backward_points(p: Plan, state, grad_out: torch.Tensor) -> torch.Tensor:
+    """`query_backward_points` on the plan of `step_query_forward` / `batch_query_forward` (needs no gs_parameters)"""
+    return query_backward_points(p, state, grad_out, _name="gsasr_step_query_backward_points")
 
 
 def set_default_cutoff(tau: float) -> None:

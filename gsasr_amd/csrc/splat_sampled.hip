@@ -1,4 +1,5 @@
-// splat_sampled.hip -- sampled pixels (the reference's sample_coords): sort of the points, point-stationary forward, Gaussian-stationary backward
+// splat_sampled.hip -- sampled pixels (the reference's sample_coords): sort of the points, point-stationary forward, Gaussian-stationary backward,
+// point-stationary backward with respect to the positions of a query
 // (one translation unit of libgsasr_splat.so; gsasr_splat.hip has the overview of the whole pipeline)
 #include "splat_common.h"
 
@@ -19,6 +20,8 @@ namespace {
 //                 all the block's points; no atomics on the output.
 //   k_sample_bwd  GAUSSIAN-stationary, eight Gaussians per wave64: a Gaussian's 8 lanes stride over the sorted points
 //                 of the point-cells its window touches; same sums and epilogue as k_render_bwd.
+//   k_query_bwd_pts  POINT-stationary again: the gradient of a query with respect to its positions, k_sample_fwd's walk with
+//                 two derivative sums per point instead of three colour sums; no atomics on the output.
 // ---------------------------------------------------------------------------------------------------
 constexpr int PT_CELLS = 12288;                    // point-cells at most: their histogram + scan live in LDS (48 KB)
 constexpr int PT_MIN_SHIFT = 3, PT_MAX_SHIFT = 9;  // point-cells are 8..512 px a side
@@ -469,6 +472,222 @@ __global__ __launch_bounds__(256) void k_sample_bwd(Params P, PlanView V, PtView
     }
 }
 
+// Gradient of a query with respect to its POSITIONS (gsasr_splat_query_backward_points): point-stationary, the two-level
+// walk of k_sample_fwd with another level 2.  With w_sj = sum_k grad_out[k, s] col[j, k] and the forward's exponent in base 2,
+// t = exp2(-(u^2 + q^2)), u = IX dx, q = IY dy + NR u (the completed square: no cancellation at saturated rho),
+//   d t / d px = -2 ln 2 * t * IX (u + NR q)          d t / d py = -2 ln 2 * t * IY q
+// so a lane sums w t IX (u + NR q) and w t IY q over its Gaussians -- the per-Gaussian factors inside the sum -- and the
+// constant -2 ln 2 with the point's own 2 / (w - 1), 2 / (h - 1) goes on once, at the store.  The term set is the forward's: the
+// same survivors, no window test per point, the dmax box per term.  Neither the box test nor the rounding of px is
+// differentiated (the almost-everywhere derivative); a point on the edge of the domain gets the analytic value.
+// Level 1 is k_sample_fwd's, line for line (a helper shared with it changes that kernel's register allocation; the copy
+// leaves it as it was).  Staged per PAIR of points, so that each packed-fp32 operand is one aligned register pair of a
+// 16-byte broadcast read: {px0, px1, py0, py1}, {gr0, gr1, gg0, gg1}, {gb0, gb1}; a missing partner is staged as zeros.
+// Two accumulators per point and lane.  Points per walk from the compiler's register report at 4 waves per SIMD (128 VGPRs):
+// 24: 120 VGPRs, 28: 126, both without scratch; 32: 5 spilled VGPRs, 24 bytes of scratch.  Timed, 28 against 24: 0.0533 against
+// 0.0544 ms on 1024^2 with 65 536 points, no difference on the config-5 batch.
+constexpr int QGRAD_BLOCK = 28;
+
+template <bool TEST>
+__device__ __forceinline__ void query_grad_eval(const float4 *s_xy, const float4 *s_ga, const float2 *s_gb, int npb, const float4 a,
+                                                const float4 b, float dmax, v2f (&acc)[QGRAD_BLOCK / 2][2])
+{
+#pragma unroll
+    for (int k = 0; k < QGRAD_BLOCK / 2; ++k) {
+        if (2 * k >= npb) continue;   // (uniform)
+        const float4 xy = s_xy[k], ga = s_ga[k];
+        const float2 gb = s_gb[k];
+        const v2f dx = (v2f){xy.x, xy.y} - a.x, dy = (v2f){xy.z, xy.w} - a.y;
+        const v2f u = a.z * dx;
+        const v2f bq = b.x * dy + a.w * u;
+        const v2f pw = -(u * u) - bq * bq;
+        v2f v = {__builtin_amdgcn_exp2f(pw.x), __builtin_amdgcn_exp2f(pw.y)};
+        if (TEST) {   // (dmax = +inf for the lanes whose Gaussian needs no test)
+            v.x = fmaxf(fabsf(dx.x), fabsf(dy.x)) <= dmax ? v.x : 0.f;
+            v.y = fmaxf(fabsf(dx.y), fabsf(dy.y)) <= dmax ? v.y : 0.f;
+        }
+        const v2f wt = ((v2f){ga.x, ga.y} * b.y + (v2f){ga.z, ga.w} * b.z + (v2f){gb.x, gb.y} * b.w) * v;
+        acc[k][0] += wt * (a.z * (u + a.w * bq));
+        acc[k][1] += wt * (b.x * bq);
+    }
+}
+
+template <bool BOUNDED>
+__global__ __launch_bounds__(64 * SAMPLE_WAVES) __attribute__((amdgpu_waves_per_eu(4))) void k_query_bwd_pts(Params P, PlanView V, PtView S, int n_per,
+                                                                    float *__restrict__ g_points)
+{
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int fsx = max(S.shx, CELL_SHIFT), fsy = max(S.shy, CELL_SHIFT);
+    const int nbx = ((P.w - 1) >> fsx) + 1, nby = ((P.h - 1) >> fsy) + 1, npc = S.ncx * S.ncy;
+    const int blk = (int)blockIdx.x == nbx * nby ? nbx * nby : (int)xcd_swizzle(blockIdx.x, (unsigned)(nbx * nby));
+    if (blk == nbx * nby) {   // the out-of-range points: no gradient
+        const unsigned pbeg = S.start[npc], pend = S.start[npc + 1];
+        for (unsigned i = pbeg + threadIdx.x; i < pend; i += 64 * SAMPLE_WAVES) {
+            float *o = g_points + 2 * (size_t)__float_as_uint(S.sorted[i].w);
+            o[0] = 0.f; o[1] = 0.f;
+        }
+        return;
+    }
+    const int bxi = blk % nbx, byi = blk / nbx;
+    const int px0 = bxi << (fsx - S.shx), px1 = min(px0 + (1 << (fsx - S.shx)), S.ncx);   // point-cell columns [px0, px1)
+    const int py0 = byi << (fsy - S.shy), two = (fsy > S.shy && py0 + 1 < S.ncy) ? 1 : 0;  // one or two rows of them
+    const unsigned beg0 = S.start[py0 * S.ncx + px0], n0 = S.start[py0 * S.ncx + px1] - beg0;
+    const unsigned beg1 = two ? S.start[(py0 + 1) * S.ncx + px0] : 0u;
+    const unsigned n1 = two ? S.start[(py0 + 1) * S.ncx + px1] - beg1 : 0u;
+    const unsigned pend = n0 + n1;   // the block's points, numbered through both rows
+    if (pend == 0u) return;
+    __shared__ unsigned s_list[SAMPLE_LIST];
+    __shared__ unsigned s_cnt[2];
+    __shared__ float4 s_xy[QGRAD_BLOCK / 2];   // per pair of points {px0, px1, py0, py1}
+    __shared__ float4 s_ga[QGRAD_BLOCK / 2];   // ... their upstream gradients {r0, r1, g0, g1}
+    __shared__ float2 s_gb[QGRAD_BLOCK / 2];   // ... {b0, b1}
+    __shared__ unsigned s_idx[QGRAD_BLOCK];    // original index
+    __shared__ float s_acc[2 * QGRAD_BLOCK];
+    const int bx0 = bxi << fsx, by0 = byi << fsy;
+    const int bx1 = min(bx0 + (1 << fsx), P.w) - 1, by1 = min(by0 + (1 << fsy), P.h) - 1;
+    const float4 *__restrict__ rec = V.rec;
+    const unsigned *__restrict__ cs = V.cell_start;
+
+    // segment table of the rectangle (every wave builds the same one)
+    const int rx = (int)V.hdr[8], ry = (int)V.hdr[9];
+    int nseg = 0;
+    unsigned sbeg = 0, send = 0;
+    if (rx > 0) {
+        const int cx0 = max(bx0 - rx, 0) >> CELL_SHIFT, cx1 = min((bx1 + rx) >> CELL_SHIFT, P.ncx - 1);
+        const int cy0 = max(by0 - ry, 0) >> CELL_SHIFT, cy1 = min((by1 + ry) >> CELL_SHIFT, P.ncy - 1);
+        nseg = cy1 - cy0 + 1;
+        if (lane < nseg) {
+            sbeg = cs[(cy0 + lane) * P.ncx + cx0];
+            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
+        }
+    }
+    if (lane == nseg) {
+        sbeg = cs[P.ncells];
+        send = cs[P.ncells + 1];
+    }
+    ++nseg;
+    const unsigned long long below = (1ull << lane) - 1ull;
+
+    for (unsigned pb = 0u; pb < pend; pb += QGRAD_BLOCK) {   // (more than QGRAD_BLOCK points in the block: walk again)
+        const int npb = (int)min((unsigned)QGRAD_BLOCK, pend - pb);
+        if ((int)threadIdx.x < QGRAD_BLOCK) {
+            float4 pt = make_float4(0.f, 0.f, 0.f, 0.f), gr = pt;
+            if ((int)threadIdx.x < npb) {
+                const unsigned pi = pb + threadIdx.x, at = pi < n0 ? beg0 + pi : beg1 + (pi - n0);
+                pt = S.sorted[at];
+                gr = S.grads[at];
+            }
+            const int k = threadIdx.x >> 1, o = threadIdx.x & 1;
+            float *xy = reinterpret_cast<float *>(s_xy + k), *ga = reinterpret_cast<float *>(s_ga + k), *gb = reinterpret_cast<float *>(s_gb + k);
+            xy[o] = pt.x; xy[2 + o] = pt.y;
+            ga[o] = gr.x; ga[2 + o] = gr.y;
+            gb[o] = gr.z;
+            s_idx[threadIdx.x] = __float_as_uint(pt.w);
+        }
+        if (threadIdx.x < 2 * QGRAD_BLOCK) s_acc[threadIdx.x] = 0.f;
+        if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
+        __syncthreads();
+        v2f acc[QGRAD_BLOCK / 2][2];   // per lane: {d/dpx, d/dpy} sums of the block's points, two points per register pair
+#pragma unroll
+        for (int k = 0; k < QGRAD_BLOCK / 2; ++k) acc[k][0] = acc[k][1] = (v2f){0.f, 0.f};
+        int r = 0;
+        unsigned i0 = (unsigned)__builtin_amdgcn_readlane((int)sbeg, 0), se = (unsigned)__builtin_amdgcn_readlane((int)send, 0);
+        constexpr unsigned BATCH = 64u * SAMPLE_WAVES * SAMPLE_CHUNKS;
+        for (unsigned round = 0;; ++round) {
+            unsigned *cnt = s_cnt + (round & 1u);
+            // ---- level 1 (k_sample_fwd's): the Gaussians whose window meets the block's rectangle -> the survivor list
+            for (unsigned proc = 0; r < nseg && proc + BATCH <= (unsigned)SAMPLE_LIST;) {
+                if (i0 >= se) {
+                    if (++r < nseg) {
+                        i0 = (unsigned)__builtin_amdgcn_readlane((int)sbeg, r);
+                        se = (unsigned)__builtin_amdgcn_readlane((int)send, r);
+                    }
+                    continue;
+                }
+                uint2 cw[SAMPLE_CHUNKS];
+#pragma unroll
+                for (int k = 0; k < SAMPLE_CHUNKS; ++k) {
+                    const unsigned i = i0 + 64u * SAMPLE_WAVES * (unsigned)k + (unsigned)threadIdx.x;
+                    cw[k] = make_uint2(0x7fffu, 0x7fffu);   // a window that overlaps nothing
+                    if (i < se) cw[k] = V.win[i];
+                }
+#pragma unroll
+                for (int k = 0; k < SAMPLE_CHUNKS; ++k) {
+                    if (i0 + 64u * SAMPLE_WAVES * (unsigned)k >= se) continue;   // (uniform)
+                    const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
+                    const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
+                    const bool hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
+                    const unsigned long long m = __ballot(hit);
+                    if (m) {
+                        unsigned at = 0;
+                        if (lane == 0) at = atomicAdd(cnt, (unsigned)__builtin_popcountll(m));
+                        at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
+                        // entry = index | "needs the dmax test" (window word bit 15) << 31
+                        if (hit) s_list[at + (unsigned)__builtin_popcountll(m & below)] =
+                            (i0 + 64u * SAMPLE_WAVES * (unsigned)k + (unsigned)threadIdx.x) | ((cw[k].x & 0x8000u) << 16);
+                    }
+                }
+                i0 += BATCH;
+                proc += BATCH;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0u;
+            const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)*cnt);
+            // ---- level 2: a survivor per lane, loaded once (the next one in flight), differentiated at every staged point
+            unsigned q = (unsigned)wv * 64u;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;   // {x, y, IX, NR}, {IY, r, g, b}; dead lanes add 0
+            bool test = false;
+            if (q + (unsigned)lane < n) {
+                const unsigned e = s_list[q + lane], j = e & 0x7fffffffu;
+                a = rec[2 * (size_t)j];
+                b = rec[2 * (size_t)j + 1];
+                test = (e >> 31) != 0u;
+            }
+            while (q < n) {
+                asm volatile("" ::: "memory");   // re-read the points from LDS every trip (hoisted, they take the accumulators' registers)
+                const unsigned nq = q + 64u * SAMPLE_WAVES;
+                float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
+                bool ntest = false;
+                if (nq + (unsigned)lane < n) {
+                    const unsigned e = s_list[nq + lane], j = e & 0x7fffffffu;
+                    na = rec[2 * (size_t)j];
+                    nb = rec[2 * (size_t)j + 1];
+                    ntest = (e >> 31) != 0u;
+                }
+                query_grad_eval<BOUNDED>(s_xy, s_ga, s_gb, npb, a, b, test ? P.dmax : INFINITY, acc);
+                q = nq; a = na; b = nb; test = ntest;
+            }
+            if (r >= nseg) break;   // (uniform)
+            __syncthreads();        // the list is rewritten by the next round
+        }
+        // one reduction per block: over the lanes with DPP, over the waves in LDS
+#pragma unroll
+        for (int k = 0; k < QGRAD_BLOCK / 2; ++k) {
+            if (2 * k >= npb) continue;   // (uniform)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const float t0 = wave_sum_dpp(acc[k][c].x), t1 = wave_sum_dpp(acc[k][c].y);
+                if (lane == 0) {
+                    atomicAdd(&s_acc[2 * (2 * k) + c], t0);
+                    atomicAdd(&s_acc[2 * (2 * k + 1) + c], t1);
+                }
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < npb) {
+            constexpr float N2LN2 = -1.38629436111989061883f;   // d exp2(e) / d e, and the 2 of the squares
+            const int idx = (int)s_idx[threadIdx.x];
+            const Geo g = sample_geo(P, V, idx / n_per);
+            const float kr = g.h > 1 ? N2LN2 * 2.f / (float)(g.h - 1) : 0.f, kc = g.w > 1 ? N2LN2 * 2.f / (float)(g.w - 1) : 0.f;
+            // [B, n_per, 2]: (d/dr, d/dc)
+            g_points[2 * (size_t)idx] = s_acc[2 * threadIdx.x + 1] * kr;
+            g_points[2 * (size_t)idx + 1] = s_acc[2 * threadIdx.x] * kc;
+        }
+        __syncthreads();   // the staged points and s_acc are rewritten for the next block of points
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -601,6 +820,38 @@ int sample_backward(const float *sigmas, const float *coords, const float *color
     const dim3 grid((unsigned)(((size_t)dims->s * SB_LANES + 255) / 256)), block(256);   // SB_LANES lanes per Gaussian
     if (P.bounded) hipLaunchKernelGGL(k_sample_bwd<true>, grid, block, 0, st, P, V, S, g_sigmas, g_coords, g_colors);
     else hipLaunchKernelGGL(k_sample_bwd<false>, grid, block, 0, st, P, V, S, g_sigmas, g_coords, g_colors);
+    HIP_TRY(hipGetLastError());
+    return GSASR_OK;
+}
+
+// gradient of a query with respect to its positions: the gather of grad_out into the sorted order + k_query_bwd_pts.  Only the
+// forward's records (rec, win) are read, so a GSASR_FLAG_FORWARD_ONLY plan serves; every point's row of g_points is WRITTEN.
+int query_backward_points(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const float *grad_out,
+                          const float *points, int n_points, float *g_points, void *sample_ws, size_t sample_ws_bytes, void *stream)
+{
+    Layout L;
+    if (int rc = check_ws(dims, workspace, workspace_bytes, L)) return rc;
+    long n_total = 0;
+    if (int rc = check_points(dims, n_points, sample_ws, sample_ws_bytes, n_total)) return rc;
+    if (!(dims->flags & GSASR_FLAG_CONTINUOUS)) return fail(GSASR_ERR_PLAN, QUERY_PLAN_ERR);
+    if (n_total == 0) return GSASR_OK;
+    if (!grad_out || !g_points) return fail(GSASR_ERR_ARG, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (dims->s == 0) {   // no Gaussians: the image is 0 everywhere
+        HIP_TRY(hipMemsetAsync(g_points, 0, (size_t)n_total * 2 * sizeof(float), st));
+        return GSASR_OK;
+    }
+    const Params P = make_params(dims, L);
+    const PlanView V = make_view(L, const_cast<void *>(workspace));
+    const PtView S = make_pt_view(dims, sample_ws, n_total);
+    if (points)   // NULL: sample_ws still holds the sorted points of the forward call
+        if (int rc = sort_points(P, V, S, points, true, (int)n_total, n_points, st)) return rc;
+    // (gathered here, whether or not a Gaussian backward has filled S.grads before: the call stands on its own)
+    hipLaunchKernelGGL(k_pts_grads, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, st, S, grad_out, (int)n_total, n_points);
+    const int fsx = S.shx > CELL_SHIFT ? S.shx : CELL_SHIFT, fsy = S.shy > CELL_SHIFT ? S.shy : CELL_SHIFT;
+    const dim3 grid((unsigned)((((dims->w - 1) >> fsx) + 1) * (((dims->h - 1) >> fsy) + 1) + 1)), block(64 * SAMPLE_WAVES);
+    if (P.bounded) hipLaunchKernelGGL(k_query_bwd_pts<true>, grid, block, 0, st, P, V, S, n_points, g_points);
+    else hipLaunchKernelGGL(k_query_bwd_pts<false>, grid, block, 0, st, P, V, S, n_points, g_points);
     HIP_TRY(hipGetLastError());
     return GSASR_OK;
 }
@@ -742,6 +993,34 @@ int gsasr_step_query_backward(const float *gs_parameters, const float *step_size
 {
     return step_sample_backward(gs_parameters, step_size, grad_out, g_parameters, dims, workspace, workspace_bytes, points, true,
                                 n_points, sample_ws, sample_ws_bytes, stream);
+}
+
+// ---- gradient of a query with respect to its positions: k_query_bwd_pts ----
+int gsasr_splat_query_backward_points(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const float *grad_out,
+                                      const float *points, int n_points, float *g_points, void *sample_ws, size_t sample_ws_bytes,
+                                      void *stream)
+{
+    return query_backward_points(dims, workspace, workspace_bytes, grad_out, points, n_points, g_points, sample_ws, sample_ws_bytes, stream);
+}
+
+int gsasr_step_query_backward_points(const gsasr_dims *dims, void *workspace, size_t workspace_bytes, const float *grad_out,
+                                     const float *points, int n_points, float *g_points, void *sample_ws, size_t sample_ws_bytes,
+                                     void *stream)
+{
+    if (!dims_ok(dims)) return fail(GSASR_ERR_ARG, "bad dims");
+    if (dims->flags & GSASR_FLAG_STRIDE8) return fail(GSASR_ERR_ARG, "GSASR_FLAG_STRIDE8 does not apply to the step entry points");
+    gsasr_dims dn = *dims;      // (the layout the query forward planned with: step_sample_backward)
+    dn.list_cap = -1;
+    dn.flags |= GSASR_FLAG_CONTINUOUS;
+    if (!dims_ok(&dn)) return fail(GSASR_ERR_ARG, "bad dims");
+    bool noted = false;
+    const StepLayout S = make_step_layout(&dn, workspace, &noted);
+    if (!workspace || ((uintptr_t)workspace & 255u) || workspace_bytes < S.total)
+        return fail(GSASR_ERR_WORKSPACE, "workspace null, misaligned or smaller than gsasr_step_workspace_bytes()");
+    if (!noted)
+        return fail(GSASR_ERR_PLAN, "the workspace holds no step query forward of these dims (gsasr_step_query_forward plans with "
+                                    "GSASR_FLAG_CONTINUOUS: run it, or run it again, first)");
+    return query_backward_points(&dn, workspace, S.plan_bytes, grad_out, points, n_points, g_points, sample_ws, sample_ws_bytes, stream);
 }
 
 }  // extern "C"

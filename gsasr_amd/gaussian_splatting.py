@@ -292,9 +292,23 @@ class _FusedBatchSampled(torch.autograd.Function):
                 None, None, None, None)
 
 
+def _query_backward(ctx, grad_output, points_arg):
+    """the two backward passes of a query, each only when its input needs a gradient: the Gaussians' (query backward + prologue
+    backward) and the positions' (`gsasr_step_query_backward_points`: like `query_coords` in shape, dtype and device)"""
+    from . import _cabi
+    gs_parameters, step = ctx.saved_tensors
+    go = grad_output.contiguous()
+    g_par = _cabi.step_query_backward(ctx.plan, ctx.state, gs_parameters, step, go) if ctx.needs_input_grad[0] else None
+    g_pts = None
+    if ctx.needs_input_grad[points_arg]:
+        dtype, device = ctx.points_like
+        g_pts = _cabi.step_query_backward_points(ctx.plan, ctx.state, go).to(device=device, dtype=dtype)
+    return g_par, g_pts
+
+
 class _FusedStepQuery(torch.autograd.Function):
-    """`_FusedStepSampled` at fractional pixel positions: float `(r, c)` points on a continuous plan (`[3,S]`); the gradient
-    goes to `gs_parameters` only."""
+    """`_FusedStepSampled` at fractional pixel positions: float `(r, c)` points on a continuous plan (`[3,S]`).  The gradient goes
+    to `gs_parameters` and, when `points` requires it (`coords_grad=True`), to the positions."""
 
     @staticmethod
     @fp32_boundary_fwd
@@ -302,21 +316,19 @@ class _FusedStepQuery(torch.autograd.Function):
         from . import _cabi
         out, plan, state = _cabi.step_query_forward(gs_parameters, step, H, W, dmax, points, scale_modify, default_step)
         ctx.save_for_backward(gs_parameters, step)
-        ctx.plan, ctx.state = plan, state
+        ctx.plan, ctx.state, ctx.points_like = plan, state, (points.dtype, points.device)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     @fp32_boundary_bwd
     def backward(ctx, grad_output):
-        from . import _cabi
-        gs_parameters, step = ctx.saved_tensors
-        return (_cabi.step_query_backward(ctx.plan, ctx.state, gs_parameters, step, grad_output.contiguous()),
-                None, None, None, None, None, None, None)
+        g_par, g_pts = _query_backward(ctx, grad_output, 5)
+        return g_par, None, None, None, None, g_pts, None, None
 
 
 class _FusedBatchQuery(torch.autograd.Function):
-    """`_FusedBatchSampled` for `query_coords[B,S,2]` (float) -> `[B,3,S]`."""
+    """`_FusedBatchSampled` for `query_coords[B,S,2]` (float) -> `[B,3,S]`; the positions' gradient as in `_FusedStepQuery`."""
 
     @staticmethod
     @fp32_boundary_fwd
@@ -324,17 +336,15 @@ class _FusedBatchQuery(torch.autograd.Function):
         from . import _cabi
         out, plan, state = _cabi.batch_query_forward(gs_parameters, steps, sizes, dmax, points)
         ctx.save_for_backward(gs_parameters, steps)
-        ctx.plan, ctx.state = plan, state
+        ctx.plan, ctx.state, ctx.points_like = plan, state, (points.dtype, points.device)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     @fp32_boundary_bwd
     def backward(ctx, grad_output):
-        from . import _cabi
-        gs_parameters, steps = ctx.saved_tensors
-        return (_cabi.step_query_backward(ctx.plan, ctx.state, gs_parameters, steps, grad_output.contiguous()),
-                None, None, None, None)
+        g_par, g_pts = _query_backward(ctx, grad_output, 4)
+        return g_par, None, None, None, g_pts
 
 
 # Kernel time of the sampled path equals the full render's at about a quarter of the pixels, but the alternative ends
@@ -592,15 +602,16 @@ def generate_2D_gaussian_splatting_step(sr_size, gs_parameters, scale, scale_mod
     return _sample(final_image, sample_coords)
 
 
-def _as_query(query_coords, batched=False):
+def _as_query(query_coords, batched=False, coords_grad=False):
     """`query_coords` as a floating-point `[S,2]` (`batched`: `[B,S,2]`) tensor of (r, c); the argument errors of the query API"""
     qc = query_coords if torch.is_tensor(query_coords) else torch.as_tensor(query_coords)
     if not qc.dtype.is_floating_point:
         raise ValueError("query_coords must be floating point (fractional pixel indices (r, c)); integer pixel indices go to sample_coords")
     if qc.dim() != (3 if batched else 2) or qc.shape[-1] != 2:
         raise ValueError("query_coords must be [B,S,2]" if batched else "query_coords must be [S,2]")
-    if qc.requires_grad:
-        raise ValueError("query_coords.requires_grad: the gradient with respect to the positions is not implemented (detach them)")
+    if qc.requires_grad and not coords_grad:
+        raise ValueError("query_coords.requires_grad: the gradient with respect to the positions is computed only on request "
+                         "(pass coords_grad=True, or detach them)")
     return qc
 
 
@@ -629,15 +640,20 @@ def query_dense(sigmas, xy, col, H, W, dmax, query_coords):
 
 
 def generate_2D_gaussian_splatting_query(sr_size, gs_parameters, scale, scale_modify, query_coords, default_step_size=1.2,
-                                         cuda_rendering=True, mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25):
+                                         cuda_rendering=True, mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25,
+                                         coords_grad=False):
     """The splatted image at fractional pixel positions: `query_coords` float `[S,2]` (tensor or nested list) of (r, c) on the
     `sr_size` grid -> `[3,S]`, differentiable in `gs_parameters`.  The Gaussians are a continuous image; pixel (i, j) of
     `generate_2D_gaussian_splatting_step` is the query (i, j), and (i + 0.5, j) lies halfway to the next row.  Domain:
     0 <= r <= H - 1, 0 <= c <= W - 1, ends included; a point outside it, or with a NaN / infinite component, gives 0 and no
-    gradient.  Repeated points are independent outputs whose gradients add.  Not differentiable in the positions
-    (`query_coords.requires_grad` raises).  CUDA tensors: the HIP query kernels (fused prologue, fp32 under autocast); CPU
-    tensors or `cuda_rendering=False`: the dense torch evaluation `query_dense`, never a fallback for the kernels."""
-    qc = _as_query(query_coords)
+    gradient.  Repeated points are independent outputs whose gradients add.  `coords_grad=True`: differentiable in the
+    positions too -- `query_coords.grad` has `query_coords`' shape, dtype and device (host or float64 positions included); it is
+    the derivative almost everywhere (neither the dmax box test nor the float32 rounding of the position is differentiated), the
+    analytic value on the edge of the domain and (0, 0) for a point outside it.  Each of the two backward passes runs only
+    when its input needs a gradient.  Without the keyword `query_coords.requires_grad` raises.  CUDA tensors: the HIP query
+    kernels (fused prologue, fp32 under autocast); CPU tensors or `cuda_rendering=False`: the dense torch evaluation
+    `query_dense`, never a fallback for the kernels."""
+    qc = _as_query(query_coords, coords_grad=coords_grad)
     if gs_parameters.dtype != torch.float32:
         gs_parameters = gs_parameters.float()
     if gs_parameters.dim() != 2 or gs_parameters.shape[1] != 9:
@@ -649,7 +665,8 @@ def generate_2D_gaussian_splatting_query(sr_size, gs_parameters, scale, scale_mo
     step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=fused)
     if fused:
         if qc.shape[0] == 0:
-            return gs_parameters.new_zeros((3, 0)) + 0.0 * gs_parameters.sum()
+            empty = gs_parameters.new_zeros((3, 0)) + 0.0 * gs_parameters.sum()
+            return empty + (0.0 * qc.sum()).to(empty) if qc.requires_grad else empty      # (a graph to both inputs)
         if step_size.__class__ is _StepSource:
             out = _FusedStepQuery.apply(gs_parameters.contiguous(), None, H, W, dm, qc, step_size.scale_modify, step_size.default_step)
             deferred_asserts.watch(gs_parameters.device)
@@ -827,18 +844,21 @@ def max_canvas_batch(h_max: int) -> int:
 
 def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_modifies, default_step_size=1.2,
                                          mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, sample_coords=None,
-                                         query_coords=None):
+                                         query_coords=None, coords_grad=False):
     """Batched `generate_2D_gaussian_splatting_step`: `gs_parameters` `[B,N,9]`, per-sample
     `sr_sizes[b]`, `scales[b]`, `scale_modifies[b]`; returns `[B,3,Hmax,Wmax]` with every sample zero-padded to
     the largest size -- exactly `torch.stack([F.pad(step(...), ...)])` of the reference's loop.  With
     `sample_coords` `[B,S,2]` (row, column on each sample's own grid; gsasr_model.py:196-197) it returns the
     `[B,3,S]` stack of the per-sample `[3,S]` results instead.  With `query_coords` float `[B,S,2]` (fractional (r, c) on each
-    sample's own grid: `generate_2D_gaussian_splatting_query`) likewise `[B,3,S]`; passing both is a ValueError."""
+    sample's own grid: `generate_2D_gaussian_splatting_query`) likewise `[B,3,S]`; passing both is a ValueError.
+    `coords_grad=True` (with `query_coords` only): differentiable in the positions as well."""
     B = gs_parameters.shape[0]
+    if coords_grad and query_coords is None:
+        raise ValueError("coords_grad=True has a meaning with query_coords only")
     if query_coords is not None:
         if sample_coords is not None:
             raise ValueError("pass sample_coords (integer pixels) or query_coords (fractional positions), not both")
-        query_coords = _as_query(query_coords, batched=True)
+        query_coords = _as_query(query_coords, batched=True, coords_grad=coords_grad)
         if query_coords.shape[0] != B:
             raise ValueError("query_coords must be [B,S,2]")
     if torch.is_tensor(sr_sizes) and sr_sizes.dim() == 2:      # e.g. the [B,2] GPU tensor of gsasr_model.py:147: ONE copy to the host
@@ -857,7 +877,7 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
         parts = [generate_2D_gaussian_splatting_batch(sr_sizes[a: a + cap], gs_parameters[a: a + cap], scales[a: a + cap],
                                                       scale_modifies[a: a + cap], default_step_size, mode, if_dmax, dmax_mode,
                                                       dmax, None if sample_coords is None else sample_coords[a: a + cap],
-                                                      None if query_coords is None else query_coords[a: a + cap])
+                                                      None if query_coords is None else query_coords[a: a + cap], coords_grad)
                  for a in range(0, B, cap)]
         if sample_coords is None and query_coords is None:
             h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
@@ -898,7 +918,7 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
         if query_coords is not None:
             outs.append(generate_2D_gaussian_splatting_query(sr_sizes[b], gs_parameters[b], scales[b], scale_modifies[b], query_coords[b],
                                                              default_step_size=default_step_size, mode=mode, if_dmax=if_dmax,
-                                                             dmax_mode=dmax_mode, dmax=dmax))
+                                                             dmax_mode=dmax_mode, dmax=dmax, coords_grad=coords_grad))
             continue
         o = generate_2D_gaussian_splatting_step(sr_sizes[b], gs_parameters[b], scales[b], scale_modifies[b],
                                                 sample_coords=None if sample_coords is None else sample_coords[b],

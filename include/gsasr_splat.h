@@ -397,7 +397,8 @@ GSASR_API int gsasr_step_sample_backward(const float *gs_parameters, const float
  *             incomplete sum.  The integer sampled points may be evaluated on a continuous plan too (same terms).
  *   out, grad_out, sample_ws (gsasr_sample_workspace_bytes serves both kinds), points = NULL in the backward, flags, errors:
  *             as for the sampled pixels.
- * The backward is the gradient of sum(grad_out * out) with respect to the Gaussians; the positions themselves get none. */
+ * gsasr_*_query_backward is the gradient of sum(grad_out * out) with respect to the Gaussians; the gradient with respect to the
+ * positions themselves is a call of its own, gsasr_*_query_backward_points below. */
 GSASR_API int gsasr_splat_query_forward(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes, const float *points,
                               int n_points, float *out, void *sample_ws, size_t sample_ws_bytes, void *stream);
 GSASR_API int gsasr_splat_query_backward(const float *sigmas, const float *coords, const float *colors, const float *grad_out,
@@ -414,6 +415,32 @@ GSASR_API int gsasr_step_query_forward_sm(const float *gs_parameters, const floa
 GSASR_API int gsasr_step_query_backward(const float *gs_parameters, const float *step_size, const float *grad_out,
                               float *g_parameters, const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
                               const float *points, int n_points, void *sample_ws, size_t sample_ws_bytes, void *stream);
+
+/* Gradient of a query with respect to its POSITIONS: g_points[s] = d sum(grad_out * out) / d (r_s, c_s).  With, for point s at
+ * (px, py) and Gaussian j, dx = px - x_j, dy = py - y_j, u = dx / sigma_x, v = dy / sigma_y, B = v - rho u,
+ * t_sj = exp(-(u^2 + B^2 / (1 - rho^2)) / 2) (0 outside the dmax box, bounded op) and w_sj = sum_k grad_out[k, s] * colour[j, k]:
+ *       g_px[s] = sum_j w_sj t_sj * -(u - rho B / (1 - rho^2)) / sigma_x        g_py[s] = sum_j w_sj t_sj * -B / ((1 - rho^2) sigma_y)
+ *       g_points[s] = (g_py[s] * 2 / (h - 1), g_px[s] * 2 / (w - 1))            (d/dr, d/dc; h, w: the sample's own grid)
+ * The sum runs over the terms the query forward sums (same cutoff rules).  It is the derivative almost everywhere: neither
+ * the box test nor the float rounding of px, py is differentiated; a point on the edge of the closed domain gets the analytic
+ * value (no projection); a point outside the domain or with a NaN / infinite component gets (0, 0); dead and non-finite
+ * Gaussians contribute nothing; repeated points are independent rows.  One point-stationary kernel, no global atomics.
+ *   workspace a GSASR_FLAG_CONTINUOUS plan (else GSASR_ERR_PLAN).  Only the forward's records are read: a plan made with
+ *             GSASR_FLAG_FORWARD_ONLY is accepted, so positions can be fitted against frozen Gaussians on an inference plan.
+ *   grad_out  device float32 [3, n_points] ([B, 3, n_points]), as for gsasr_splat_query_backward.
+ *   points    as for the forward, or NULL: sample_ws still holds what the forward (or a backward) sorted.
+ *   g_points  device float32 [n_points, 2] ([B, n_points, 2]); every row is WRITTEN, whatever GSASR_FLAG_OVERWRITE_GRADS says.
+ *   sample_ws gsasr_sample_workspace_bytes(dims, n_points) bytes, 256-byte aligned (else GSASR_ERR_WORKSPACE).  The call
+ *             gathers grad_out into it itself: it does not matter whether a Gaussian backward ran before.
+ * n_points == 0: GSASR_OK, nothing touched; n_points < 0 or a null grad_out / g_points with n_points > 0: GSASR_ERR_ARG;
+ * dims.s == 0: zeros.  The step form takes the dims and the workspace of gsasr_step_query_forward[_sm] (it sets list_cap = -1
+ * and GSASR_FLAG_CONTINUOUS itself, as gsasr_step_query_backward does) and needs no gs_parameters. */
+GSASR_API int gsasr_splat_query_backward_points(const gsasr_dims *dims, const void *workspace, size_t workspace_bytes,
+                                      const float *grad_out, const float *points, int n_points, float *g_points,
+                                      void *sample_ws, size_t sample_ws_bytes, void *stream);
+GSASR_API int gsasr_step_query_backward_points(const gsasr_dims *dims, void *workspace, size_t workspace_bytes,
+                                     const float *grad_out, const float *points, int n_points, float *g_points,
+                                     void *sample_ws, size_t sample_ws_bytes, void *stream);
 
 /* Reference-shaped launchers: the argument lists of `_gs_render` / `_gs_render_backward` in utils/gs_cuda/gs.h:4-24 and
  * utils/gs_cuda_dmax/gs.h:4-26 (+ the stream, + a status instead of void).  The reference's launchers take no workspace,

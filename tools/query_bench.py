@@ -11,7 +11,10 @@ on (a) 1024^2 x4 at 65 536 Gaussians with 65 536 points and (b) the config-5 bat
 6.25% of its pixels as points.  int-cont and float-cont run the same kernels on the same sorted records everywhere but in the
 sort, so on every other stage their medians may differ by no more than int-cont's own spread (`float_within_int_spread`);
 int-cont against int-plain is reported beside the ratio the padding predicts, the mean of (w + 2)(h + 2) / (w h) over the
-windows (restated on the host from the plan's own cutoff).  The sort is timed as the difference of the backward with and
+windows (restated on the host from the plan's own cutoff).  float-cont has one more stage, "position backward": the gradient
+with respect to the positions (gsasr_splat_query_backward_points with points = NULL: the gather of grad_out + k_query_bwd_pts),
+which must cost less than four sort + forward of the same run -- what central differences in r and c cost
+(`position_backward_below_four_forwards`).  The sort is timed as the difference of the backward with and
 without a re-sort of the points.  hipEvent timing around batches of calls, the variants alternated round by round in one
 process, at least `--seconds` of work per variant and stage; the figure is the median of the rounds, the spread their range.
 
@@ -126,6 +129,11 @@ def main():
 
             fns[v] = {"plan": planfn, "sort+forward": f_fwd, "backward": f_bwd, "sort+backward": lambda f=f_bwd: f(resort=True)}
             f_bwd()
+            if v == "float-cont":
+                def posbwd(plan=plan, state=state):
+                    return _cabi.query_backward_points(plan, state, gout)
+                gpos = posbwd()
+                assert bool(torch.isfinite(gpos).all()) and float(gpos.abs().max()) > 0
             outs[v], grads[v], plans[v] = out, gr, plan
         # the same values and gradients, three ways
         row = {"H": H, "W": W, "batch": B, "gaussians": int(tensors[0].shape[0]), "points": int(S * B), "same_values": {}}
@@ -172,12 +180,16 @@ def main():
         for _ in range(3):
             refine()
         counts["refine"] = max(3, int(args.seconds * 1000.0 / batch_ms(refine, 3) / args.rounds) + 1)
+        for _ in range(3):
+            posbwd()
+        counts["posbwd"] = max(5, int(args.seconds * 1000.0 / batch_ms(posbwd, 5) / args.rounds) + 1)
         times = {k: [] for k in counts}
         for _ in range(args.rounds):        # alternated: int-plain int-cont float-cont int-plain ...
             for st in stage_names:
                 for v in VARIANTS:
                     times[v, st].append(batch_ms(fns[v][st], counts[v, st]))
             times["refine"].append(batch_ms(refine, counts["refine"]))
+            times["posbwd"].append(batch_ms(posbwd, counts["posbwd"]))
 
         def cell(t, n):
             return {"ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t), "calls_per_round": n, "total_s": sum(t) * n / 1000.0}
@@ -188,6 +200,10 @@ def main():
             row[v]["sort"] = cell(sort, counts[v, "sort+backward"])
             row[v]["forward"] = cell([x - y for x, y in zip(times[v, "sort+forward"], sort)], counts[v, "sort+forward"])
         row["refine-m2"] = {"plan+forward+gather": cell(times["refine"], counts["refine"])}
+        row["float-cont"]["position backward"] = cell(times["posbwd"], counts["posbwd"])
+        row["position_backward_over_sort+forward"] = row["float-cont"]["position backward"]["ms"] / row["float-cont"]["sort+forward"]["ms"]
+        row["position_backward_below_four_forwards"] = row["position_backward_over_sort+forward"] < 4.0
+        ok_all = ok_all and row["position_backward_below_four_forwards"]
         row["float_within_int_spread"] = {}
         for st in GATED:
             ii, fl = row["int-cont"][st], row["float-cont"][st]
@@ -201,6 +217,9 @@ def main():
         print(f"{name} | refine-m2 plan+forward+gather ms | {r['ms']:.4f} [{r['min_ms']:.4f}, {r['max_ms']:.4f}]", flush=True)
         print(f"{name} | expected padding ratio {ratio:.3f} (mean window {wm:.1f} x {hm:.1f}); measured int-cont / int-plain: {row['padding_measured_ratio']}", flush=True)
         print(f"{name} | float-cont within int-cont's spread: {row['float_within_int_spread']}", flush=True)
+        pb = row["float-cont"]["position backward"]
+        print(f"{name} | float-cont position backward ms | {pb['ms']:.4f} [{pb['min_ms']:.4f}, {pb['max_ms']:.4f}] = "
+              f"{row['position_backward_over_sort+forward']:.2f} x sort+forward (must be < 4)", flush=True)
         del fns, outs, grads, plans, tensors, ws2, img2
         torch.cuda.empty_cache()
     report["conditions_hold"] = ok_all
