@@ -263,7 +263,8 @@ class Plan:
     #                                       must set this to None: the pool's "counters clean" bookkeeping no longer holds
     parity: int = 0
     view: Optional[View] = None           # the window this plan renders (the view of its dims, `make_view`), None for a whole image /
-    #                                       band / canvas: every call on the plan passes it on
+    #                                       band / canvas: every call on the plan passes it on.  A canvas with one window per
+    #                                       sample: the ctypes array of its B views
 
     def __post_init__(self):
         if self.view is None:
@@ -289,14 +290,29 @@ def make_dims(s: int, h: int, w: int, dmax: Optional[float], rows: Optional[Tupl
 # ---- a window of the grid (include/gsasr_splat.h: gsasr_view) ------------------------------------------------
 def make_view(d: Dims, view) -> Dims:
     """attach `view` = (full_h, full_w, y0, x0) to the dims of the window (`make_dims(s, h, w, ...)` with the WINDOW's h, w):
-    the calls below then go to the `_view` entry points"""
+    the calls below then go to the `_view` entry points.  Dims of a batched canvas (`make_batch_dims`, whose sizes are then
+    the windows'): `view` = one such tuple per sample"""
     if view is not None:
-        d._view = View(*[int(v) for v in view])
+        if d.batch > 1:
+            if len(view) != d.batch:
+                raise RuntimeError("views must hold one (full_h, full_w, y0, x0) per sample")
+            d._view = (View * d.batch)(*[View(*[int(v) for v in one]) for one in view])
+        else:
+            d._view = View(*[int(v) for v in view])
     return d
 
 
 def _view_of(d: Dims) -> Optional[View]:
     return d.__dict__.get("_view")
+
+
+def _vref(v):
+    """a view as the `const gsasr_view *` argument: the struct by reference, a canvas' array of views as it is"""
+    return v if isinstance(v, ctypes.Array) else ctypes.byref(v)
+
+
+def _view_key(v) -> tuple:
+    return tuple(x for one in (v if isinstance(v, ctypes.Array) else (v,)) for x in (one.full_h, one.full_w, one.y0, one.x0))
 
 
 def _vcall(name: str, d: Dims):
@@ -305,7 +321,7 @@ def _vcall(name: str, d: Dims):
     if v is None:
         return getattr(lib(), name), name, (ctypes.byref(d),)
     name += "_view"
-    return getattr(lib(), name), name, (ctypes.byref(d), ctypes.byref(v))
+    return getattr(lib(), name), name, (ctypes.byref(d), _vref(v))
 
 
 # ---- batched canvas: its dims -------------------------------------------------------
@@ -370,13 +386,30 @@ def _image_shape(bytes_fn: str, s: int, h: int, w: int, dmax, flags: int, rows=N
     return _SHAPES.get(key) or _new_shape(key, dmax, lambda f: make_view(make_dims(s, h, w, dmax, rows, cutoff, int(flags) | f, list_cap), view), bytes_fn)
 
 
-def _canvas_shape(n_per: int, sizes, dmax, flags: int):
-    """the canvas of `sizes` = [(h_b, w_b)] with `n_per` Gaussians per sample, sized by gsasr_step_workspace_bytes"""
+def _views(views, batch: int):
+    """`views` = [(full_h, full_w, y0, x0)] * B of a canvas, as a tuple of int tuples"""
+    views = tuple(tuple(int(v) for v in one) for one in views)
+    if len(views) != batch or any(len(one) != 4 for one in views):
+        raise RuntimeError("views must hold one (full_h, full_w, y0, x0) per sample")
+    return views
+
+
+def _canvas_shape(n_per: int, sizes, dmax, flags: int, views=None, bytes_fn: str = _STEP_BYTES, cutoff: float = 0.0, list_cap: int = 0):
+    """the canvas of `sizes` = [(h_b, w_b)] with `n_per` Gaussians per sample, sized by gsasr_step_workspace_bytes.
+    `views` = [(full_h, full_w, y0, x0)]: sample b is the h_b x w_b window at (y0, x0) of its own full grid (`make_view`)"""
     sizes = tuple(map(tuple, sizes))
     key = (n_per, sizes, dmax, flags)
-    return _SHAPES.get(key) or _new_shape(
-        key, dmax, lambda f: make_batch_dims(n_per, sizes, max(w for _, w in sizes), max(h for h, _ in sizes), dmax, flags=int(flags) | f),
-        _STEP_BYTES)
+    if views is not None:
+        views = _views(views, len(sizes))
+        key += (views,)
+    if bytes_fn != _STEP_BYTES or cutoff != 0.0 or list_cap != 0:
+        key += (bytes_fn, cutoff, list_cap)
+
+    def make(f):
+        d = make_batch_dims(n_per, sizes, max(w for _, w in sizes), max(h for h, _ in sizes), dmax, cutoff, flags=int(flags) | f)
+        d.list_cap = int(list_cap)
+        return make_view(d, views)
+    return _SHAPES.get(key) or _new_shape(key, dmax, make, bytes_fn)
 
 
 _LAYOUT_FLAGS = FLAG_FORWARD_ONLY | FLAG_BWD_TILE | FLAG_BWD_GAUSSIAN | FLAG_BWD_ATOMIC | FLAG_BWD_HOME | FLAG_CHW_GRAD | FLAG_STRIDE8
@@ -388,7 +421,7 @@ def _pool_key(d: Dims, nbytes: int, dev, stream: int):
     layout depends on, not just the byte count (two small shapes easily round to the same size)."""
     key = (dev.index, stream, nbytes, d.s, d.h, d.w, d.batch, d.slot, d.flags & _LAYOUT_FLAGS)
     v = d.__dict__.get("_view")     # (a window's layout also follows the grid it is cut from: the kernel-choice rules read it)
-    return key if v is None else key + (v.full_h, v.full_w, v.y0, v.x0)
+    return key if v is None else key + _view_key(v)
 
 
 def _acquire(shape, dev, stream: int):
@@ -406,24 +439,33 @@ def _acquire(shape, dev, stream: int):
 
 def plan(sigmas: torch.Tensor, coords: torch.Tensor, colors: torch.Tensor, h: int, w: int,
          dmax: Optional[float], rows: Optional[Tuple[int, int]] = None, cutoff: float = 0.0,
-         flags: int = 0, list_cap: int = 0, view=None) -> Plan:
+         flags: int = 0, list_cap: int = 0, view=None, sizes=None, views=None) -> Plan:
     """`view` = (full_h, full_w, y0, x0): plan the h x w window of that grid whose first pixel is its (y0, x0); `forward`,
-    `forward_u8` and `backward` on the plan then render / differentiate the window only."""
+    `forward_u8` and `backward` on the plan then render / differentiate the window only.
+    `sizes` = [(h_b, w_b)] * B: a batched canvas of kernel-frame Gaussians in sample-major order (`h`, `w`, `rows` are not
+    read: `make_batch_dims`); with `views` = [(full_h, full_w, y0, x0)] * B sample b is that window of its own grid."""
     ps = _ptr3(sigmas, "sigmas", 3)
     pc = _ptr3(coords, "coords", 2)
     pk = _ptr3(colors, "colors", 3)
     s = sigmas.shape[0]
     if coords.shape[0] != s or colors.shape[0] != s:
         raise RuntimeError("sigmas, coords, colors disagree on the number of Gaussians")
-    shape = _image_shape(_SPLAT_BYTES, s, int(h), int(w), dmax, flags, rows, cutoff, list_cap, view)
+    if sizes is not None:
+        if view is not None or s % len(sizes) != 0:
+            raise RuntimeError("a canvas takes `views`, one per sample, and the same number of Gaussians for every sample")
+        shape = _canvas_shape(s // len(sizes), sizes, dmax, flags, views, _SPLAT_BYTES, cutoff, list_cap)
+    elif views is not None:
+        raise RuntimeError("`views` go with the `sizes` of a canvas (one image: `view`)")
+    else:
+        shape = _image_shape(_SPLAT_BYTES, s, int(h), int(w), dmax, flags, rows, cutoff, list_cap, view)
     dev = sigmas.device
     with _on(dev):
         stream = _stream(dev)
         d, ws, pool_key, parity = _acquire(shape, dev, stream)
-        if view is None:
+        if _view_of(d) is None:
             check(lib().gsasr_splat_plan(ps, pc, pk, ctypes.byref(d), ws.data_ptr(), shape[1], stream), "gsasr_splat_plan")
         else:
-            check(lib().gsasr_splat_plan_view(ps, pc, pk, ctypes.byref(d), ctypes.byref(_view_of(d)), ws.data_ptr(), shape[1], stream),
+            check(lib().gsasr_splat_plan_view(ps, pc, pk, ctypes.byref(d), _vref(_view_of(d)), ws.data_ptr(), shape[1], stream),
                   "gsasr_splat_plan_view")
     return Plan(d, ws, dev, pool_key, parity)
 
@@ -468,7 +510,7 @@ def forward(p: Plan, img: torch.Tensor, overwrite: bool = False, chw: bool = Fal
             check(lib().gsasr_splat_forward(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), pi,
                                             _stream(p.device)), "gsasr_splat_forward")
         else:
-            check(lib().gsasr_splat_forward_view(ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(), p.workspace.numel(), pi,
+            check(lib().gsasr_splat_forward_view(ctypes.byref(d), _vref(p.view), p.workspace.data_ptr(), p.workspace.numel(), pi,
                                                  _stream(p.device)), "gsasr_splat_forward_view")
     return img
 
@@ -519,7 +561,7 @@ def forward_u8(p: Plan, crop=None, bgr: bool = False, out: Optional[torch.Tensor
             check(lib().gsasr_splat_forward_u8(ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), out.data_ptr(), rows, cols,
                                                pitch, U8_SWAP_RB if bgr else 0, _stream(p.device)), "gsasr_splat_forward_u8")
         else:
-            check(lib().gsasr_splat_forward_u8_view(ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(), p.workspace.numel(),
+            check(lib().gsasr_splat_forward_u8_view(ctypes.byref(d), _vref(p.view), p.workspace.data_ptr(), p.workspace.numel(),
                                                     out.data_ptr(), rows, cols, pitch, U8_SWAP_RB if bgr else 0, _stream(p.device)),
                   "gsasr_splat_forward_u8_view")
     return out
@@ -546,7 +588,7 @@ def _splat_backward(p: Plan, ptrs, extra_flags: int) -> None:
             check(lib().gsasr_splat_backward(*ptrs, ctypes.byref(d), p.workspace.data_ptr(), p.workspace.numel(), _stream(p.device)),
                   "gsasr_splat_backward")
         else:
-            check(lib().gsasr_splat_backward_view(*ptrs, ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(),
+            check(lib().gsasr_splat_backward_view(*ptrs, ctypes.byref(d), _vref(p.view), p.workspace.data_ptr(),
                                                   p.workspace.numel(), _stream(p.device)), "gsasr_splat_backward_view")
 
 
@@ -773,7 +815,7 @@ def _step_call(names, pp: int, src, d: Dims, ws: torch.Tensor, nbytes: int, *tai
         check(getattr(lib(), name)(pp, *src, ctypes.byref(d), ws.data_ptr(), nbytes, *tail), name)
     else:
         name += "_view"
-        check(getattr(lib(), name)(pp, *src, ctypes.byref(d), ctypes.byref(v), ws.data_ptr(), nbytes, *tail), name)
+        check(getattr(lib(), name)(pp, *src, ctypes.byref(d), _vref(v), ws.data_ptr(), nbytes, *tail), name)
 
 
 def _step_planar(shape, pp: int, src, dev):
@@ -834,29 +876,32 @@ def step_backward(p: Plan, gs_parameters: torch.Tensor, step: Optional[torch.Ten
             check(lib().gsasr_step_backward(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), p.workspace.data_ptr(),
                                             p.workspace.numel(), _stream(p.device)), "gsasr_step_backward")
         else:
-            check(lib().gsasr_step_backward_view(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), ctypes.byref(p.view), p.workspace.data_ptr(),
+            check(lib().gsasr_step_backward_view(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), _vref(p.view), p.workspace.data_ptr(),
                                                  p.workspace.numel(), _stream(p.device)), "gsasr_step_backward_view")
     return gp
 
 
 # ---- batched canvas: the step entry points on `make_batch_dims`' dims ----------------------------------------
 def batch_forward(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], sizes, dmax: Optional[float], extra_flags: int = 0,
-                  scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+                  scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2, views=None):
     """prologue + plan + forward of a whole batch in ONE set of launches.
     `gs_parameters` [B,N,9], `steps` [B] (device), `sizes` [(h_b, w_b)] -> planar images `[B,3,slot,w_max]`
-    (sample b in `[:, :, :h_b, :w_b]`, zero elsewhere) and the plan for `batch_backward`."""
+    (sample b in `[:, :, :h_b, :w_b]`, zero elsewhere) and the plan for `batch_backward`.
+    `views` = [(full_h, full_w, y0, x0)] * B: sample b is the h_b x w_b window at (y0, x0) of its own full_h x full_w grid --
+    step sizes and the prologue are the full grid's (gsasr_view)."""
     pp, src = _step_args(gs_parameters, steps, scale_modify, default_step_size, sizes)
-    shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags))
+    shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags), views)
     return _step_planar(shape, pp, src, gs_parameters.device)
 
 
 def batch_forward_u8(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor], sizes, dmax: Optional[float], crop=None,
                      bgr: bool = False, out: Optional[torch.Tensor] = None, extra_flags: int = 0,
-                     scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2):
+                     scale_modify: Optional[torch.Tensor] = None, default_step_size: float = 1.2, views=None):
     """`batch_forward` ending in the 8-bit store: `gs_parameters` [B,N,9] -> uint8 `[B, rows, cols, 3]` (`crop`, default the
-    largest sample's size; sample b in `[b, :h_b, :w_b]`, zero elsewhere) and the plan (FLAG_FORWARD_ONLY)."""
+    largest sample's size; sample b in `[b, :h_b, :w_b]`, zero elsewhere) and the plan (FLAG_FORWARD_ONLY).  `views`: as for
+    `batch_forward`; `crop` is then of the windows."""
     pp, src = _step_args(gs_parameters, steps, scale_modify, default_step_size, sizes)
-    shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_FORWARD_ONLY | int(extra_flags))
+    shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_FORWARD_ONLY | int(extra_flags), views)
     return _step_u8(shape, pp, src, crop, bgr, out, gs_parameters.device)
 
 
@@ -881,8 +926,12 @@ def batch_backward(p: Plan, gs_parameters: torch.Tensor, steps: Optional[torch.T
         pg = _chk(grad, "grads", (p.dims.batch, p.dims.slot, p.dims.w, 3))
     with _on(p.device):
         gp = torch.empty_like(gs_parameters)
-        check(lib().gsasr_step_backward(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), p.workspace.data_ptr(),
-                                        p.workspace.numel(), _stream(p.device)), "gsasr_step_backward")
+        if p.view is None:
+            check(lib().gsasr_step_backward(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), p.workspace.data_ptr(),
+                                            p.workspace.numel(), _stream(p.device)), "gsasr_step_backward")
+        else:
+            check(lib().gsasr_step_backward_view(pp, ps, pg, gp.data_ptr(), ctypes.byref(d), _vref(p.view), p.workspace.data_ptr(),
+                                                 p.workspace.numel(), _stream(p.device)), "gsasr_step_backward_view")
     return gp
 
 

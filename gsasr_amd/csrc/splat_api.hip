@@ -114,10 +114,10 @@ static unsigned long long note_shape(const gsasr_dims *d, const gsasr_view *vw)
     unsigned long long x = (unsigned long long)(unsigned)d->s * 0x9E3779B97F4A7C15ull;
     x ^= ((unsigned long long)(unsigned)d->h << 32 | (unsigned)d->w) * 0xC2B2AE3D27D4EB4Full;
     x ^= (unsigned long long)(unsigned)batch_of(d) * 0x27D4EB2F165667C5ull;
-    if (vw) {
-        x ^= (((unsigned long long)(unsigned)vw->full_h << 32 | (unsigned)vw->full_w) + 0x165667B19E3779F9ull) * 0x9E3779B97F4A7C15ull;
+    for (int b = 0; vw && b < batch_of(d); ++b) {   // (every sample's view of a batched canvas, in order)
+        x ^= (((unsigned long long)(unsigned)vw[b].full_h << 32 | (unsigned)vw[b].full_w) + 0x165667B19E3779F9ull) * 0x9E3779B97F4A7C15ull;
         x = (x ^ x >> 29) * 0xBF58476D1CE4E5B9ull;
-        x ^= ((unsigned long long)(unsigned)vw->y0 << 32 | (unsigned)vw->x0) * 0xC2B2AE3D27D4EB4Full + 0x94D049BB133111EBull;
+        x ^= ((unsigned long long)(unsigned)vw[b].y0 << 32 | (unsigned)vw[b].x0) * 0xC2B2AE3D27D4EB4Full + 0x94D049BB133111EBull;
         x = (x ^ x >> 32) * 0x94D049BB133111EBull;
     }
     return (x >> 40) & 0xffffull;

@@ -683,7 +683,8 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
                 const long over = n0 % 512;
                 if (n0 > 512 && over != 0 && over <= 384) variant = 3;      // (up to one set: nothing to even out)
             }
-            return launch_bwd_home(P, V, grad_img, g_sigmas, g_coords, g_colors, variant, st, vw);
+            const ViewArg VW = view_arg(vw, dims->batch, (const char *)workspace + L.off_vtab);
+            return launch_bwd_home(P, V, grad_img, g_sigmas, g_coords, g_colors, variant, st, vw ? &VW : nullptr);
         }
         // Eight Gaussians per wave (k_render_bwd8): built in round 5, parity-green, and SLOWER than one wave per Gaussian --
         // config 2 39.4 vs 30.7 us, 16 Gaussians per LR pixel 475 vs 401, the config-5 canvas 271 vs 235

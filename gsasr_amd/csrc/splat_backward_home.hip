@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
         // (GSASR_SPLAT_GRAD_TAU: a gradient sums over its own pixels only)
         float kw = __uint_as_float(V.hdr[3]);
         if (P.kb_max > 0.f && kw > P.kb_max) kw = P.kb_max;
-        const Scale sc = view_scale<VIEW>(VW, g);
+        const Scale sc = view_scale<VIEW>(sample_view<VIEW>(VW, smp), g);
         const float hx = 0.5f * (float)(sc.gw - 1), hy = 0.5f * (float)(sc.gh - 1);
         __syncthreads();
 
@@ -481,9 +481,9 @@ namespace gsasr_detail {
 // their workgroups only take part in the tails).  variant: 0 = 32 x 16-px tiles, eight waves (dense plans); 1 = 32 x 32, four
 // waves; 2 = 64 x 32, four waves (sparse plans).
 int launch_bwd_home(const Params &P, const PlanView &V, const float *grad_img, float *g_sigmas, float *g_coords, float *g_colors,
-                    int variant, hipStream_t st, const gsasr_view *vw)
+                    int variant, hipStream_t st, const ViewArg *vw)
 {
-    const ViewArg VW = view_arg(vw);
+    const ViewArg VW = vw ? *vw : view_arg(nullptr);
     const int cps = P.batch > 1 ? P.slot / CELL : P.ncy;
 #define GSASR_HOME_V(TCX, TCY, W, ISVIEW) do { \
         if (P.bounded) hipLaunchKernelGGL((k_render_bwd_home<true, TCX, TCY, W, ISVIEW>), grid, block, 0, st, P, V, grad_img, g_sigmas, g_coords, g_colors, tiles_x, tps, cps, VW); \

@@ -128,11 +128,19 @@ struct Params {
 // that turn a Gaussian's normalised coordinate into a pixel position (k_classify, k_bin, the home-tile backward; instantiated
 // with VIEW = true) map it with the full grid's scale, minus the window's origin (view_scale).  Their LAST kernel argument, so
 // that Params and every argument offset of the other kernels stay what they were; all zero without a view.
+// Batched canvas with one window per sample: `tab` points at the plan's table of {full_h, full_w, y0, x0}, one entry per sample
+// (Layout::off_vtab, written by k_batch_views), and the kernels take sample b's entry (sample_view); null for a single image.
 struct ViewArg {
     int fh, fw;              // the full grid
     int y0, x0;              // the window's first row / column on it
+    const int4 *tab;         // batched canvas: the per-sample views in the workspace
 };
-inline ViewArg view_arg(const gsasr_view *vw) { return vw ? ViewArg{vw->full_h, vw->full_w, vw->y0, vw->x0} : ViewArg{0, 0, 0, 0}; }
+inline ViewArg view_arg(const gsasr_view *vw, int batch = 1, const void *tab = nullptr)
+{
+    if (!vw) return ViewArg{0, 0, 0, 0, nullptr};
+    if (batch > 1) return ViewArg{0, 0, 0, 0, (const int4 *)tab};
+    return ViewArg{vw->full_h, vw->full_w, vw->y0, vw->x0, nullptr};
+}
 
 // One sample of a batched canvas: its own pixel-grid size, its first canvas row and its px-table offset.
 // A single image is the sample {h, w, 0, 0}.
@@ -185,8 +193,19 @@ __device__ __forceinline__ Geo sample_geo(const Params &P, const PlanView &V, in
     return Geo{g.x, g.y, g.z, g.w};
 }
 
+// the view of sample b: the kernel argument itself, or -- batched canvas -- the sample's entry of the table
+template <bool VIEW>
+__device__ __forceinline__ ViewArg sample_view(const ViewArg &vw, int b)
+{
+    if (VIEW && vw.tab) {
+        const int4 t = vw.tab[b];
+        return ViewArg{t.x, t.y, t.z, t.w, nullptr};
+    }
+    return vw;
+}
+
 // Where normalised coordinates land in pixels: pixel = (coordinate + 1) * 0.5 * (gw - 1) - ox (rows: gh, oy).  A sample's own
-// grid and no offset, or -- VIEW, single images only -- the full grid a window is cut from and the window's origin.
+// grid and no offset, or -- VIEW -- the full grid a window is cut from and the window's origin (vw: the SAMPLE's view, sample_view).
 struct Scale {
     int gh, gw, oy, ox;
 };
@@ -200,6 +219,7 @@ __device__ __forceinline__ Scale view_scale(const ViewArg &vw, const Geo &g)
 struct Layout {
     size_t off_geo, off_hdr, off_count, off_start, off_px, off_py, off_key, off_rank, off_bmax, off_stot, off_rec, off_fin, off_sums, off_done, off_bbox, off_win, off_part, off_qspan;
     size_t off_tlc, off_tle;     // tile lists (at the END of the workspace: every other offset is the same with and without them)
+    size_t off_vtab;             // batched canvas with views: int4[GSASR_MAX_BATCH] behind everything else (no bytes without views)
     int tl_hlog, tl_cap, tl_ntx, tl_ntiles;
     bool tl_ok;                  // the lists may be READ: the plan's note says it wrote them (plan_layout)
     int part_k;
@@ -236,22 +256,36 @@ inline bool dims_ok(const gsasr_dims *d)
 
 inline int batch_of(const gsasr_dims *d) { return d->batch > 1 ? d->batch : 1; }
 
-constexpr const char *VIEW_ERR = "bad view (a window is one whole image: row0 = 0, row1 = h, batch = 0; 2<=full_h,full_w<=32767, 0<=y0<=full_h-h, 0<=x0<=full_w-w)";
+constexpr const char *VIEW_ERR = "bad view (a window is one whole image or one sample of a whole canvas: row0 = 0, row1 = h; per window 2<=full_h,full_w<=32767, 0<=y0<=full_h-h, 0<=x0<=full_w-w)";
 constexpr const char *CONTINUOUS_ERR = "a plan made with GSASR_FLAG_CONTINUOUS serves the query and sampled-pixel entry points only (its windows are padded: no row spans, tile lists or slots for the image kernels)";
-// dims + view of a `_view` entry point: one whole image of the window's size, cut from a grid within the whole-image limits
+// size of the window of sample b: the image itself, or -- batched canvas -- the sample's own size
+inline int window_h(const gsasr_dims *d, int b) { return d->batch > 1 ? d->sample_hw[2 * b] : d->h; }
+inline int window_w(const gsasr_dims *d, int b) { return d->batch > 1 ? d->sample_hw[2 * b + 1] : d->w; }
+
+// dims + view(s) of a `_view` entry point: one whole image of the window's size, cut from a grid within the whole-image limits;
+// a batched canvas: v[b] is the view of sample b, whose window is sample_hw[b]
 inline bool view_ok(const gsasr_dims *d, const gsasr_view *v)
 {
     if (!dims_ok(d)) return false;
     if (!v) return true;
     if (d->flags & GSASR_FLAG_CONTINUOUS) return false;      // (queries are not combinable with a view)
-    return d->batch <= 1 && d->row0 == 0 && d->row1 == d->h && v->full_h >= 2 && v->full_w >= 2 && v->full_h <= 32767 &&
-           v->full_w <= 32767 && v->y0 >= 0 && v->x0 >= 0 && v->y0 <= v->full_h - d->h && v->x0 <= v->full_w - d->w;
+    if (d->row0 != 0 || d->row1 != d->h) return false;
+    for (int b = 0; b < batch_of(d); ++b)
+        if (!(v[b].full_h >= 2 && v[b].full_w >= 2 && v[b].full_h <= 32767 && v[b].full_w <= 32767 && v[b].y0 >= 0 && v[b].x0 >= 0 &&
+              v[b].y0 <= v[b].full_h - window_h(d, b) && v[b].x0 <= v[b].full_w - window_w(d, b)))
+            return false;
+    return true;
 }
 
-// a view that is the whole grid is no view: such a call takes the whole-image path, bit for bit
+// a view that is the whole grid is no view: such a call takes the whole-image path, bit for bit (batched canvas: when every
+// sample's view is its whole grid)
 inline const gsasr_view *norm_view(const gsasr_dims *d, const gsasr_view *v)
 {
-    return (d && v && v->y0 == 0 && v->x0 == 0 && v->full_h == d->h && v->full_w == d->w) ? nullptr : v;
+    if (!d || !v) return v;
+    if (d->batch > 1 && !d->sample_hw) return v;      // (bad dims: the entry point refuses them)
+    for (int b = 0; b < batch_of(d); ++b)
+        if (!(v[b].y0 == 0 && v[b].x0 == 0 && v[b].full_h == window_h(d, b) && v[b].full_w == window_w(d, b))) return v;
+    return nullptr;
 }
 
 // The dims the kernel-choice rules below are evaluated with (fwd_wants_wide, bwd_wants_tile / _home, bwd_part_k, bt_tall,
@@ -268,7 +302,11 @@ inline gsasr_dims policy_dims(const gsasr_dims *d, const gsasr_view *v)
         p.cutoff = NAN;
     }
     if (v) {
-        const double live = (double)d->s * ((double)d->h * (double)d->w) / ((double)v->full_h * (double)v->full_w);
+        // (batched canvas: the canvas is judged as the image it is, with the sum of what its samples' windows can expect)
+        double live = 0.0;
+        const int B = batch_of(d);
+        for (int b = 0; b < B; ++b)
+            live += (double)(d->s / B) * ((double)window_h(d, b) * (double)window_w(d, b)) / ((double)v[b].full_h * (double)v[b].full_w);
         p.s = d->s > 0 ? (int)std::fmax(1.0, std::floor(live)) : 0;
         p.cutoff = NAN;
     }
@@ -546,6 +584,7 @@ inline Layout make_layout(const gsasr_dims *d, int part_k = -1, int tl_hlog = -1
     L.off_tlc = o;    o += align_up((size_t)L.tl_ntiles * TL_STRIDE * 4, 256);
     L.off_tle = o;    o += align_up((size_t)L.tl_ntiles * (size_t)L.tl_cap * 8, 256);
     L.tl_ok = L.tl_hlog != 0;
+    L.off_vtab = o;   o += (vw && d->batch > 1) ? (size_t)GSASR_MAX_BATCH * 16 : 0;
     L.total = o;
     return L;
 }
@@ -616,8 +655,20 @@ inline Params make_params(const gsasr_dims *d, const Layout &L, const gsasr_view
 {
     Params P;
     const gsasr_dims pd = policy_dims(d, vw);
-    // (sizes that set a SCALE -- the dmax box in pixels, the cells it covers -- are the full grid's under a view)
-    const double scale_w = vw ? (double)vw->full_w : (double)d->w, scale_h = vw ? (double)vw->full_h : (double)d->h;
+    // (sizes that set a SCALE -- the dmax box in pixels, the cells it covers -- are the full grid's under a view; with one view
+    // per sample of a batched canvas the LARGEST grid counts the cells -- an upper bound of every sample's -- and the smallest
+    // one sets cap_px)
+    const bool bviews = vw && d->batch > 1;
+    double scale_w = vw ? (double)vw->full_w : (double)d->w, scale_h = vw ? (double)vw->full_h : (double)d->h;
+    double full_wmin = scale_w, full_hmin = scale_h;
+    if (bviews) {
+        for (int b = 1; b < d->batch; ++b) {
+            scale_w = std::fmax(scale_w, (double)vw[b].full_w);
+            scale_h = std::fmax(scale_h, (double)vw[b].full_h);
+            full_wmin = std::fmin(full_wmin, (double)vw[b].full_w);
+            full_hmin = std::fmin(full_hmin, (double)vw[b].full_h);
+        }
+    }
     P.s = d->s; P.h = d->h; P.w = d->w; P.row0 = d->row0; P.row1 = d->row1;
     P.bounded = d->dmax >= 0.f;
     P.dmax = P.bounded ? d->dmax : INFINITY;
@@ -632,8 +683,8 @@ inline Params make_params(const gsasr_dims *d, const Layout &L, const gsasr_view
     P.ext_groups = L.ext_groups;
     P.dead_off = (int)L.dead_off_words;
     {
-        double wmin = scale_w, hmin = scale_h;
-        if (d->batch > 1) {
+        double wmin = full_wmin, hmin = full_hmin;
+        if (d->batch > 1 && !bviews) {
             for (int b = 0; b < d->batch; ++b) {
                 hmin = std::fmin(hmin, (double)d->sample_hw[2 * b]);
                 wmin = std::fmin(wmin, (double)d->sample_hw[2 * b + 1]);
@@ -654,7 +705,7 @@ inline Params make_params(const gsasr_dims *d, const Layout &L, const gsasr_view
     P.kb_max = (adapt && gradtau_on && whole) ? (float)(std::sqrt(2.0 * (double)GSASR_SPLAT_GRAD_TAU) * (1.0 + 1e-6)) : 0.f;
     if (P.bounded && adapt) {
         const int B = batch_of(d);
-        const double dpx = (double)d->dmax * 0.5 * (scale_w - 1.0), dpy = (double)d->dmax * 0.5 * ((B > 1 ? (double)d->slot : scale_h) - 1.0);
+        const double dpx = (double)d->dmax * 0.5 * (scale_w - 1.0), dpy = (double)d->dmax * 0.5 * ((B > 1 && !bviews ? (double)d->slot : scale_h) - 1.0);
         // (a continuous plan counts for a point up to half a pixel off its nearest pixel p: a Gaussian whose box covers it is
         // binned within floor(dmax_px + 1.02) + 1 pixels of p -- adapt_kcut, "box")
         const double half = (d->flags & GSASR_FLAG_CONTINUOUS) ? 1.0 : 0.0;
@@ -721,7 +772,7 @@ constexpr double WINDOW_EPS = 0.02;  // px; covers every rounding between these 
 // (VIEW: g is the window -- what the box is clipped to -- and the pixel scale is the full grid's, view_scale)
 template <bool VIEW = false>
 __device__ __forceinline__ Box gaussian_box(float sx, float sy, float x, float y, const Params &P, const Geo &g, float kcut,
-                                            const ViewArg &vw = ViewArg{0, 0, 0, 0})
+                                            const ViewArg &vw = ViewArg{0, 0, 0, 0, nullptr})
 {
     Box b;
     float ext_x = P.dmax, ext_y = P.dmax;
@@ -898,6 +949,9 @@ __device__ __forceinline__ unsigned count_index(int k, int ncells, int dead_off)
 struct BatchSizes {   // kernel argument: the host's per-sample sizes
     unsigned short h[GSASR_MAX_BATCH], w[GSASR_MAX_BATCH];
 };
+struct BatchViews {   // kernel argument: the host's per-sample views {full_h, full_w, y0, x0}
+    int4 v[GSASR_MAX_BATCH];
+};
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
@@ -1063,8 +1117,9 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
                    float *g_coords, float *g_colors, const gsasr_dims *dims, const void *workspace, size_t workspace_bytes,
                    void *stream, bool gather, int *mode_out, const gsasr_view *vw = nullptr);
 // splat_backward_home.hip
+// (VW: the plan's view argument, view_arg; null without a view)
 int launch_bwd_home(const Params &P, const PlanView &V, const float *grad_img, float *g_sigmas, float *g_coords, float *g_colors,
-                    int variant, hipStream_t st, const gsasr_view *vw = nullptr);
+                    int variant, hipStream_t st, const ViewArg *VW = nullptr);
 // splat_step.hip
 struct StepLayout {
     size_t plan_bytes, off_step, off_sig, off_xy, off_col, off_gsig, off_gxy, off_gcol, off_ghwc, total;
@@ -1073,7 +1128,8 @@ StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws = nullpt
 int step_prologue_plan(const float *gs_parameters, StepSrc SS, const gsasr_dims *dims, void *workspace,
                        size_t workspace_bytes, void *stream, StepLayout &S, const gsasr_view *vw = nullptr);
 int prologue_backward_batched(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
-                              const float *gs, const float *gc, const float *gk, float *g_parameters, void *stream);
+                              const float *gs, const float *gc, const float *gk, float *g_parameters, void *stream,
+                              const void *view_tab = nullptr);
 
 }  // namespace gsasr_detail
 

@@ -15,6 +15,14 @@ __global__ __launch_bounds__(64) void k_batch_geo(BatchSizes S, int batch, int s
     if (b < batch) geo[b] = make_int4((int)S.h[b], (int)S.w[b], b * slot, b * w);
 }
 
+// batched canvas with one window per sample: publish the views (host array) to the workspace, for the plan's kernels and the
+// home-tile backward (sample_view)
+__global__ __launch_bounds__(64) void k_batch_views(BatchViews S, int batch, int4 *__restrict__ tab)
+{
+    const int b = threadIdx.x;
+    if (b < batch) tab[b] = S.v[b];
+}
+
 // (VIEW: the plan of a window, gsasr_view -- P.h, P.w are the window, coordinates scale with the full grid: view_scale)
 template <bool PROLOGUE, bool VIEW>
 __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restrict__ sigmas,
@@ -32,7 +40,16 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
     for (int k = i; k < P.tl_ntiles; k += (int)(gridDim.x * blockDim.x)) V.tl_cursor[(size_t)k * TL_STRIDE] = 0u;
     if (i == 0) V.hdr[2] = V.hdr[6] = V.hdr[7] = V.hdr[8] = V.hdr[9] = 0u;   // largest cell / block count: raised with atomicMax by k_scan_local / block_count_max
     // pixel-centre tables: the reference's double expression, rounded to float (gs_cuda/gs.cu:27-28)
-    if (VIEW) {   // the window's slice of the full grid's tables: the same floats
+    if (VIEW && P.batch > 1) {   // ... per sample: its slice of its own full grid's tables (padding continues it)
+        if (i < P.w * P.batch) {
+            const ViewArg a = sample_view<VIEW>(VW, i / P.w);
+            V.px[i] = (float)(2.0 * (double)(a.x0 + i % P.w) / (double)(a.fw - 1) - 1.0);
+        }
+        if (i < P.h) {
+            const ViewArg a = sample_view<VIEW>(VW, i / P.slot);
+            V.py[i] = (float)(2.0 * (double)(a.y0 + i % P.slot) / (double)(a.fh - 1) - 1.0);
+        }
+    } else if (VIEW) {   // the window's slice of the full grid's tables: the same floats
         if (i < P.w) V.px[i] = (float)(2.0 * (double)(VW.x0 + i) / (double)(VW.fw - 1) - 1.0);
         if (i < P.h) V.py[i] = (float)(2.0 * (double)(VW.y0 + i) / (double)(VW.fh - 1) - 1.0);
     } else if (P.batch <= 1) {
@@ -45,7 +62,8 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
     unsigned rx = 0, ry = 0, key = 0xffffffffu;
     if (i < P.s) {
         const Geo g = sample_geo(P, V, P.batch > 1 ? i / P.nper : 0);
-        const Scale sc = view_scale<VIEW>(VW, g);
+        const ViewArg vws = sample_view<VIEW>(VW, P.batch > 1 ? i / P.nper : 0);
+        const Scale sc = view_scale<VIEW>(vws, g);
         float sx, sy, x, y;
         if (PROLOGUE) {
             float o[8];
@@ -74,7 +92,7 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
             sx = sigmas[i3 + 0]; sy = sigmas[i3 + 1];
             x = coords[i2 + 0]; y = coords[i2 + 1];
         }
-        const Box b = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kcut, VW);
+        const Box b = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kcut, vws);
         if (b.cls == 2) {
             // NDEAD counters instead of one: a row band of a large image sees most of the Gaussians here, and one
             // returning atomic per wave on a single word serialises (203 us for 1 M Gaussians, 7/8 dead)
@@ -539,14 +557,15 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
     if (valid) {
         const int smp = P.batch > 1 ? i / P.nper : 0;
         const Geo g = sample_geo(P, V, smp);
-        const Scale sc = view_scale<VIEW>(VW, g);
-        Box b = gaussian_box<VIEW>(sx, sy, x, y, P, g, kc, VW);
+        const ViewArg vws = sample_view<VIEW>(VW, smp);
+        const Scale sc = view_scale<VIEW>(vws, g);
+        Box b = gaussian_box<VIEW>(sx, sy, x, y, P, g, kc, vws);
         // A Gaussian k_classify kept (with the conservative cutoff) whose window under the smaller cutoff holds no pixel keeps
         // its conservative window: every consumer finds a non-empty window behind a live key, and the classes' extents
         // (header words 0, 1: the conservative ones) cover it.
         float kw = kc;
         if (b.cls == 2 && key <= (unsigned)P.ncells && kc != P.kcut) {
-            b = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kcut, VW);
+            b = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kcut, vws);
             kw = P.kcut;
             if (key < (unsigned)P.ncells) {   // (normal class: the tiles must search as far as this conservative window reaches)
                 fb_rx = (unsigned)ceilf(b.ex) + 2u;
@@ -669,7 +688,7 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
                 Box w = b;
                 bool test_b = needs_test;
                 if (P.kb_max > 0.f && kw > P.kb_max) {
-                    const Box t = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kb_max, VW);
+                    const Box t = gaussian_box<VIEW>(sx, sy, x, y, P, g, P.kb_max, vws);
                     if (t.cls != 2) {
                         w = t;
                         test_b = P.bounded && !(P.kb_max * fabsf(sx) * hx + 1.f <= P.dmax * hx && P.kb_max * fabsf(sy) * hy + 1.f <= P.dmax * hy);
@@ -815,7 +834,13 @@ int plan_impl(const float *sigmas, const float *coords, const float *colors, con
     hipStream_t st = (hipStream_t)stream;
     const Params P = make_params(dims, L, vw);
     const PlanView V = make_view(L, workspace, dims->flags);
-    const ViewArg VW = view_arg(vw);
+    const ViewArg VW = view_arg(vw, dims->batch, (const char *)workspace + L.off_vtab);
+    if (vw && dims->batch > 1) {   // (before the classify kernel, which reads them)
+        BatchViews S;
+        for (int b = 0; b < GSASR_MAX_BATCH; ++b)
+            S.v[b] = b < dims->batch ? make_int4(vw[b].full_h, vw[b].full_w, vw[b].y0, vw[b].x0) : make_int4(0, 0, 0, 0);
+        hipLaunchKernelGGL(k_batch_views, dim3(1), dim3(64), 0, st, S, dims->batch, (int4 *)((char *)workspace + L.off_vtab));
+    }
     if (!(dims->flags & GSASR_FLAG_COUNTERS_CLEAN)) HIP_TRY(hipMemsetAsync(V.cell_count, 0, L.count_bytes, st));
     if (!raw)
         if (int rc = launch_batch_geo(dims, V, st)) return rc;   // (a step call has published the geometry already)

@@ -169,13 +169,17 @@ StepLayout make_step_layout(const gsasr_dims *d, const void *planned_ws, bool *n
 
 // chain rule of the prologue on a batched canvas (per-sample grid sizes): shared by the step and the sampled-step backward
 int prologue_backward_batched(const float *gs_parameters, const float *step_size, const gsasr_dims *dims, void *workspace,
-                              const float *gs, const float *gc, const float *gk, float *g_parameters, void *stream)
+                              const float *gs, const float *gc, const float *gk, float *g_parameters, void *stream,
+                              const void *view_tab)
 {
     const PlanView V = make_view(make_layout(dims), workspace);
     int uh, uw;
     batch_uniform(dims, uh, uw);
+    // (one window per sample: the chain rule's factors are each sample's FULL grid's -- the first two words of its view)
+    if (view_tab) uh = uw = 0;
     hipLaunchKernelGGL(k_prologue_bwd, dim3((unsigned)((dims->s + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gs_parameters,
-                       step_size, dims->s, uh, uw, gs, gc, gk, g_parameters, dims->s / dims->batch, (const int4 *)V.geo);
+                       step_size, dims->s, uh, uw, gs, gc, gk, g_parameters, dims->s / dims->batch,
+                       view_tab ? (const int4 *)view_tab : (const int4 *)V.geo);
     HIP_TRY(hipGetLastError());
     return GSASR_OK;
 }
@@ -406,14 +410,19 @@ int step_backward(const float *gs_parameters, const float *step_size, const floa
         const Layout L = plan_layout(dims, workspace, nullptr, vw);
         const PlanView V = make_view(L, workspace);
         Params Pg = make_params(&d, L, vw);
-        if (vw) { Pg.h = vw->full_h; Pg.w = vw->full_w; }      // (the chain rule's align-corners factors: the full grid's; the gather reads no size)
-        hipLaunchKernelGGL(k_prologue_bwd_gather, grid, block, 0, (hipStream_t)stream, Pg, V, (int)(mode == 2 || d.row1 == d.row0),
+        PlanView Vg = V;
+        if (vw && dims->batch > 1) {      // ... per sample: the table of views stands in for the geometry (its first two words: the full grid)
+            Pg.geo_h = Pg.geo_w = 0;
+            Vg.geo = (int4 *)(b + L.off_vtab);
+        } else if (vw) { Pg.h = vw->full_h; Pg.w = vw->full_w; }      // (the chain rule's align-corners factors: the full grid's; the gather reads no size)
+        hipLaunchKernelGGL(k_prologue_bwd_gather, grid, block, 0, (hipStream_t)stream, Pg, Vg, (int)(mode == 2 || d.row1 == d.row0),
                            gs_parameters, step_size, g_parameters);
         HIP_TRY(hipGetLastError());
         return GSASR_OK;
     }
     if (dims->batch > 1) {
-        return prologue_backward_batched(gs_parameters, step_size, dims, workspace, gs, gc, gk, g_parameters, stream);
+        return prologue_backward_batched(gs_parameters, step_size, dims, workspace, gs, gc, gk, g_parameters, stream,
+                                         vw ? b + plan_layout(dims, workspace, nullptr, vw).off_vtab : nullptr);
     }
     return gsasr_prologue_backward(gs_parameters, step_size, dims->s, vw ? vw->full_h : dims->h, vw ? vw->full_w : dims->w, gs, gc, gk,
                                    g_parameters, stream);

@@ -775,16 +775,23 @@ class _FusedBatch(torch.autograd.Function):
     `[B,3,Hmax,Wmax]`, sample b rendered on its own `sizes[b]` pixel grid in the top-left corner of its slot
     and zero elsewhere.  Replaces the reference's per-sample Python loop of `generate_2D_gaussian_splatting_step`
     + `F.pad` (basicsr/models/gsasr_model.py:191-233): B x (prologue, plan, splat) launches and B autograd nodes
-    become one of each."""
+    become one of each.  `views` = [(H_b, W_b, y0_b, x0_b)]: `sizes[b]` is then the window at (y0_b, x0_b) of sample b's own
+    H_b x W_b grid (`generate_2D_gaussian_splatting_batch(windows=...)`)."""
 
     @staticmethod
     @fp32_boundary_fwd
-    def forward(ctx, gs_parameters, steps, sizes, dmax, scale_modify=None, default_step=1.2):
+    def forward(ctx, gs_parameters, steps, sizes, dmax, scale_modify=None, default_step=1.2, views=None):
         from . import _cabi
-        tile = _backward_kernel(sum(h * w for h, w in sizes), gs_parameters.shape[0] * gs_parameters.shape[1],
-                                _batch_shape(gs_parameters.shape[1], sizes, dmax))
+        if views is not None:
+            # (the backward kernel for the Gaussians the windows can expect, as the library judges views; no registered choice)
+            n_per = gs_parameters.shape[1]
+            live = max(1, sum(n_per * (h * w) // (v[0] * v[1]) for (h, w), v in zip(sizes, views)))
+            tile = _backward_kernel(sum(h * w for h, w in sizes), live)
+        else:
+            tile = _backward_kernel(sum(h * w for h, w in sizes), gs_parameters.shape[0] * gs_parameters.shape[1],
+                                    _batch_shape(gs_parameters.shape[1], sizes, dmax))
         flags = _plan_flags(ctx.needs_input_grad[0], tile)
-        img, plan = _cabi.batch_forward(gs_parameters, steps, sizes, dmax, flags, scale_modify, default_step)
+        img, plan = _cabi.batch_forward(gs_parameters, steps, sizes, dmax, flags, scale_modify, default_step, views=views)
         ctx.save_for_backward(gs_parameters, steps)
         ctx.plan = plan
         ctx.h_max = max(h for h, _ in sizes)
@@ -797,7 +804,7 @@ class _FusedBatch(torch.autograd.Function):
         from . import _cabi
         gs_parameters, steps = ctx.saved_tensors
         # [B,3,Hmax,Wmax] read in place (rows per plane = Hmax <= slot): pixels outside a sample's own grid are never read
-        return _cabi.batch_backward(ctx.plan, gs_parameters, steps, grad_output.contiguous(), chw=True), None, None, None, None, None
+        return _cabi.batch_backward(ctx.plan, gs_parameters, steps, grad_output.contiguous(), chw=True), None, None, None, None, None, None
 
 
 def _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev):
@@ -842,17 +849,64 @@ def max_canvas_batch(h_max: int) -> int:
     return max(1, min(64, 32767 // slot))
 
 
+def _batch_windows(sizes, gs_parameters, scales, scale_modifies, windows, default_step_size, mode, if_dmax, dmax_mode, dmax,
+                   uniform_dmax):
+    """`generate_2D_gaussian_splatting_batch(windows=...)`: one canvas whose slots are the windows, each on its own full grid
+    (gsasr_view per sample), or the loop over `generate_2D_gaussian_splatting_view` where a canvas does not apply"""
+    B = gs_parameters.shape[0]
+    if len(windows) != B:
+        raise ValueError("one window per sample")
+    wins = [_window(windows[b], *sizes[b]) for b in range(B)]
+    h_max, w_max = max(w[2] for w in wins), max(w[3] for w in wins)
+    if 1 < B <= max_canvas_batch(h_max) and gs_parameters.is_cuda and gs_parameters.dim() == 3 and gs_parameters.shape[2] == 9 \
+            and uniform_dmax:
+        dev = gs_parameters.device
+        dmax_eff = _resolve_dmax(dmax, dmax_mode, sizes[0]) if if_dmax else None
+        dm = None if dmax_eff is None else float(dmax_eff)
+        wsizes = tuple((w[2], w[3]) for w in wins)
+        views = tuple((H, W, w[0], w[1]) for (H, W), w in zip(sizes, wins))
+        gp = gs_parameters.contiguous()
+        if mode == 'scale_modify':      # (device pairs go to the plan's first kernel as they are: the plain batch's rule)
+            sm = None
+            if torch.is_tensor(scale_modifies) and scale_modifies.dim() == 2 and _sm_source_ok(scale_modifies[0]) \
+                    and scale_modifies.stride(0) >= 2 and scale_modifies.device == dev:
+                sm = scale_modifies
+            elif not torch.is_tensor(scale_modifies) and all(_sm_source_ok(v) and v.device == dev for v in scale_modifies):
+                sm = torch.stack([v[:2] for v in scale_modifies])
+            if sm is not None:
+                out = _FusedBatch.apply(gp, None, wsizes, dm, sm, float(default_step_size), views)
+                deferred_asserts.watch(dev)
+                return out
+        steps = _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev)
+        return _FusedBatch.apply(gp, steps, wsizes, dm, None, 1.2, views)
+    # per-sample path (a single sample, more samples than a canvas holds, a per-sample dmax, CPU tensors)
+    outs = []
+    for b in range(B):
+        o = generate_2D_gaussian_splatting_view(sizes[b], gs_parameters[b], scales[b], scale_modifies[b], wins[b],
+                                                default_step_size=default_step_size, mode=mode, if_dmax=if_dmax, dmax_mode=dmax_mode,
+                                                dmax=dmax)
+        outs.append(torch.nn.functional.pad(o, (0, w_max - wins[b][3], 0, h_max - wins[b][2])))
+    return torch.stack(outs)
+
+
 def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_modifies, default_step_size=1.2,
                                          mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, sample_coords=None,
-                                         query_coords=None, coords_grad=False):
+                                         query_coords=None, coords_grad=False, windows=None):
     """Batched `generate_2D_gaussian_splatting_step`: `gs_parameters` `[B,N,9]`, per-sample
     `sr_sizes[b]`, `scales[b]`, `scale_modifies[b]`; returns `[B,3,Hmax,Wmax]` with every sample zero-padded to
     the largest size -- exactly `torch.stack([F.pad(step(...), ...)])` of the reference's loop.  With
     `sample_coords` `[B,S,2]` (row, column on each sample's own grid; gsasr_model.py:196-197) it returns the
     `[B,3,S]` stack of the per-sample `[3,S]` results instead.  With `query_coords` float `[B,S,2]` (fractional (r, c) on each
     sample's own grid: `generate_2D_gaussian_splatting_query`) likewise `[B,3,S]`; passing both is a ValueError.
-    `coords_grad=True` (with `query_coords` only): differentiable in the positions as well."""
+    `coords_grad=True` (with `query_coords` only): differentiable in the positions as well.
+    `windows` = [(y0, x0, h, w)] * B: sample b's window of its own `sr_sizes[b]` grid only
+    (`generate_2D_gaussian_splatting_view` per sample) -- `[B,3,hmax,wmax]` with hmax, wmax the largest window height and width,
+    window b in the top-left corner of its slot and zero elsewhere: one patch shape whatever the scales are, for the losses
+    that need neighbouring pixels.  One set of launches and one autograd node on CUDA tensors; `dmax_mode` resolves against
+    `sr_sizes`, not the windows; not combinable with `sample_coords` / `query_coords` (ValueError)."""
     B = gs_parameters.shape[0]
+    if windows is not None and (sample_coords is not None or query_coords is not None):
+        raise ValueError("windows render image patches: not combinable with sample_coords / query_coords")
     if coords_grad and query_coords is None:
         raise ValueError("coords_grad=True has a meaning with query_coords only")
     if query_coords is not None:
@@ -870,6 +924,9 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
     if gs_parameters.dtype != torch.float32:
         gs_parameters = gs_parameters.float()
     uniform_dmax = (not if_dmax) or dmax_mode == 'fix' or len(set(sizes)) == 1
+    if windows is not None:
+        return _batch_windows(sizes, gs_parameters, scales, scale_modifies, windows, default_step_size, mode, if_dmax,
+                              dmax_mode, dmax, uniform_dmax)
     cap = max_canvas_batch(max(h for h, _ in sizes))
     if B > cap >= 2 and gs_parameters.is_cuda and gs_parameters.dim() == 3 and uniform_dmax:
         # more samples than one canvas holds (64 slots, 32 767 rows): several canvases of `cap` samples, the last

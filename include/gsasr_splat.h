@@ -297,8 +297,8 @@ GSASR_API int gsasr_step_backward(const float *gs_parameters, const float *step_
  *             FORWARD_ONLY, the kernel-choice flags, crop / pitch / swap of the 8-bit store: those of a whole image of
  *             the window's size.
  *   view      the grid it is cut from, 2 <= full_h, full_w <= 32767, and its origin: 0 <= y0, y0 + h <= full_h, likewise
- *             columns.  Anything else (a row band, a batched canvas, a window that leaves the grid) is GSASR_ERR_ARG /
- *             a workspace size of 0, before anything is enqueued.  view = NULL: the plain entry point.
+ *             columns.  Anything else (a row band, a window that leaves the grid) is GSASR_ERR_ARG / a workspace size
+ *             of 0, before anything is enqueued.  view = NULL: the plain entry point.  (A batched canvas: below.)
  *
  * Output pixel (i, j) IS pixel (y0 + i, x0 + j) of the full grid: the same float coordinates
  * ((float)(2.0 * (x0 + j) / (full_w - 1) - 1.0)), the same dmax box test, the same cutoff rules; the step forms run the host
@@ -310,7 +310,20 @@ GSASR_API int gsasr_step_backward(const float *gs_parameters, const float *step_
  * The view belongs to the plan: forward / backward with another view, or none, on that workspace is GSASR_ERR_PLAN.  The
  * kernel-choice rules see the Gaussians the window can expect, s * (h * w) / (full_h * full_w), not s; choices registered
  * with gsasr_set_kernel_choice are keyed on whole-image shapes and are not looked up for a window (explicit flags in the
- * dims hold as always).  A view that is the whole grid (y0 = x0 = 0, full = dims) is the plain call, bit for bit. */
+ * dims hold as always).  A view that is the whole grid (y0 = x0 = 0, full = dims) is the plain call, bit for bit.
+ *
+ * One window per sample of a batched canvas: with dims.batch = B > 1 (a whole canvas as always: h = B * slot, row0 = 0,
+ * row1 = h, s a multiple of B) `view` addresses B gsasr_views, one per sample in order, and dims.sample_hw[b] is the size of
+ * window b: at least 2 x 2, at most slot x dims.w, inside its own grid (0 <= y0_b, y0_b + h_b <= full_h_b, likewise columns;
+ * 2 <= full_h_b, full_w_b <= 32767).  Everything above holds per sample: pixel (i, j) of slot b is pixel (y0_b + i, x0_b + j)
+ * of sample b rendered alone on its full grid, the step forms run the prologue (and its chain rule) with each sample's full
+ * grid and step size, the backward is the gradient of a loss that looks at the windows only, the padding of a slot is zero
+ * under GSASR_FLAG_OVERWRITE_IMAGE and never read by the backward.  The adaptive cutoff counts with the largest full grid's
+ * dmax box (an upper bound for every sample).  All B views are part of the plan's identity (another set, or none, is
+ * GSASR_ERR_PLAN); when every view is its sample's whole grid the call is the plain batched one, bit for bit.  Row bands and
+ * GSASR_FLAG_CONTINUOUS stay GSASR_ERR_ARG.  The workspace carries the table of views behind everything else: a plan
+ * without views has the bytes and offsets it always had.  The kernel-choice rules judge the canvas with the Gaussians its
+ * windows can expect, sum_b (s / B) * h_b w_b / (full_h_b full_w_b). */
 typedef struct gsasr_view {
     int full_h, full_w;   /* the grid the window is cut from: pixel (Y, X) of it sits at 2*X/(full_w-1)-1, 2*Y/(full_h-1)-1 */
     int y0, x0;           /* the window's first row / column on that grid; its size is dims.h x dims.w               */
