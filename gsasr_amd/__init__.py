@@ -6,9 +6,17 @@ ChrisDud0257/GSASR, behind the reference's own autograd/operator surface).
     from gsasr_amd.gs_cuda.gswrapper import GSCUDA                                 # utils/gs_cuda/gswrapper.py
     import gsasr_amd.gscuda                                                        # pybind module `gscuda`
     from gsasr_amd.shard import splat_band                                         # multi-GPU row-band shard
+    from gsasr_amd import ssim_loss                                                # cri_ssim (SSIMLoss) as one HIP call
 
-The compute lives in gsasr_amd/csrc/splat_{plan,forward,backward,backward_home,step,sampled,shard,api}.hip (hand-written HIP
+The compute lives in gsasr_amd/csrc/splat_{plan,forward,backward,backward_home,step,sampled,shard,ssim,api}.hip (hand-written HIP
 for gfx950; csrc/gsasr_splat.hip is the same code as one translation unit for the micro-benchmark) behind the C ABI of
 include/gsasr_splat.h; Python only moves pointers.  Build with `python -m gsasr_amd.build`.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):      # (lazily: importing the package alone does not import torch)
+    if name == "ssim_loss":
+        from .ssim import ssim_loss
+        return ssim_loss
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -59,11 +59,20 @@ class Loss(ctypes.Structure):
                 ("loss", ctypes.c_void_p), ("img", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
 
 
+class Ssim(ctypes.Structure):
+    """struct gsasr_ssim: the SSIM loss of a stored image (gsasr_ssim_loss)"""
+    _fields_ = [("batch", ctypes.c_int), ("rows", ctypes.c_int), ("w", ctypes.c_int), ("target_rows", ctypes.c_int),
+                ("grad_rows", ctypes.c_int), ("sample_hw", ctypes.POINTER(ctypes.c_int)), ("weight", ctypes.c_float),
+                ("flags", ctypes.c_uint), ("img", ctypes.c_void_p), ("target", ctypes.c_void_p), ("grad_img", ctypes.c_void_p),
+                ("loss", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
+
+
+SSIM_GRAD_HWC, SSIM_ACCUMULATE = 1, 2                   # GSASR_SSIM_GRAD_HWC / _ACCUMULATE
 LOSS_KINDS = {"l1": 0, "mse": 1, "charbonnier": 2}      # GSASR_LOSS_L1 / _MSE / _CHARBONNIER
 LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
-_vwp, _lp = ctypes.POINTER(View), ctypes.POINTER(Loss)
+_vwp, _lp, _ssp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -125,6 +134,9 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_loss_scratch_bytes": (_sz, [_dp]),
     "gsasr_splat_forward_loss": (_i, [_dp, _vwp, _vp, _sz, _lp, _vp]),
     "gsasr_step_forward_loss": (_i, [_vp, _vp, _vp, _i, _f, _vp, _dp, _vwp, _vp, _sz, _lp, _vp]),
+    # the SSIM loss of a stored image (gsasr_ssim)
+    "gsasr_ssim_scratch_bytes": (_sz, [_ssp]),
+    "gsasr_ssim_loss": (_i, [_ssp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1068,6 +1080,65 @@ def batch_forward_loss(gs_parameters: torch.Tensor, steps: Optional[torch.Tensor
     pp, src = _step_args(gs_parameters, steps, scale_modify, default_step_size, sizes)
     shape = _canvas_shape(gs_parameters.shape[1], sizes, dmax, FLAG_OVERWRITE_IMAGE | FLAG_CHW_IMAGE | int(extra_flags), views)
     return _step_loss(shape, pp, src, target, kind, norm, weight, eps, want_image, gs_parameters.device)
+
+
+# ---- SSIM loss of a stored image (include/gsasr_splat.h: gsasr_ssim) -----------------------------------------
+def make_ssim(batch: int, rows: int, w: int, sizes=None, target_rows: int = 0, grad_rows: int = 0, weight: float = 1.0,
+              flags: int = 0) -> Ssim:
+    """a gsasr_ssim descriptor without pointers; `sizes`: the (h_b, w_b) of every sample, None = all rows x w"""
+    d = Ssim(int(batch), int(rows), int(w), int(target_rows), int(grad_rows))
+    d.weight, d.flags = float(weight), int(flags)
+    if sizes is not None:
+        if len(sizes) != batch:
+            raise RuntimeError("sizes must hold one (h, w) per sample")
+        d._hw = (ctypes.c_int * (2 * batch))(*[int(v) for hw in sizes for v in hw])     # kept alive by the descriptor
+        d.sample_hw = ctypes.cast(d._hw, ctypes.POINTER(ctypes.c_int))
+    return d
+
+
+def ssim_loss(img: torch.Tensor, target: torch.Tensor, sizes=None, weight: float = 1.0, want_grad: bool = True,
+              grad: Optional[torch.Tensor] = None, hwc: bool = False, accumulate: bool = False,
+              scratch: Optional[torch.Tensor] = None):
+    """gsasr_ssim_loss: `img` planar `[B,3,rows,W]` (or `[3,rows,W]`), `target` `[B,3,any rows >= every h_b,W]`, `sizes` the
+    samples' own (h_b, w_b) -> (loss `[1 + B]` = {L, L_0 .. L_{B-1}}, d L / d img or None).  The gradient is planar
+    `[B,3,grad_rows,W]`, or with `hwc` interleaved `[B,grad_rows,W,3]`; `grad`: the caller's buffer of that layout (any
+    grad_rows >= every h_b), stored into or -- `accumulate` -- added to, on the samples' own pixels only.  `scratch`: a
+    caller's fp32 buffer of gsasr_ssim_scratch_bytes."""
+    _chk(img, "img")
+    _chk(target, "target")
+    if img.dim() not in (3, 4) or target.dim() != img.dim() or img.shape[-3] != 3 or target.shape[-3] != 3:
+        raise RuntimeError(f"img {tuple(img.shape)} and target {tuple(target.shape)} must both be [B,3,rows,W] or [3,rows,W]")
+    B = img.shape[0] if img.dim() == 4 else 1
+    rows, w, dev = int(img.shape[-2]), int(img.shape[-1]), img.device
+    if target.shape[-1] != w or (target.dim() == 4 and target.shape[0] != B) or target.device != dev:
+        raise RuntimeError(f"target has shape {tuple(target.shape)}, expected [{B}, 3, *, {w}] on the image's device")
+    flags = (SSIM_GRAD_HWC if hwc else 0) | (SSIM_ACCUMULATE if accumulate else 0)
+    d = make_ssim(B, rows, w, sizes, int(target.shape[-2]), 0, weight, flags)
+    with _on(dev):
+        if grad is not None:
+            _chk(grad, "grad")
+            lead = () if img.dim() == 3 and grad.dim() == 3 else (B,)
+            grows = int(grad.shape[-3] if hwc else grad.shape[-2])
+            if tuple(grad.shape) != lead + ((grows, w, 3) if hwc else (3, grows, w)) or grad.device != dev:
+                raise RuntimeError(f"grad has shape {tuple(grad.shape)}, expected {'[B,rows,W,3]' if hwc else '[B,3,rows,W]'}")
+            d.grad_rows = grows
+        elif want_grad:
+            if accumulate:
+                raise RuntimeError("accumulate needs the gradient buffer to add to")
+            lead = (B,) if img.dim() == 4 else ()
+            grad = torch.empty(lead + ((rows, w, 3) if hwc else (3, rows, w)), dtype=torch.float32, device=dev)
+        d.img, d.target, d.grad_img = img.data_ptr(), target.data_ptr(), None if grad is None else grad.data_ptr()
+        n = int(lib().gsasr_ssim_scratch_bytes(ctypes.byref(d)))
+        if n == 0:
+            check(-1, "gsasr_ssim_scratch_bytes")
+        if scratch is None:
+            scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        elif _chk(scratch, "scratch") == 0 or 4 * scratch.numel() < n or scratch.device != dev:
+            raise RuntimeError("scratch is smaller than gsasr_ssim_scratch_bytes()")
+        loss = torch.empty(1 + B, dtype=torch.float32, device=dev)
+        d.loss, d.scratch = loss.data_ptr(), scratch.data_ptr()
+        check(lib().gsasr_ssim_loss(ctypes.byref(d), _stream(dev)), "gsasr_ssim_loss")
+    return loss, grad
 
 
 # ---- sampled pixels (SURVEY.md 8 row f4) ----------------------------------------------------------------

@@ -46,6 +46,8 @@
 //   sampled  k_pts_count/scan/place, k_sample_fwd, k_pts_grads, k_sample_bwd   values and gradients at a list of
 //                        pixels only (the reference's `sample_coords`, row f4): point-stationary two-level walk forward,
 //                        Gaussian-stationary backward with eight Gaussians per wave.
+//   ssim     k_ssim_stats/grad/reduce   the SSIM loss of a stored image against its target and d loss / d image, stored or added
+//                        to the gradient the fused pixel loss wrote (GSASR's cri_ssim; splat_ssim.hip).
 //
 // No MFMA: this is gather/scatter-accumulate with one transcendental per pair, not a contraction.
 // This file is the WHOLE library as one translation unit (tools/mb.hip includes it); gsasr_amd/build.py compiles the parts
@@ -59,3 +61,4 @@
 #include "splat_step.hip"
 #include "splat_sampled.hip"
 #include "splat_shard.hip"
+#include "splat_ssim.hip"

@@ -992,6 +992,9 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
 # truth to gt_size[i], cri_pix(b_output, b_gt) -- L1Loss / MSELoss / CharbonnierLoss of basicsr/losses/basic_loss.py:14-25,
 # reduction='mean', times loss_weight --, summed over the samples and divided by b.  The forward kernels do it at the store: no image
 # is written or read back, no torch loss kernels run, one autograd node.
+from . import ssim as _ssim  # noqa: E402  (the torch expression of the SSIM term and its size rule)
+
+
 def _loss_names(loss, reduction):
     from . import _cabi
     if loss not in _cabi.LOSS_KINDS:
@@ -1006,6 +1009,19 @@ def _pixel_loss(image, target, loss, loss_weight, eps, reduction):
     d = image - target
     phi = d.abs() if loss == 'l1' else d * d if loss == 'mse' else torch.sqrt(d * d + eps)
     return loss_weight * (phi.mean() if reduction == 'mean' else phi.sum())
+
+
+def _ssim_weight(ssim_weight, reduction) -> float:
+    ssim_weight = float(ssim_weight)
+    if ssim_weight != 0.0 and reduction != 'mean':
+        raise ValueError(f"reduction-{reduction}: the SSIM term exists as a mean only (ssim_weight != 0 needs reduction='mean')")
+    return ssim_weight
+
+
+def _loss_returns(value, *extras):
+    """the loss, or the tuple of it and whichever extras were asked for (not None)"""
+    ret = (value,) + tuple(e for e in extras if e is not None)
+    return ret[0] if len(ret) == 1 else ret
 
 
 def _fused_loss_backward(ctx, g_loss, batched):
@@ -1029,6 +1045,17 @@ def _loss_plan_flags(needs_grad: bool, kernel: int) -> int:
     return int(kernel) | (_cabi.FLAG_CHW_GRAD if kernel == _cabi.FLAG_BWD_TILE else 0)
 
 
+def _add_ssim(loss, grad, img, plan, target, sizes, ssim_weight):
+    """the SSIM term behind a fused pixel loss that stored its image: gsasr_ssim_loss on `img` against the same `target`, its
+    gradient ADDED to the one the forward wrote (in the layout the plan's backward reads) -- or, on a forward-only plan, the
+    value alone.  Returns (total, per-sample totals, l_pix, l_ssim)."""
+    from . import _cabi
+    hwc = not (plan.dims.flags & _cabi.FLAG_CHW_GRAD)
+    sl, _ = _cabi.ssim_loss(img, target, sizes, ssim_weight, want_grad=False, grad=grad, hwc=hwc and grad is not None,
+                            accumulate=grad is not None)
+    return loss[0] + sl[0], loss[1:] + sl[1:], loss[0], sl[0]
+
+
 class _FusedStepLoss(torch.autograd.Function):
     """`_FusedStep` ending in the fused pixel loss: raw `gs_parameters[N,9]` and `target[3,h,w]` -> (L, `[1]` per-sample loss,
     and with `want_image` the image), the image gradient kept in `ctx` for the existing backward."""
@@ -1036,7 +1063,7 @@ class _FusedStepLoss(torch.autograd.Function):
     @staticmethod
     @fp32_boundary_fwd
     def forward(ctx, gs_parameters, step, target, H, W, dmax, scale_modify, default_step, extra_flags, window, kind, norm, weight, eps,
-                want_image, needs_grad):
+                want_image, needs_grad, ssim_weight):
         from . import _cabi
         # (needs_grad: requires_grad AND grad mode, from the caller -- a Function's forward always runs with grad mode off)
         if window is not None:
@@ -1048,9 +1075,13 @@ class _FusedStepLoss(torch.autograd.Function):
             h, w, view = H, W, None
             flags = _loss_plan_flags(needs_grad, _backward_kernel(H * W, gs_parameters.shape[0], _step_shape(gs_parameters.shape[0], H, W, dmax))) | int(extra_flags)
         loss, grad, img, plan = _cabi.step_forward_loss(gs_parameters, step, h, w, dmax, target, kind, norm, weight, eps, flags,
-                                                        scale_modify, default_step, view, want_image)
+                                                        scale_modify, default_step, view, want_image or ssim_weight != 0.0)
         ctx.save_for_backward(gs_parameters, step)
         ctx.plan, ctx.grad = plan, grad
+        if ssim_weight != 0.0:      # (total, per, l_pix, l_ssim[, img])
+            out = _add_ssim(loss, grad, img, plan, target, None, ssim_weight) + ((img,) if want_image else ())
+            ctx.mark_non_differentiable(*out[1:])
+            return out
         total, per = loss[0], loss[1:]
         if want_image:
             ctx.mark_non_differentiable(per, img)
@@ -1062,7 +1093,7 @@ class _FusedStepLoss(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     @fp32_boundary_bwd
     def backward(ctx, g_loss, *_):
-        return (_fused_loss_backward(ctx, g_loss, False),) + (None,) * 15
+        return (_fused_loss_backward(ctx, g_loss, False),) + (None,) * 16
 
 
 class _FusedBatchLoss(torch.autograd.Function):
@@ -1072,7 +1103,7 @@ class _FusedBatchLoss(torch.autograd.Function):
     @staticmethod
     @fp32_boundary_fwd
     def forward(ctx, gs_parameters, steps, target, sizes, dmax, scale_modify, default_step, views, kind, norm, weight, eps, want_image,
-                needs_grad):
+                needs_grad, ssim_weight):
         from . import _cabi
         if views is not None:
             n_per = gs_parameters.shape[1]
@@ -1083,9 +1114,14 @@ class _FusedBatchLoss(torch.autograd.Function):
                                       _batch_shape(gs_parameters.shape[1], sizes, dmax))
         flags = _loss_plan_flags(needs_grad, kernel)
         loss, grad, img, plan = _cabi.batch_forward_loss(gs_parameters, steps, sizes, dmax, target, kind, norm, weight, eps, flags,
-                                                         scale_modify, default_step, views, want_image)
+                                                         scale_modify, default_step, views, want_image or ssim_weight != 0.0)
         ctx.save_for_backward(gs_parameters, steps)
         ctx.plan, ctx.grad = plan, grad
+        if ssim_weight != 0.0:      # (total, per, l_pix, l_ssim[, img])
+            out = _add_ssim(loss, grad, img, plan, target, sizes, ssim_weight)
+            out += (img[:, :, : max(h for h, _ in sizes)],) if want_image else ()
+            ctx.mark_non_differentiable(*out[1:])
+            return out
         total, per = loss[0], loss[1:]
         if want_image:
             img = img[:, :, : max(h for h, _ in sizes)]
@@ -1098,7 +1134,7 @@ class _FusedBatchLoss(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     @fp32_boundary_bwd
     def backward(ctx, g_loss, *_):
-        return (_fused_loss_backward(ctx, g_loss, True),) + (None,) * 13
+        return (_fused_loss_backward(ctx, g_loss, True),) + (None,) * 14
 
 
 def _loss_target_tensor(target, shape, dev, what="target"):
@@ -1114,12 +1150,15 @@ def _loss_target_tensor(target, shape, dev, what="target"):
 def generate_2D_gaussian_splatting_loss(sr_size, gs_parameters, scale, scale_modify, target, loss='l1', loss_weight=1.0, eps=1e-12,
                                         reduction='mean', window=None, return_image=False, default_step_size=1.2,
                                         mode='scale_modify', if_dmax=True, dmax_mode='fix', dmax=25, sample_coords=None,
-                                        query_coords=None):
+                                        query_coords=None, ssim_weight=0.0, return_terms=False):
     """`loss_weight * cri_pix(generate_2D_gaussian_splatting_step(...), target)` for `loss` in 'l1' | 'mse' | 'charbonnier'
     (basicsr/losses/basic_loss.py:14-25; `reduction` 'mean' | 'sum') as ONE differentiable call that never materialises the
     image: the forward kernels load `target[3,H,W]` at the store, write d loss / d image for the backward and reduce the loss
     (gsasr_step_forward_loss).  Returns the 0-dim loss, or `(loss, image)` with `return_image=True` (the image is not
-    differentiable: `cri_ssim` and perceptual terms that need gradients through it take the plain call).  `window` =
+    differentiable: perceptual terms that need gradients through it take the plain call).  `ssim_weight` != 0 adds GSASR's other
+    training term, `ssim_weight * (1 - ssim(image, target))` (`cri_ssim`, basic_loss.py:256-264; 'mean' only): the forward stores
+    the image, gsasr_ssim_loss adds its gradient to the one the forward wrote, and the whole `l_pix + l_ssim` is still one autograd
+    node with one backward.  `return_terms` appends the pair `(l_pix, l_ssim)` of detached 0-dim tensors.  `window` =
     (y0, x0, h, w): the loss over that window of the grid only, `target[3,h,w]` (`generate_2D_gaussian_splatting_view`).
     Under `torch.no_grad()` the plan is forward-only (a validation loss).  CPU tensors: the torch expression on
     `rendering_python`'s image.  `sample_coords` / `query_coords` are not covered (ValueError)."""
@@ -1128,32 +1167,42 @@ def generate_2D_gaussian_splatting_loss(sr_size, gs_parameters, scale, scale_mod
         raise ValueError("the fused pixel loss covers whole images and windows, not sample_coords / query_coords")
     if not (float(eps) >= 0.0):
         raise ValueError(f"eps-{eps} must be >= 0")
+    ssim_weight = _ssim_weight(ssim_weight, reduction)
     if gs_parameters.dtype != torch.float32:
         gs_parameters = gs_parameters.float()
     H, W = _hw(sr_size)
     win = None if window is None else _window(window, H, W)
     h, w = (H, W) if win is None else (win[2], win[3])
+    if ssim_weight != 0.0:
+        _ssim.check_sizes([(h, w)], "sample or window")
     target = _loss_target_tensor(target, (3, h, w), gs_parameters.device)
     if not gs_parameters.is_cuda:
         step_size = _step_size(scale, scale_modify, default_step_size, mode)
         image = rendering_python(*_activate(gs_parameters), sr_size, step_size, device=gs_parameters.device)
         if win is not None:
             image = image[:, win[0]:win[0] + h, win[1]:win[1] + w]
-        value = _pixel_loss(image, target, loss, loss_weight, eps, reduction)
-        return (value, image.detach()) if return_image else value
+        value = l_pix = _pixel_loss(image, target, loss, loss_weight, eps, reduction)
+        l_ssim = torch.zeros((), dtype=value.dtype)
+        if ssim_weight != 0.0:
+            l_ssim = _ssim.ssim_torch(image, target, ssim_weight)
+            value = l_pix + l_ssim
+        return _loss_returns(value, image.detach() if return_image else None, (l_pix.detach(), l_ssim.detach()) if return_terms else None)
     if not _fused_ok(gs_parameters):
         raise RuntimeError("generate_2D_gaussian_splatting_loss needs gs_parameters [N,9] on the GPU (no fallback)")
     step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=True)
     dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
     dm = None if dmax_eff is None else float(dmax_eff)
     gp, hint = gs_parameters.contiguous(), _forward_flag(scale, h, w)
-    tail = (kind, norm, float(loss_weight), float(eps), bool(return_image), gp.requires_grad and torch.is_grad_enabled())
+    tail = (kind, norm, float(loss_weight), float(eps), bool(return_image), gp.requires_grad and torch.is_grad_enabled(), ssim_weight)
     if step_size.__class__ is _StepSource:
         out = _FusedStepLoss.apply(gp, None, target, H, W, dm, step_size.scale_modify, step_size.default_step, hint, win, *tail)
         deferred_asserts.watch(gp.device)
     else:
         out = _FusedStepLoss.apply(gp, _step_tensor(step_size, gp.device), target, H, W, dm, None, 1.2, hint, win, *tail)
-    return (out[0], out[2]) if return_image else out[0]
+    if ssim_weight != 0.0:
+        return _loss_returns(out[0], out[4] if return_image else None, (out[2], out[3]) if return_terms else None)
+    terms = (out[0].detach(), torch.zeros_like(out[0])) if return_terms else None
+    return _loss_returns(out[0], out[2] if return_image else None, terms)
 
 
 def _batch_sm_source(scale_modifies, dev):
@@ -1169,7 +1218,7 @@ def _batch_sm_source(scale_modifies, dev):
 def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, scale_modifies, targets, loss='l1', loss_weight=1.0,
                                               eps=1e-12, reduction='mean', default_step_size=1.2, mode='scale_modify', if_dmax=True,
                                               dmax_mode='fix', dmax=25, windows=None, return_per_sample=False, return_images=False,
-                                              sample_coords=None, query_coords=None):
+                                              sample_coords=None, query_coords=None, ssim_weight=0.0, return_terms=False):
     """The pixel loss of a training batch (the loop of basicsr/models/gsasr_model.py:191-237) as ONE differentiable call:
     sample b of `generate_2D_gaussian_splatting_batch(...)` against `targets[b][:, :h_b, :w_b]` with `cri_pix` = `loss`
     ('l1' | 'mse' | 'charbonnier', `reduction` 'mean' | 'sum', times `loss_weight`), summed over the samples and -- 'mean' --
@@ -1177,12 +1226,16 @@ def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, s
     a list of `[3,h_b,w_b]` (stacked once); with `windows` the patches `[B,3,hmax,wmax]`.  Returns the 0-dim loss; with
     `return_per_sample` / `return_images` a tuple (loss, `[B]` per-sample losses L_b, `[B,3,Hmax,Wmax]` images) of what was asked
     for -- both non-differentiable.  On CUDA tensors the image is never written unless asked for, and there is one autograd node;
-    where the batch function takes its per-sample path the same value is computed sample by sample."""
+    where the batch function takes its per-sample path the same value is computed sample by sample.  `ssim_weight` != 0 adds
+    `ssim_weight * (1 - ssim)` of every sample (`cri_ssim`; reduction 'mean' only) inside the same node -- the loop's
+    `l_total = l_pix + l_ssim` --, the per-sample losses are then the totals, and `return_terms` appends the pair
+    `(l_pix, l_ssim)` of detached 0-dim tensors (the reference's `loss_dict`)."""
     kind, norm = _loss_names(loss, reduction)
     if sample_coords is not None or query_coords is not None:
         raise ValueError("the fused pixel loss covers whole images and windows, not sample_coords / query_coords")
     if not (float(eps) >= 0.0):
         raise ValueError(f"eps-{eps} must be >= 0")
+    ssim_weight = _ssim_weight(ssim_weight, reduction)
     B = gs_parameters.shape[0]
     if torch.is_tensor(sr_sizes) and sr_sizes.dim() == 2:
         sizes = [(int(r[0]), int(r[1])) for r in sr_sizes.tolist()]
@@ -1197,6 +1250,8 @@ def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, s
     wins = None if windows is None else [_window(windows[b], *sizes[b]) for b in range(B)]
     wsizes = tuple(sizes) if wins is None else tuple((w[2], w[3]) for w in wins)
     h_max, w_max = max(h for h, _ in wsizes), max(w for _, w in wsizes)
+    if ssim_weight != 0.0:
+        _ssim.check_sizes(wsizes, "sample or window")
     dev = gs_parameters.device
     if torch.is_tensor(targets):
         targets = _loss_target_tensor(targets, (B, 3, None, w_max), dev, "targets")
@@ -1214,7 +1269,8 @@ def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, s
         dm = None if dmax_eff is None else float(dmax_eff)
         views = None if wins is None else tuple((H, W, w[0], w[1]) for (H, W), w in zip(sizes, wins))
         gp = gs_parameters.contiguous()
-        tail = (kind, norm, float(loss_weight), float(eps), bool(return_images), gp.requires_grad and torch.is_grad_enabled())
+        tail = (kind, norm, float(loss_weight), float(eps), bool(return_images), gp.requires_grad and torch.is_grad_enabled(),
+                ssim_weight)
         sm = _batch_sm_source(scale_modifies, dev) if mode == 'scale_modify' else None
         if sm is not None:
             out = _FusedBatchLoss.apply(gp, None, targets, wsizes, dm, sm, float(default_step_size), views, *tail)
@@ -1222,24 +1278,31 @@ def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, s
         else:
             steps = _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev)
             out = _FusedBatchLoss.apply(gp, steps, targets, wsizes, dm, None, 1.2, views, *tail)
-        total, per, images = out[0], out[1], (out[2] if return_images else None)
+        if ssim_weight != 0.0:
+            total, per, terms, images = out[0], out[1], (out[2], out[3]), (out[4] if return_images else None)
+        else:
+            total, per, images = out[0], out[1], (out[2] if return_images else None)
+            terms = (total.detach(), torch.zeros_like(total)) if return_terms else None
     else:
         # per-sample path (a single sample, more samples than a canvas holds, a per-sample dmax, CPU tensors): the same value
-        vals, imgs = [], []
+        vals, imgs, pix, ssm = [], [], [], []
         for b in range(B):
             hb, wb = wsizes[b]
             o = generate_2D_gaussian_splatting_loss(sizes[b], gs_parameters[b], scales[b], scale_modifies[b], targets[b, :, :hb, :wb],
                                                     loss, loss_weight, eps, reduction, None if wins is None else wins[b], return_images,
-                                                    default_step_size, mode, if_dmax, dmax_mode, dmax)
+                                                    default_step_size, mode, if_dmax, dmax_mode, dmax, ssim_weight=ssim_weight,
+                                                    return_terms=True)
             if return_images:
                 imgs.append(F.pad(o[1], (0, w_max - wb, 0, h_max - hb)))
-                o = o[0]
-            vals.append(o)
+            vals.append(o[0])
+            pix.append(o[-1][0])
+            ssm.append(o[-1][1])
         stacked = torch.stack(vals)
-        total = stacked.sum() / B if reduction == 'mean' else stacked.sum()
+        div = B if reduction == 'mean' else 1
+        total = stacked.sum() / div
         per, images = stacked.detach(), (torch.stack(imgs) if return_images else None)
-    ret = (total,) + ((per,) if return_per_sample else ()) + ((images,) if return_images else ())
-    return ret[0] if len(ret) == 1 else ret
+        terms = (torch.stack(pix).sum() / div, torch.stack(ssm).sum() / div)
+    return _loss_returns(total, per if return_per_sample else None, images if return_images else None, terms if return_terms else None)
 
 
 def generate_2D_gaussian_splatting_step_buffer(sr_size, gs_parameters, scale, scale_modify, sample_coords=None,

@@ -420,6 +420,55 @@ GSASR_API int gsasr_step_forward_loss(const float *gs_parameters, const float *s
                             float default_step_size, int *mismatch, const gsasr_dims *dims, const gsasr_view *view,
                             void *workspace, size_t workspace_bytes, const gsasr_loss *loss, void *stream);
 
+/* SSIM loss of a rendered batch (training: the other half of l_total = l_pix + l_ssim, basicsr/models/gsasr_model.py:213-242 --
+ * cri_ssim = SSIMLoss, basicsr/losses/basic_loss.py:256-264: loss_weight * (1 - pytorch_msssim.ssim(x, y, data_range=1)) per sample,
+ * summed over the samples and divided by b).  It needs the image, so it is a call of its own behind a forward that stored one
+ * (GSASR_FLAG_CHW_IMAGE; gsasr_loss.img), and it can ADD its gradient to the one the fused pixel loss wrote: one backward serves
+ * both terms.  No float atomics, no memset, no allocation, no host synchronisation; two calls give the same bits.
+ *
+ *   window  g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, i = 0..10, applied along rows and columns per channel in "valid" mode: sample
+ *           b (h_b x w_b pixels) has a map of 3 x (h_b - 10) x (w_b - 10) values
+ *   mu1 = g*x, mu2 = g*y, s1 = g*(x^2) - mu1^2, s2 = g*(y^2) - mu2^2, s12 = g*(xy) - mu1 mu2,  C1 = 0.01^2, C2 = 0.03^2
+ *   A1 = 2 mu1 mu2 + C1, A2 = 2 s12 + C2, B1 = mu1^2 + mu2^2 + C1, B2 = s1 + s2 + C2,  map = (A1 / B1) (A2 / B2)  (not clamped)
+ *   L_b = weight * (1 - mean(map)),  L = (1 / B) sum_b L_b;  loss[0] = L, loss[1 + b] = L_b
+ *   d map / d s1 = -A1 A2 / (B1 B2^2),  d map / d s12 = 2 A1 / (B1 B2),
+ *   d map / d mu1 = 2 mu2 A2 / (B1 B2) - 2 mu1 A1 A2 / (B1^2 B2) - 2 mu1 d map / d s1 - mu2 d map / d s12
+ *   grad_img = c_b [ gT*(d map / d mu1) + 2 x gT*(d map / d s1) + y gT*(d map / d s12) ],  c_b = -weight / (3 (h_b - 10) (w_b - 10) B)
+ *           (gT*: the transposed correlation with the same window, the map taken as zero outside its valid pixels)
+ * Plain IEEE fp32 arithmetic, the tiles' sums of 1 - map added in double: a NaN pixel makes the map NaN within its 11 x 11 reach, and its sample's loss.
+ * (The kernels evaluate the formulas on x - cx, y - cy, cx and cy the sample's centre pixel of the channel -- the same quantities
+ * with less cancellation where the images are flat; a NaN or Inf there reaches every value of that sample's channel.)
+ *
+ *   img        planar [batch, 3, rows, w], as GSASR_FLAG_CHW_IMAGE stores it (one image: batch = 1, [3, rows, w])
+ *   target     planar [batch, 3, target_rows, w], read in place (target_rows = 0: rows; the padded ground truth may have more rows)
+ *   sample_hw  HOST array [2 * batch] of (h_b, w_b), read during the call, as gsasr_dims.sample_hw; NULL: every sample is rows x w.
+ *              Only a sample's own pixels are read, of img and of target
+ *   grad_img   NULL: the value only.  Else d L / d img, planar [batch, 3, grad_rows, w] (what a backward with GSASR_FLAG_CHW_GRAD
+ *              reads), or with GSASR_SSIM_GRAD_HWC interleaved [batch * grad_rows, w, 3] (grad_rows = 0: rows).  The samples' own
+ *              pixels are stored -- with GSASR_SSIM_ACCUMULATE added to what is there --, the padding is never touched
+ *   loss       device float[1 + batch]
+ *   scratch    gsasr_ssim_scratch_bytes(descriptor) bytes, 4-byte aligned: the tiles' partial sums and, when grad_img is not NULL,
+ *              the three derivative maps (36 bytes per pixel of img).  Every word is written before it is read
+ * GSASR_ERR_ARG before anything is enqueued: null img / target / loss / scratch, batch outside 1..GSASR_MAX_BATCH, rows or w
+ * outside 11..32767, a sample smaller than 11 in either extent or larger than rows x w, 0 < target_rows or 0 < grad_rows below a
+ * sample's height, unknown flag bits. */
+#define GSASR_SSIM_GRAD_HWC 1u   /* grad_img interleaved [batch * grad_rows, w, 3]; else planar [batch, 3, grad_rows, w] */
+#define GSASR_SSIM_ACCUMULATE 2u /* grad_img += ...; else the samples' own pixels are stored, padding untouched */
+typedef struct gsasr_ssim {
+    int batch, rows, w;
+    int target_rows;      /* 0 = rows */
+    int grad_rows;        /* 0 = rows */
+    const int *sample_hw; /* HOST array [2*batch], or NULL */
+    float weight;         /* loss_weight */
+    unsigned flags;       /* GSASR_SSIM_* */
+    const float *img, *target;
+    float *grad_img;
+    float *loss;
+    void *scratch;
+} gsasr_ssim;
+GSASR_API size_t gsasr_ssim_scratch_bytes(const gsasr_ssim *ssim);   /* 0 on bad arguments (the pointers other than grad_img are not looked at) */
+GSASR_API int gsasr_ssim_loss(const gsasr_ssim *ssim, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate
