@@ -7,8 +7,9 @@ ChrisDud0257/GSASR, behind the reference's own autograd/operator surface).
     import gsasr_amd.gscuda                                                        # pybind module `gscuda`
     from gsasr_amd.shard import splat_band                                         # multi-GPU row-band shard
     from gsasr_amd import ssim_loss                                                # cri_ssim (SSIMLoss) as one HIP call
+    from gsasr_amd import image_metrics, calculate_psnr, calculate_ssim            # val.metrics of the 8-bit picture, on the GPU
 
-The compute lives in gsasr_amd/csrc/splat_{plan,forward,backward,backward_home,step,sampled,shard,ssim,api}.hip (hand-written HIP
+The compute lives in gsasr_amd/csrc/splat_{plan,forward,backward,backward_home,step,sampled,shard,ssim,metrics,api}.hip (hand-written HIP
 for gfx950; csrc/gsasr_splat.hip is the same code as one translation unit for the micro-benchmark) behind the C ABI of
 include/gsasr_splat.h; Python only moves pointers.  Build with `python -m gsasr_amd.build`.
 """
@@ -19,4 +20,7 @@ def __getattr__(name):      # (lazily: importing the package alone does not impo
     if name == "ssim_loss":
         from .ssim import ssim_loss
         return ssim_loss
+    if name in ("image_metrics", "calculate_psnr", "calculate_ssim"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

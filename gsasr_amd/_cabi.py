@@ -67,12 +67,21 @@ class Ssim(ctypes.Structure):
                 ("loss", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
 
 
+class Metrics(ctypes.Structure):
+    """struct gsasr_metrics: PSNR and SSIM of an 8-bit picture against its ground truth (gsasr_image_metrics)"""
+    _fields_ = [("batch", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("sample_hw", ctypes.POINTER(ctypes.c_int)),
+                ("img", ctypes.c_void_p), ("img_pitch", ctypes.c_size_t), ("img_stride", ctypes.c_size_t),
+                ("ref", ctypes.c_void_p), ("ref_pitch", ctypes.c_size_t), ("ref_stride", ctypes.c_size_t),
+                ("crop_border", ctypes.c_int), ("flags", ctypes.c_uint), ("out", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
+
+
 SSIM_GRAD_HWC, SSIM_ACCUMULATE = 1, 2                   # GSASR_SSIM_GRAD_HWC / _ACCUMULATE
+METRIC_PSNR, METRIC_SSIM, METRIC_Y, METRIC_BGR = 1, 2, 4, 8     # GSASR_METRIC_*
 LOSS_KINDS = {"l1": 0, "mse": 1, "charbonnier": 2}      # GSASR_LOSS_L1 / _MSE / _CHARBONNIER
 LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
-_vwp, _lp, _ssp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim)
+_vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -137,6 +146,9 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     # the SSIM loss of a stored image (gsasr_ssim)
     "gsasr_ssim_scratch_bytes": (_sz, [_ssp]),
     "gsasr_ssim_loss": (_i, [_ssp, _vp]),
+    # PSNR / SSIM of an 8-bit picture (gsasr_metrics)
+    "gsasr_metrics_scratch_bytes": (_sz, [_mp]),
+    "gsasr_image_metrics": (_i, [_mp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1139,6 +1151,68 @@ def ssim_loss(img: torch.Tensor, target: torch.Tensor, sizes=None, weight: float
         d.loss, d.scratch = loss.data_ptr(), scratch.data_ptr()
         check(lib().gsasr_ssim_loss(ctypes.byref(d), _stream(dev)), "gsasr_ssim_loss")
     return loss, grad
+
+
+# ---- validation metrics of an 8-bit picture (include/gsasr_splat.h: gsasr_metrics) -----------------------------
+def make_metrics(batch: int, h: int, w: int, sizes=None, crop_border: int = 0, flags: int = METRIC_PSNR | METRIC_SSIM,
+                 img_pitch: Optional[int] = None, img_stride: Optional[int] = None, ref_pitch: Optional[int] = None,
+                 ref_stride: Optional[int] = None) -> Metrics:
+    """a gsasr_metrics descriptor without pointers (dense pitches and strides unless given); `sizes`: the (h_b, w_b) of every
+    sample, None = all h x w"""
+    d = Metrics(int(batch), int(h), int(w))
+    d.img_pitch = 3 * int(w) if img_pitch is None else int(img_pitch)
+    d.ref_pitch = 3 * int(w) if ref_pitch is None else int(ref_pitch)
+    d.img_stride = int(h) * d.img_pitch if img_stride is None else int(img_stride)
+    d.ref_stride = int(h) * d.ref_pitch if ref_stride is None else int(ref_stride)
+    d.crop_border, d.flags = int(crop_border), int(flags)
+    if sizes is not None:
+        if len(sizes) != batch:
+            raise RuntimeError("sizes must hold one (h, w) per sample")
+        d._hw = (ctypes.c_int * (2 * batch))(*[int(v) for hw in sizes for v in hw])     # kept alive by the descriptor
+        d.sample_hw = ctypes.cast(d._hw, ctypes.POINTER(ctypes.c_int))
+    return d
+
+
+def _u8_picture(t: torch.Tensor, name: str):
+    """a uint8 CUDA `[h,w,3]` or `[B,h,w,3]` tensor whose innermost `[w,3]` is dense and whose row and sample strides are not
+    negative -> (pointer, pitch, stride) in bytes"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+        raise RuntimeError(f"{name} must be a uint8 CUDA tensor")
+    if t.dim() not in (3, 4) or t.shape[-1] != 3:
+        raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected [h,w,3] or [B,h,w,3]")
+    st = t.stride()
+    dense = st[-1] == 1 and (st[-2] == 3 or t.shape[-2] == 1)              # (the stride of an extent of 1 is never used)
+    rows_apart = st[-3] >= 3 * t.shape[-2] or t.shape[-3] == 1
+    if not dense or not rows_apart or (t.dim() == 4 and st[0] < 0):
+        raise RuntimeError(f"{name} has strides {st}: the innermost [w,3] must be dense and rows at least 3 * w bytes apart")
+    return t.data_ptr(), (st[-3] if t.shape[-3] > 1 else 3 * t.shape[-2]), (st[0] if t.dim() == 4 else 0)
+
+
+def image_metrics(img: torch.Tensor, ref: torch.Tensor, sizes=None, crop_border: int = 0, y_channel: bool = False, bgr: bool = False,
+                  psnr: bool = True, ssim: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gsasr_image_metrics: `img`, `ref` uint8 `[h,w,3]` or `[B,H,W,3]` (windows of larger tensors are taken through their
+    strides), `sizes` the samples' own (h_b, w_b) -> float64 `[B,2]` = {psnr, ssim} per sample on the device, no
+    synchronisation.  A metric that is not asked for leaves its column as it is (`out`: the caller's tensor; else zeros)."""
+    pi, ip, istr = _u8_picture(img, "img")
+    pr, rp, rstr = _u8_picture(ref, "ref")
+    if img.shape != ref.shape or img.device != ref.device:
+        raise RuntimeError(f"img {tuple(img.shape)} and ref {tuple(ref.shape)} must have the same shape and device")
+    B = img.shape[0] if img.dim() == 4 else 1
+    h, w, dev = int(img.shape[-3]), int(img.shape[-2]), img.device
+    flags = (METRIC_PSNR if psnr else 0) | (METRIC_SSIM if ssim else 0) | (METRIC_Y if y_channel else 0) | (METRIC_BGR if bgr else 0)
+    d = make_metrics(B, h, w, sizes, crop_border, flags, ip, istr, rp, rstr)
+    n = int(lib().gsasr_metrics_scratch_bytes(ctypes.byref(d)))
+    if n == 0:
+        check(-1, "gsasr_metrics_scratch_bytes")
+    with _on(dev):
+        if out is None:
+            out = torch.empty(B, 2, dtype=torch.float64, device=dev) if psnr and ssim else torch.zeros(B, 2, dtype=torch.float64, device=dev)
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, 2) and out.device == dev):
+            raise RuntimeError(f"out must be a contiguous float64 [{B}, 2] tensor on the pictures' device")
+        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+        d.img, d.ref, d.out, d.scratch = pi, pr, out.data_ptr(), scratch.data_ptr()
+        check(lib().gsasr_image_metrics(ctypes.byref(d), _stream(dev)), "gsasr_image_metrics")
+    return out
 
 
 # ---- sampled pixels (SURVEY.md 8 row f4) ----------------------------------------------------------------

@@ -48,6 +48,8 @@
 //                        Gaussian-stationary backward with eight Gaussians per wave.
 //   ssim     k_ssim_stats/grad/reduce   the SSIM loss of a stored image against its target and d loss / d image, stored or added
 //                        to the gradient the fused pixel loss wrote (GSASR's cri_ssim; splat_ssim.hip).
+//   metrics  k_metric_stats/reduce   PSNR and SSIM of an 8-bit picture against its 8-bit ground truth, cropped, in RGB or on the Y
+//                        channel (GSASR's val.metrics; splat_metrics.hip).
 //
 // No MFMA: this is gather/scatter-accumulate with one transcendental per pair, not a contraction.
 // This file is the WHOLE library as one translation unit (tools/mb.hip includes it); gsasr_amd/build.py compiles the parts
@@ -62,3 +64,4 @@
 #include "splat_sampled.hip"
 #include "splat_shard.hip"
 #include "splat_ssim.hip"
+#include "splat_metrics.hip"

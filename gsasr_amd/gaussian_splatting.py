@@ -728,6 +728,29 @@ def generate_2D_gaussian_splatting_step_uint8(sr_size, gs_parameters, scale, sca
     return quantise_uint8(image[:, y0:y0 + h, x0:x0 + w], crop, bgr)
 
 
+def generate_2D_gaussian_splatting_step_uint8_metrics(sr_size, gs_parameters, scale, scale_modify, gt, crop_border=0,
+                                                      test_y_channel=False, default_step_size=1.2, mode='scale_modify', if_dmax=True,
+                                                      dmax_mode='fix', dmax=25, crop=None, bgr=False, window=None):
+    """`generate_2D_gaussian_splatting_step_uint8` and the validation metrics of its picture in one call: returns
+    `(picture, metrics)`, the picture being bit for bit what `..._step_uint8` returns with the same arguments and `metrics`
+    float64 `[2]` = {psnr, ssim} of it against `gt` (`gsasr_amd.metrics.image_metrics`: the reference's `calculate_psnr` /
+    `calculate_ssim` with `crop_border` and `test_y_channel`).  `gt`: uint8 `[gt_h, gt_w, 3]` in the byte order `bgr` says, on the
+    parameters' device; it defines `crop` when that is not given (the reference's `[:, :, :gt_h, :gt_w]`) and must have the
+    crop's extent otherwise.  On CUDA tensors the 8-bit forward and gsasr_image_metrics run on the current stream, back to
+    back, and nothing is read on the host: the picture need not leave the device for its metrics to exist."""
+    from .metrics import image_metrics
+    if not (torch.is_tensor(gt) and gt.dtype == torch.uint8 and gt.dim() == 3 and gt.shape[-1] == 3):
+        raise ValueError("gt must be a uint8 tensor [gt_h, gt_w, 3]")
+    if gt.device != gs_parameters.device:
+        raise ValueError(f"gt is on {gt.device}, gs_parameters on {gs_parameters.device}")
+    crop = (int(gt.shape[0]), int(gt.shape[1])) if crop is None else (int(crop[0]), int(crop[1]))
+    if crop != (int(gt.shape[0]), int(gt.shape[1])):
+        raise ValueError(f"Image shapes are different: {crop + (3,)}, {tuple(gt.shape)}.")
+    picture = generate_2D_gaussian_splatting_step_uint8(sr_size, gs_parameters, scale, scale_modify, default_step_size, mode, if_dmax,
+                                                        dmax_mode, dmax, crop, bgr, window)
+    return picture, image_metrics(picture, gt, crop_border, test_y_channel, bgr)
+
+
 def _window(window, H: int, W: int):
     """`window` = (y0, x0, h, w) on the H x W grid, checked: at least 2 x 2 pixels, inside the grid"""
     try:

@@ -469,6 +469,56 @@ typedef struct gsasr_ssim {
 GSASR_API size_t gsasr_ssim_scratch_bytes(const gsasr_ssim *ssim);   /* 0 on bad arguments (the pointers other than grad_img are not looked at) */
 GSASR_API int gsasr_ssim_loss(const gsasr_ssim *ssim, void *stream);
 
+/* Validation metrics of an 8-bit picture (inference / validation: what basicsr/models/gsasr_model.py:483-488 asks of every
+ * validation image -- basicsr/metrics/psnr_ssim.py calculate_psnr (12-48) and calculate_ssim (85-128, 170-198) with crop_border and
+ * test_y_channel (metric_util.py:32-45, color_util.py:38-68)), computed where the 8-bit forward stored the picture.  No float
+ * atomics, no memset, no allocation, no host synchronisation; two calls on the same inputs give the same bits.
+ *
+ *   img, ref   uint8, interleaved [h, w, 3], rows img_pitch / ref_pitch bytes apart (>= 3 * w; any alignment), sample b at
+ *              img + b * img_stride / ref + b * ref_stride bytes: either may be a window of a larger picture.  Bytes outside the
+ *              3 * w_b bytes of a sample's h_b rows are never read
+ *   sample_hw  HOST array [2 * batch] of (h_b, w_b), read during the call: sample b is the top-left h_b x w_b pixels of its
+ *              h x w slot; NULL: every sample is h x w
+ *   crop_border = cb >= 0: both metrics look at rows [cb, h_b - cb) and columns [cb, w_b - cb) only (img[cb:-cb, cb:-cb]; 0: no
+ *              crop), hc x wc pixels
+ *   values     RGB mode: the bytes as numbers 0..255, three channels (their order does not matter).  GSASR_METRIC_Y: one channel,
+ *              with r, g, b the pixel's bytes (in memory r, g, b; with GSASR_METRIC_BGR b, g, r -- as GSASR_U8_SWAP_RB stores):
+ *                x = float32(v) / 255f per channel;  y64 = 24.966 b + 128.553 g + 65.481 r + 16.0 in double (products and sums
+ *                rounded one by one, left to right);  y32 = float32(y64 / 255.0);  Y = float32(y32 * 255f), widened to double
+ *   PSNR       mse = mean over the cropped pixels and the channels of (a - b)^2 -- in RGB mode the sum is an exact integer --,
+ *              psnr = 10 log10(255^2 / mse), +inf when mse == 0
+ *   SSIM       per channel: window g (x) g, g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, i = 0..10 (cv2.getGaussianKernel(11, 1.5);
+ *              applied along rows, then columns), "valid" mode over a, b, a^2, b^2, ab: a (hc - 10) x (wc - 10) map;
+ *              C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, mu1 = g*a, mu2 = g*b, s1 = g*(a^2) - mu1^2, s2 = g*(b^2) - mu2^2,
+ *              s12 = g*(ab) - mu1 mu2,  map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2));
+ *              ssim = mean of the map over its pixels and the channels.  All of it in double
+ *   out        device double [batch][2]: out[2 b] = psnr, out[2 b + 1] = ssim of sample b; a metric that was not asked for
+ *              (flags) is left untouched
+ *   scratch    gsasr_metrics_scratch_bytes(descriptor) bytes, 8-byte aligned: the tiles' partial sums.  Every word that is read
+ *              was written by the same call
+ * GSASR_ERR_ARG before anything is enqueued: a null descriptor, null img / ref / out / scratch, a pitch below 3 * w, batch outside
+ * 1..GSASR_MAX_BATCH, h or w outside 1..32767, a sample larger than h x w, neither GSASR_METRIC_PSNR nor GSASR_METRIC_SSIM, unknown
+ * flag bits, crop_border < 0, hc < 1 or wc < 1, and with GSASR_METRIC_SSIM hc < 11 or wc < 11 (the reference would return the
+ * mean of an empty map). */
+#define GSASR_METRIC_PSNR 1u
+#define GSASR_METRIC_SSIM 2u
+#define GSASR_METRIC_Y 4u     /* test_y_channel: the metrics of the Y channel (one channel) */
+#define GSASR_METRIC_BGR 8u   /* the bytes of a pixel are b, g, r (matters in Y mode only) */
+typedef struct gsasr_metrics {
+    int batch, h, w;      /* the canvas: batch slots of h x w pixels */
+    const int *sample_hw; /* HOST array [2*batch], or NULL */
+    const unsigned char *img;
+    size_t img_pitch, img_stride;   /* bytes between rows / between samples */
+    const unsigned char *ref;
+    size_t ref_pitch, ref_stride;
+    int crop_border;
+    unsigned flags;       /* GSASR_METRIC_* */
+    double *out;          /* device [batch][2] */
+    void *scratch;
+} gsasr_metrics;
+GSASR_API size_t gsasr_metrics_scratch_bytes(const gsasr_metrics *metrics);   /* 0 on bad arguments (img, ref, out and scratch are not looked at) */
+GSASR_API int gsasr_image_metrics(const gsasr_metrics *metrics, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate
