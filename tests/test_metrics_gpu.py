@@ -5,7 +5,8 @@ Bars (tests/test_metrics.py derives them): RGB PSNR 1e-9 relative (the sum of sq
 inputs keep an rms error of at least one level, asserted); SSIM 5e-6 absolute in either mode.  Every case prints its errors.
 Shapes are the smallest at which the part in question can go wrong: full and partial 32 x 32 tiles in both directions, a
 one-pixel map, an error that sits only where no map tile reaches, the largest per-tile integer sums, every residue of the base
-address modulo 4, a padded batch."""
+address modulo 4, a padded batch; then 4 x 5 tiles (interior ones), more items than the reduce kernel has lanes, and batches of
+17 and 64 samples."""
 import math
 import os
 import shutil
@@ -132,6 +133,58 @@ def test_batch_of_three(dev):
             assert torch.equal(got[b], one), (b, y)
             assert torch.equal(got[b], M.image_metrics(ti[b, :h, :w].contiguous(), tr[b, :h, :w].contiguous(), 3, y, False)), (b, y)
             check(got[b].cpu(), cimg[b, :h, :w], cref[b, :h, :w], 3, y, False, f"batch sample {b} y={y}")
+
+
+# ---- more than 2 x 3 tiles, more than one trip of the reduce loop, more than 16 samples ------------------------------------
+@pytest.mark.parametrize("bgr", [False, True], ids=["rgb_bytes", "bgr_bytes"])
+@pytest.mark.parametrize("y", [False, True], ids=["rgb", "y"])
+@pytest.mark.parametrize("cb", [0, 4])
+def test_interior_tiles(dev, cb, y, bgr):
+    """109 x 141: cropped by 4 it is 101 x 133, 4 x 5 tiles, of which 2 x 3 have a neighbour on every side"""
+    img, ref = make_pair(109, 141, seed=20)
+    got = M.image_metrics(torch.from_numpy(img).to(dev), torch.from_numpy(ref).to(dev), cb, y, bgr)
+    check(got.cpu(), img, ref, cb, y, bgr, f"109x141 cb={cb} y={y} bgr={bgr}")
+
+
+@pytest.mark.parametrize("shape,cb,y", [((300, 332), 4, False), ((544, 512), 0, True)], ids=["rgb_330_items", "y_272_items"])
+def test_reduce_second_trip(dev, shape, cb, y):
+    """k_metric_reduce adds a sample's channels x tiles with 256 lanes: 3 x 10 x 11 = 330 and 1 x 17 x 16 = 272 items"""
+    hc, wc, nch = shape[0] - 2 * cb, shape[1] - 2 * cb, 1 if y else 3
+    assert nch * ((hc + 31) // 32) * ((wc + 31) // 32) == (272 if y else 330)
+    img, ref = make_pair(*shape, seed=21)
+    got = M.image_metrics(torch.from_numpy(img).to(dev), torch.from_numpy(ref).to(dev), cb, y, True)
+    check(got.cpu(), img, ref, cb, y, True, f"{shape} cb={cb} y={y}")
+
+
+BIG_BATCH_SIZES = [(96, 112), (17, 17), (33, 45), (21, 112), (96, 20)]
+_BIG_BATCH = {}
+
+
+def big_batch(B):
+    """[B,96,112,3] (3 x 4 tiles), sizes cycling; the padding holds 255 in img and 0 in ref: one leaked pixel moves PSNR by dBs"""
+    if B not in _BIG_BATCH:
+        sizes = [BIG_BATCH_SIZES[b % len(BIG_BATCH_SIZES)] for b in range(B)]
+        cimg, cref = np.full((B, 96, 112, 3), 255, np.uint8), np.zeros((B, 96, 112, 3), np.uint8)
+        for b, (h, w) in enumerate(sizes):
+            cimg[b, :h, :w], cref[b, :h, :w] = make_pair(h, w, seed=30 + b)
+        _BIG_BATCH[B] = (sizes, cimg, cref)
+    return _BIG_BATCH[B]
+
+
+@pytest.mark.parametrize("y", [False, True], ids=["rgb", "y"])
+@pytest.mark.parametrize("B", [17, 64])
+def test_batches_past_sixteen(dev, B, y):
+    """every row of a batch of 17 and of 64 equals the single-sample call on the same view bit for bit, and is within the bars of
+    the float64 restatement"""
+    sizes, cimg, cref = big_batch(B)
+    ti, tr = torch.from_numpy(cimg).to(dev), torch.from_numpy(cref).to(dev)
+    got = M.image_metrics(ti, tr, 3, y, False, sizes=sizes)
+    assert tuple(got.shape) == (B, 2)
+    host = got.cpu()
+    for b, (h, w) in enumerate(sizes):
+        one = M.image_metrics(ti[b, :h, :w], tr[b, :h, :w], 3, y, False)
+        assert torch.equal(got[b], one), (b, y)
+        check(host[b], cimg[b, :h, :w], cref[b, :h, :w], 3, y, False, f"batch of {B} sample {b} y={y}")
 
 
 def test_two_calls_and_one_metric_alone(dev):

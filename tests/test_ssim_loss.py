@@ -26,9 +26,9 @@ from gsasr_amd import ssim as ssim_mod
 from gsasr_amd import ssim_loss
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(11, 11), (12, 27), (37, 53)]
+SHAPES = [(11, 11), (12, 27), (37, 53), (75, 107), (43, 139)]      # the last two: valid maps of 3 x 4 and 2 x 5 tiles of 32 x 32
 BATCH_SIZES = [(11, 16), (24, 40), (17, 11)]      # padded to [3, 3, 24, 40], the target to 29 rows
-KINDS = ("noise", "smooth", "flat")
+KINDS = ("noise", "smooth", "flat", "two-level")
 
 
 def window_f64():
@@ -70,8 +70,9 @@ def ssim_metric_f64(x, y):
 
 
 def make_input(kind, h, w, seed=0):
-    """(x, y) fp32 [3,h,w] of the three kinds the bars were measured on: uniform noise; a smooth sinusoid + 2 % noise; near-flat
-    0.7 + 0.1 % noise"""
+    """(x, y) fp32 [3,h,w] of the kinds the bars were measured on: uniform noise; a smooth sinusoid + 2 % noise; near-flat
+    0.7 + 0.1 % noise; two flat levels, 0.15 left of column w // 2 and 0.85 from it on (the sample's centre pixel is on the bright
+    side, so half the picture is 0.7 away from it), + 0.1 % noise"""
     g = torch.Generator().manual_seed(1000 * seed + 10 * h + w)
     if kind == "noise":
         return torch.rand(3, h, w, generator=g), torch.rand(3, h, w, generator=g)
@@ -79,6 +80,9 @@ def make_input(kind, h, w, seed=0):
         yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
         base = torch.stack([0.5 + 0.4 * torch.sin(0.21 * xx + 0.13 * yy + c) for c in range(3)])
         return (base + 0.02 * torch.randn(3, h, w, generator=g)).clamp(0, 1), (base + 0.02 * torch.randn(3, h, w, generator=g)).clamp(0, 1)
+    if kind == "two-level":
+        level = torch.where(torch.arange(w) < w // 2, 0.15, 0.85).expand(3, h, w)
+        return level + 0.001 * torch.randn(3, h, w, generator=g), level + 0.001 * torch.randn(3, h, w, generator=g)
     return 0.7 + 0.001 * torch.randn(3, h, w, generator=g), 0.7 + 0.001 * torch.randn(3, h, w, generator=g)
 
 
@@ -111,7 +115,8 @@ def test_torch_expression_against_the_oracle(shape, kind):
     _, g64, e_loss, e_grad = fp32_error(x, y, 0.8)
     rel = e_grad / float(g64.abs().max())
     print(f"{kind} {shape}: e32 loss {e_loss:.3e}, gradient {rel:.3e} of max-abs")
-    assert rel <= {"noise": 2e-5, "smooth": 2e-3, "flat": 2e-2}[kind] and e_loss <= 1e-4
+    # (two-level: each half is a near-flat picture and cancels like one, so it is held to the near-flat level)
+    assert rel <= {"noise": 2e-5, "smooth": 2e-3, "flat": 2e-2, "two-level": 2e-2}[kind] and e_loss <= 1e-4
 
 
 def test_the_two_restatements_of_the_reference_agree():

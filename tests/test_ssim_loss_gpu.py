@@ -5,8 +5,12 @@ Oracle and bar are those of tests/test_ssim_loss.py: the float64 restatement of 
 `4 * e32 + 1e-6 * scale`, e32 being the error of the fp32 torch expression against the same oracle on the same input (scale: |L|
 for a loss, the gradient's max-abs for a gradient).  Every check prints the ratio it measured before it asserts.
 
-Shapes: 11 x 11 (one valid pixel), 12 x 27, 37 x 53 (straddles the 32 x 32 tiles in both directions, odd pitch), and a batch of three,
-(11, 16), (24, 40), (17, 11), padded to [3, 3, 24, 40] with a target of 29 rows and a gradient of 26.
+Shapes: 11 x 11 (one valid pixel), 12 x 27, 37 x 53 (straddles the 32 x 32 tiles in both directions, odd pitch), 75 x 107 and
+43 x 139 (3 x 4 and 2 x 5 tiles of the valid map: interior tiles, a second tile row), and a batch of three, (11, 16), (24, 40),
+(17, 11), padded to [3, 3, 24, 40] with a target of 29 rows and a gradient of 26; at the end of the entry-point tests, pictures and
+canvases with more partials than the reduce kernel has lanes and batches of 2 to 64 samples (every split of its 16 waves).
+Inputs: uniform noise, a sinusoid, a near-flat picture, and one with two flat levels 0.7 apart (tests/test_ssim_loss.py).
+profiles/ssim_loss_geometry.txt keeps the figures of one run.
 
 End to end the fused call is compared with what a user composes today on the same GPU: the plain step / batch image, the fp32 torch
 expression of L1 + SSIM and autograd; the gs_parameters gradients under the project's own bars (tests/test_fused_loss_gpu.py)."""
@@ -275,3 +279,94 @@ def test_fused_per_sample_path_and_argument_errors(dev):
                                                       ssim_weight=0.5)
     with pytest.raises(ValueError, match="reduction"):
         gsp.generate_2D_gaussian_splatting_loss((24, 40), p[0], SCALE, (SCALE, SCALE), t[0], reduction="sum", ssim_weight=0.5)
+
+
+# ---- more than 2 x 2 tiles, more than 16 samples, more than one trip of the reduce loops -----------------------------------
+# Until here every picture was at most 37 x 53 (a valid map of 27 x 43: no tile of k_ssim_stats with ty0 > 0, none with a
+# neighbour on all four sides), every canvas one tile, every batch three samples (wps = 4).  SHAPES now holds 75 x 107 (3 x 4
+# tiles of the map, interior ones in both kernels) and 43 x 139 (a second tile row of ONE map row), so the tests above run them
+# with every kind, "two-level" included.  Below: what the shapes alone do not reach.
+def canvas_reference(B, cycle, rows, w, trows, weight=0.8):
+    """a canvas of B samples whose sizes cycle through `cycle`, kinds through KINDS and seeds through 0..4: x [B,3,rows,w] and y
+    [B,3,trows,w] with NaN outside every sample, and per sample (L_b, d L / d x_b, e32 of both) with the 1 / B of the batch mean
+    in the gradient.  One float64 reference per distinct (kind, size, seed, B), shared through _REFS."""
+    sizes = [cycle[b % len(cycle)] for b in range(B)]
+    x, y, per = torch.full((B, 3, rows, w), NAN), torch.full((B, 3, trows, w), NAN), []
+    for b, (h, ww) in enumerate(sizes):
+        kind, seed = KINDS[b % len(KINDS)], b % 5
+        xb, yb = make_input(kind, h, ww, seed=seed)
+        x[b, :, :h, :ww], y[b, :, :h, :ww] = xb, yb
+        key = ("sample", kind, (h, ww), seed, weight, B)
+        if key not in _REFS:
+            _REFS[key] = fp32_error(xb, yb, weight, B)
+        per.append(_REFS[key])
+    return sizes, x, y, per
+
+
+def check_canvas(B, sizes, x, y, per, grows, hwc, dev, what):
+    """the checks of test_entry_point_padded_batch_never_touches_the_padding on any canvas"""
+    from gsasr_amd import _cabi
+    rows, w = x.shape[2], x.shape[3]
+    xd, yd = x.to(dev), y.to(dev)
+    own = torch.zeros(B, 3, grows, w, dtype=torch.bool)
+    for b, (h, ww) in enumerate(sizes):
+        own[b, :, :h, :ww] = True
+    own = (own.permute(0, 2, 3, 1).contiguous() if hwc else own).to(dev)
+    shape = (B, grows, w, 3) if hwc else (B, 3, grows, w)
+    grad = torch.full(shape, NAN, device=dev)
+    before = bits(grad)
+    loss, _ = _cabi.ssim_loss(xd, yd, sizes, 0.8, grad=grad, hwc=hwc)
+    assert tuple(loss.shape) == (1 + B,) and bool(torch.isfinite(loss).all()), what
+    total = sum(p[0] for p in per) / B
+    check(float(loss[0]), total, sum(p[2] for p in per) / B, abs(total), f"{what} loss")
+    # ... and loss[0] is the mean of the per-sample values the call itself returned, formed in double and rounded once
+    assert abs(float(loss[0]) - float(loss[1:].double().mean())) <= 1.2e-7 * abs(total), what
+    assert bool(torch.isfinite(grad[own]).all()) and torch.equal(bits(grad)[~own.cpu()], before[~own.cpu()]), what
+    planar = grad.permute(0, 3, 1, 2) if hwc else grad
+    for b, (h, ww) in enumerate(sizes):
+        L, g64, e_loss, e_grad = per[b]
+        check(float(loss[1 + b]), L, e_loss, abs(L), f"{what} sample {b} {KINDS[b % len(KINDS)]} {h}x{ww} loss")
+        check(planar[b, :, :h, :ww], g64, e_grad, float(g64.abs().max()), f"{what} sample {b} {KINDS[b % len(KINDS)]} {h}x{ww} gradient")
+    buf = torch.where(own, torch.randn(shape, generator=torch.Generator().manual_seed(6)).to(dev) * 1e-3, torch.full(shape, NAN, device=dev))
+    acc = buf.clone()
+    again, _ = _cabi.ssim_loss(xd, yd, sizes, 0.8, grad=acc, hwc=hwc, accumulate=True)
+    assert torch.equal(bits(again), bits(loss)), what
+    assert torch.equal(bits(acc)[~own.cpu()], bits(buf)[~own.cpu()]), what
+    assert bool(((acc[own] - (buf[own] + grad[own])).abs() <= 1.2e-7 * (buf[own].abs() + grad[own].abs())).all()), what
+
+
+def test_reduce_second_trip_of_the_lane_loop_one_sample(dev):
+    """618 x 586: a valid map of 19 x 18 tiles, 3 * 342 = 1026 partials for the 1024 lanes of wps = 16 -- two lanes of
+    k_ssim_reduce take a second trip; and tiles that are interior many times over"""
+    from gsasr_amd import _cabi
+    shape = (618, 586)
+    x, y, L, g64, e_loss, e_grad = reference("smooth", shape)
+    assert 3 * ((shape[0] - 10 + 31) // 32) * ((shape[1] - 10 + 31) // 32) == 1026
+    loss, grad = _cabi.ssim_loss(x.to(dev), y.to(dev), None, 0.8)
+    check(float(loss[0]), L, e_loss, abs(L), f"smooth {shape} loss")
+    check(grad, g64, e_grad, float(g64.abs().max()), f"smooth {shape} planar gradient")
+    only, _ = _cabi.ssim_loss(x.to(dev), y.to(dev), None, 0.8, want_grad=False)
+    assert torch.equal(bits(only), bits(loss))
+
+
+NINE = [(170, 170), (11, 11), (43, 160), (75, 107), (160, 43)]
+
+
+def test_reduce_second_trip_of_the_lane_loop_one_wave_per_sample(dev):
+    """nine samples in [9,3,170,170]: wps = 1, and 3 * 25 = 75 partials per sample for the 64 lanes of its one wave"""
+    sizes, x, y, per = canvas_reference(9, NINE, 170, 170, 170)
+    assert 3 * ((170 - 10 + 31) // 32) ** 2 == 75
+    check_canvas(9, sizes, x, y, per, 170, False, dev, "nine in 170x170")
+
+
+RAGGED = [(75, 107), (11, 11), (11, 107), (75, 11), (43, 80), (33, 65)]
+
+
+@pytest.mark.parametrize("hwc", [False, True], ids=["planar", "interleaved"])
+@pytest.mark.parametrize("B", [2, 5, 9, 17, 64])
+def test_every_wave_split_of_the_reduce_and_padding_tiles(B, hwc, dev):
+    """B = 2, 5, 9, 17, 64 in a [B,3,75,107] canvas (3 x 4 tiles; a target of 80 rows, a gradient of 78): wps = 8, 2, 1, 1, 1, and
+    from B = 17 on the second to fourth trip of `b += 16 / wps`.  Most samples leave whole tiles of the canvas to the padding
+    (the zero partial of k_ssim_stats, the early return of k_ssim_grad); image, target and gradient hold NaN there."""
+    sizes, x, y, per = canvas_reference(B, RAGGED, 75, 107, 80)
+    check_canvas(B, sizes, x, y, per, 78, hwc, dev, f"B={B}")
