@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import gradbars
 from test_bwd_tile import GRAD_RTOL, RASTER, _backward, _check, _synth, _t, per_gaussian_ok
 
 pytestmark = pytest.mark.gpu
@@ -137,14 +138,14 @@ def test_config2_full_size_home_backward_against_oracle(dev):
     full = _backward(s, c, k, g, H, W, 0.1, dev, _home())
     ref = _backward(s, c, k, g, H, W, 0.1, dev, _cabi.FLAG_BWD_GAUSSIAN)
     for a, b, name in zip(full, ref, ("sigmas", "coords", "colors")):
-        per_gaussian_ok(a, b, name, rho=s[:, 2])
+        per_gaussian_ok(a, b, name, rho=s[:, 2], independent=False)
     sig, xy, col, H, W = synthetic.kernel_inputs(128, 128, 4.0, seed=3, gpp=16)
     wgt = synthetic.grad_image(H, W, 4)
     s, c, k, g = sig.numpy(), xy.numpy(), col.numpy(), wgt.numpy()
     full = _backward(s, c, k, g, H, W, 0.1, dev, _home())
     ref = _backward(s, c, k, g, H, W, 0.1, dev, _cabi.FLAG_BWD_GAUSSIAN)
     for a, b, name in zip(full, ref, ("sigmas", "coords", "colors")):
-        per_gaussian_ok(a, b, name, rho=s[:, 2])
+        per_gaussian_ok(a, b, name, rho=s[:, 2], independent=False)
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("GSASR_FUZZ_SEEDS", "12"))))   # more seeds: set the variable
@@ -238,6 +239,7 @@ def test_fused_step_home_backward_through_host_api(dev):
     want = pc.grad.numpy()
     for mode in ("gaussian", "home"):
         per_gaussian_ok(res[mode][1], want, "gs_parameters/" + mode)
+        gradbars.check_raw(res[mode][1], want, p, 1.0, "home step through the host api/" + mode)
 
 
 @pytest.mark.parametrize("gpp", [2, 16], ids=["gpp2", "gpp16"])

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import gradbars
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -30,7 +32,7 @@ def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 
 
-def per_gaussian_ok(got, want, name, rho=None):
+def per_gaussian_ok(got, want, name, rho=None, independent=True, min_share=0.0):
     err = np.abs(got - want)
     assert np.isfinite(got).all(), name
     assert err.max() <= GRAD_RTOL * np.abs(want).max() + 1e-30, (name, float(err.max()), float(np.abs(want).max()))
@@ -42,6 +44,10 @@ def per_gaussian_ok(got, want, name, rho=None):
     tol = rel * np.abs(want).max(axis=1, keepdims=True) + 1e-5 * np.abs(want).max() + 1e-30
     bad = err > tol
     assert not bad.any(), (name, int(np.argwhere(bad)[0][0]), float(err[bad].max()), float(np.abs(want).max()))
+    # every column to its own bar, element by element (tests/gradbars.py), where `want` is an independent truth of a kernel-frame
+    # tensor (the comparisons of two kernels of this build keep the bars above alone)
+    if independent and rho is not None and name in gradbars.KERNEL_GROUPS:
+        gradbars.check(got, want, rho, gradbars.KERNEL_GROUPS[name], min_share, name, [f"{name}{k}" for k in range(want.shape[1])])
 
 
 def _backward(sig, xy, col, wgt, h, w, dmax, dev, flag, cutoff=0.0, rows=None, chw=False, accumulate=False):
@@ -212,6 +218,7 @@ def test_fused_step_planar_backward_through_host_api(dev):
     want = pc.grad.numpy()
     for mode in ("gaussian", "tile"):
         per_gaussian_ok(res[mode][1], want, "gs_parameters/" + mode)
+        gradbars.check_raw(res[mode][1], want, p, 1.0, "planar step through the host api/" + mode)
     # (two plans: the order of the Gaussians inside a cell, hence the forward's summation order, is not fixed)
     assert np.abs(res["gaussian"][0] - res["tile"][0]).max() <= 1e-5
 
@@ -267,7 +274,7 @@ def test_config2_full_size_tile_backward_against_oracle(dev):
     full = _backward(s, c, k, g, H, W, 0.1, dev, _flags()["tile"])
     ref = _backward(s, c, k, g, H, W, 0.1, dev, _flags()["gaussian"])
     for a, b, name in zip(full, ref, ("sigmas", "coords", "colors")):
-        per_gaussian_ok(a, b, name, rho=s[:, 2])
+        per_gaussian_ok(a, b, name, rho=s[:, 2], independent=False)
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("GSASR_FUZZ_SEEDS", "12"))))   # more seeds: set the variable

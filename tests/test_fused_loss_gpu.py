@@ -29,6 +29,7 @@ ROOT = os.path.dirname(HERE)
 for _p in (ROOT, HERE):      # (also run as a script: test_store_is_exact_through_the_fine_forward)
     if _p not in sys.path:
         sys.path.insert(0, _p)
+import gradbars  # noqa: E402
 from test_fused_loss import loss_f64  # noqa: E402
 from test_u8_output_gpu import KERNELS, TAU, box_dmax, kernel_case, raw_parameters, separated  # noqa: E402
 
@@ -224,8 +225,9 @@ def rho_of(p):
     return 0.999999 * np.tanh(p.detach().cpu().numpy().reshape(-1, 9)[:, 2].astype(np.float64))
 
 
-def check_param_grads(got, want, p, what=""):
-    """the project's bars on d/d gs_parameters [.., 9]"""
+def check_param_grads(got, want, p, what="", independent=False, min_share=0.0):
+    """the project's bars on d/d gs_parameters [.., 9]; `independent`: `want` is the float64 truth, not the unfused path of this
+    build -- then every column is held to its own bar as well, element by element (tests/gradbars.py)"""
     g, w = got.detach().cpu().numpy().reshape(-1, 9).astype(np.float64), want.detach().cpu().numpy().reshape(-1, 9).astype(np.float64)
     assert np.isfinite(g).all(), what
     rel = float(np.abs(g - w).max() / max(1e-30, np.abs(w).max()))
@@ -235,6 +237,8 @@ def check_param_grads(got, want, p, what=""):
     print(f"{what}: rel err {rel:.3e} of max-abs {np.abs(w).max():.3e}, rows over their bar {int(bad.any(axis=1).sum())}")
     assert rel <= GRAD_RTOL, (what, rel)
     assert not bad.any(), (what, int(np.argwhere(bad)[0][0]))
+    if independent:
+        gradbars.check(g, w, rho_of(p), gradbars.RAW_GROUPS, min_share, what, list(gradbars.RAW_NAMES))
 
 
 class forced_backward:
@@ -389,7 +393,7 @@ def test_against_the_oracle_end_to_end(kind, bounded, dev):
     value.backward()
     assert float((image.cpu() - v_ref).abs().max()) <= 1e-4                            # the image bar of tests/test_hip_parity.py
     assert abs(float(value.detach()) - want_v) <= 1e-4 * 0.9 + 1e-5 * want_v           # every |d phi| <= |d v| <= 1e-4
-    check_param_grads(pg.grad, q.grad.float(), p, f"oracle {kind}")
+    check_param_grads(pg.grad, q.grad.float(), p, f"oracle {kind}", independent=True, min_share=1.0)
 
 
 # ---- (5) upstream scalar ------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import gradbars
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -65,7 +67,7 @@ def _render(sig, xy, col, h, w, dmax, dev, wgt=None, cutoff=None):
         _cabi.set_default_cutoff(old)
 
 
-def _check(sig, xy, col, h, w, dmax, dev, wgt, cutoff=None, img_atol=IMG_ATOL, grad_rtol=GRAD_RTOL, img_scaled=False):
+def _check(sig, xy, col, h, w, dmax, dev, wgt, cutoff=None, img_atol=IMG_ATOL, grad_rtol=GRAD_RTOL, img_scaled=False, min_share=0.0):
     """img_scaled: the per-pixel bar is 1e-4 * max(1, |ref|) -- for raw-op inputs whose pixel sums reach ~1e2 (fp32 holds
     1e-4 absolute only up to ~1e3 ulp-wise; the north star's 1e-4 is stated for images of O(1) values)"""
     from oracle import gs_oracle
@@ -93,6 +95,8 @@ def _check(sig, xy, col, h, w, dmax, dev, wgt, cutoff=None, img_atol=IMG_ATOL, g
         tol = _row_tol(want, sig)
         bad = np.abs(got - want) > tol
         assert not bad.any(), (name, int(np.argwhere(bad)[0][0]), float(np.abs(got - want)[bad].max()), float(np.abs(want).max()))
+    # ... and every column to its own bar, element by element (tests/gradbars.py); `min_share` of the rows must be in its scope
+    gradbars.check_kernel(grads, gref, sig, min_share, f"_check {h}x{w} dmax {dmax} cutoff {cutoff}")
     return err
 
 
@@ -152,7 +156,7 @@ def _synth(h_lr, w_lr, scale, seed, gpp=1):
 @pytest.mark.parametrize("dmax", [None, 0.5, 0.1], ids=["unbounded", "dmax0.5", "dmax0.1"])
 def test_synthetic_x4_256(dmax, cutoff, dev):
     sig, xy, col, H, W, wgt = _synth(64, 64, 4.0, seed=10)
-    _check(sig, xy, col, H, W, dmax, dev, wgt, cutoff)
+    _check(sig, xy, col, H, W, dmax, dev, wgt, cutoff, min_share=gradbars.SYNTHETIC_SHARE)
 
 
 @pytest.mark.parametrize("case", [(37, 29, 3.0, 1), (24, 40, 2.5, 1), (12, 12, 4.0, 16), (20, 16, 12.0, 1),
@@ -162,14 +166,14 @@ def test_synthetic_ragged_sizes(case, dev):
     h_lr, w_lr, scale, gpp = case
     sig, xy, col, H, W, wgt = _synth(h_lr, w_lr, scale, seed=20, gpp=gpp)
     for dmax in (None, 0.25):
-        _check(sig, xy, col, H, W, dmax, dev, wgt)
+        _check(sig, xy, col, H, W, dmax, dev, wgt, min_share=gradbars.SYNTHETIC_SHARE)
 
 
 def test_training_shape_c5(dev):
     """BASELINE.json config 5 per-sample shape: 48x48 LR x4, 16 Gaussians / LR px, dmax 0.5"""
     sig, xy, col, H, W, wgt = _synth(48, 48, 4.0, seed=30, gpp=16)
     assert (H, W, sig.shape[0]) == (192, 192, 36864)
-    _check(sig, xy, col, H, W, 0.5, dev, wgt)
+    _check(sig, xy, col, H, W, 0.5, dev, wgt, min_share=gradbars.SYNTHETIC_SHARE)
 
 
 def test_large_class_random_sigmas(dev):
@@ -284,6 +288,7 @@ def test_host_api_end_to_end_matches_oracle(dev):
         g = gs_oracle.backward_f64(sig.numpy(), xy.numpy(), col.numpy(), wgt.numpy(), dmax)
         torch.autograd.backward([s2, x2, c2], [torch.from_numpy(a) for a in g])
         assert _relmax(pg.grad.cpu().numpy(), pr.grad.numpy()) <= GRAD_RTOL
+        gradbars.check_raw(pg.grad, pr.grad, p, 1.0, f"host api end to end {kw}")
 
 
 def test_fused_prologue_matches_unfused_torch_path(dev):
@@ -308,6 +313,8 @@ def test_fused_prologue_matches_unfused_torch_path(dev):
     torch.autograd.backward([s2, x2, c2], g)
     gp = _cabi.prologue_backward(p, step, H, W, *g)
     assert float((gp - pr.grad).abs().max()) <= 2e-6 * float(pr.grad.abs().max())
+    for k in range(9):       # ... and every column by its own largest value (the two mean columns are 30-100 times the others)
+        assert float((gp - pr.grad)[:, k].abs().max()) <= 2e-6 * float(pr.grad[:, k].abs().max()), k
     # end to end: fused step vs unfused renderer, forward and gradient w.r.t. the raw parameters
     wgt = synthetic.grad_image(H, W, 66, device=dev).permute(2, 0, 1)
     sm = torch.tensor([scale, scale], device=dev)
@@ -441,7 +448,7 @@ def test_config2_full_size_against_oracle_dmax0p1(dev):
     """config 2: 256x256 LR -> x4 (1024^2), 65 536 Gaussians, fp32 fwd+bwd, per-pixel check (dmax 0.1)"""
     sig, xy, col, H, W, wgt = _synth(256, 256, 4.0, seed=0)
     assert (H, W, sig.shape[0]) == (1024, 1024, 65536)
-    _check(sig, xy, col, H, W, 0.1, dev, wgt)
+    _check(sig, xy, col, H, W, 0.1, dev, wgt, min_share=gradbars.SYNTHETIC_SHARE)
 
 
 def test_config2_properties_all_variants(dev):
@@ -810,6 +817,7 @@ def test_batched_step_against_oracle(dev):
         g = gs_oracle.backward_f64(sig.numpy(), xy.numpy(), col.numpy(), wgts[b].numpy(), dmax)
         torch.autograd.backward([s2, x2, c2], [torch.from_numpy(a) for a in g])
         assert _relmax(pa.grad[b].cpu().numpy(), pr.grad.numpy()) <= GRAD_RTOL
+        gradbars.check_raw(pa.grad[b], pr.grad, pc, 1.0, f"batched step sample {b}")
 
 
 def test_batched_config5_shape(dev):
@@ -913,7 +921,7 @@ def test_forward_pair_kernel_range_against_oracle(dev):
     sig, xy, col, H, W, wgt = _synth(40, 52, 16.0, seed=210)
     assert 4096 <= ((W + 7) // 8) * ((H + 15) // 16) < 8192
     for dmax in (0.05, None):
-        _check(sig, xy, col, H, W, dmax, dev, wgt)
+        _check(sig, xy, col, H, W, dmax, dev, wgt, min_share=gradbars.SYNTHETIC_SHARE)
 
 
 def test_batched_canvas_large_enough_for_the_two_level_forward(dev):
@@ -981,6 +989,7 @@ def test_saturated_rho_per_gaussian_gradients(kernel, dev):
         assert np.isfinite(got).all(), name
         bad = np.abs(got - ref) > _row_tol(ref, sig.numpy())
         assert not bad.any(), (name, int(np.argwhere(bad)[0][0]), float(np.abs(got - ref)[bad].max()))
+    gradbars.check_kernel([t.cpu().numpy() for t in gs], want, sig.numpy(), 0.0, f"saturated rho {kernel}")
 
 
 @pytest.mark.parametrize("shape", [(96, 96), (46, 2845)], ids=["square", "wide"])
@@ -1033,6 +1042,7 @@ def test_raw_op_colours_far_above_one(dmax, dev):
     for got, want, name in zip(grads, gref, ("sigmas", "coords", "colors")):
         assert _relmax(got, want) <= GRAD_RTOL, name
         assert not (np.abs(got - want) > _row_tol(want, sig)).any(), name
+    gradbars.check_kernel(grads, gref, sig, 1.0, f"colours far above one dmax {dmax}")
 
 
 @pytest.mark.parametrize("kernel", ["gaussian", "tile"])

@@ -25,6 +25,7 @@ ROOT = os.path.dirname(HERE)
 for _p in (ROOT, HERE):
     if _p not in sys.path:
         sys.path.insert(0, _p)
+import gradbars  # noqa: E402
 from test_fused_loss import loss_f64  # noqa: E402
 from test_fused_loss_gpu import check_param_grads, conditioned_target, forced_backward, unfused_batch  # noqa: E402
 from test_hip_parity import GRAD_RTOL, IMG_ATOL, _batch_case, _relmax  # noqa: E402
@@ -80,6 +81,31 @@ def sample_reference(b, size, bounded, window=None):
     return _REFS[key]
 
 
+_DEVICE_TRUTH = {}
+
+
+def device_frame_truth(b, p_b, size, sm_b, wgt, dmax, window):
+    """The float64 truth of d sum(wgt * image) / d raw parameters for the per-ELEMENT bars: backward_f64 at the kernel frame that
+    THIS device's fp32 torch makes of the parameters (the reference's own host code, gsp._activate + _to_kernel_frame, which the
+    fused prologue equals bit for bit: test_fused_prologue_matches_unfused_torch_path), then the float64 chain rule of
+    oracle/host_ref.py.  `sample_reference` takes the frame of the CPU's fp32 torch; the two differ by an ulp in some centres, and at
+    the scales here (x1.67 up: standard deviations from 0.3 px) a Gaussian's d / d mean is a cancelling sum over a few pixels that
+    an ulp of its centre moves by 1e-3 of itself (tools/fuzz_host.py) -- measured on sample 13 of the batched windows, row 105
+    (0.72 px, rho -0.90): 8.6e-4 for one ulp of the centre's y, the same 1.9e-3 off the CPU frame's truth in all three kernels.
+    That is the conditioning of the input, which the tensor-level bar never saw and an element's own bar does."""
+    key = (b, size, dmax, window)
+    if key not in _DEVICE_TRUTH:
+        from gsasr_amd import gaussian_splatting as gsp
+        from oracle import gs_oracle, host_ref
+        frame = gsp._to_kernel_frame(*gsp._activate(p_b.detach()), size, 1.2 / sm_b[0])[:3]
+        g = gs_oracle.backward_f64(*(t.cpu().numpy() for t in frame), wgt, dmax)
+        pr = p_b.detach().cpu().double().requires_grad_(True)
+        s2, x2, c2, _ = host_ref.prologue(pr, size, sm_b.detach().cpu().double(), dmax=DMAX, dmax_mode="fix")
+        torch.autograd.backward([s2, x2, c2], [torch.from_numpy(a) for a in g])
+        _DEVICE_TRUTH[key] = pr.grad.numpy()
+    return _DEVICE_TRUTH[key]
+
+
 def render_and_check(dev, sizes, bounded, which=None, windows=None, what=""):
     """the construction of test_batched_step_against_oracle on a canvas of len(sizes) samples: image, padding and raw-parameter
     gradient of sum(out * wgt) of every sample in `which` (default: all) against its own single-image oracle"""
@@ -111,6 +137,10 @@ def render_and_check(dev, sizes, bounded, which=None, windows=None, what=""):
         worst_img, worst_grad = max(worst_img, e_img), max(worst_grad, e_grad)
         assert e_img <= IMG_ATOL, (what, b, e_img)
         assert e_grad <= GRAD_RTOL, (what, b, e_grad)
+        # every column to its own bar (tests/gradbars.py); 120 rows a sample, at most one of them outside its scope (seed 169 has one)
+        truth = device_frame_truth(b, p[b], sizes[b], sms[b], refs[b][1].numpy(), DMAX if bounded else None,
+                                   None if windows is None else windows[b])
+        gradbars.check_raw(grad[b], truth, p[b], 0.99, f"{what} B={B} sample {b}")
     print(f"{what}: B={B}, samples checked {len(list(which))}, image max|err| {worst_img:.3e} (bar {IMG_ATOL:.0e}), "
           f"gradient max rel err {worst_grad:.3e} (bar {GRAD_RTOL:.0e})")
 
@@ -366,6 +396,9 @@ def test_longest_image_against_the_oracle(tall, bounded, dev):
               f"(bar {IMG_ATOL:.0e}), gradient max rel err sigmas {rels[0]:.3e} coords {rels[1]:.3e} colors {rels[2]:.3e} (bar {GRAD_RTOL:.0e})")
         assert e_img <= IMG_ATOL, (kernel, e_img)
         assert max(rels) <= GRAD_RTOL, (kernel, rels)
+        # (element bar only: every other small Gaussian sits on a pixel centre of the only line across that its box keeps, so the
+        # truth's d / d sigma across the short axis is zero but for 3e-5 -- against 1e4 along the long one, in the same rows)
+        gradbars.check_kernel(g, gref, sig, 0.0, f"longest image tall={tall} bounded={bounded} {kernel}", column_bar=False)
 
 
 @pytest.mark.parametrize("rows", [(16300, 16460), (-100, None)], ids=["across_2^14", "last_100_rows"])
@@ -391,6 +424,7 @@ def test_row_band_of_the_tallest_image(rows, dev):
         print(f"tall rows {rows} dmax {dmax}: image max|err| {e_img:.3e} (bar {IMG_ATOL:.0e}), gradient max rel err {max(rels):.3e} "
               f"(bar {GRAD_RTOL:.0e})")
         assert e_img <= IMG_ATOL and max(rels) <= GRAD_RTOL, (dmax, e_img, rels)
+        gradbars.check_kernel(g3, gref, sig, 0.0, f"tall rows {rows} dmax {dmax}")
 
 
 def test_tallest_canvas(dev):
@@ -441,3 +475,5 @@ def test_tallest_canvas(dev):
               f"(all samples, bar 2e-6), image max|err| {e_img:.3e} (bar {IMG_ATOL:.0e}), gradient max rel err {e_grad:.3e} (bar {GRAD_RTOL:.0e})")
         assert e_img <= IMG_ATOL, (b, e_img)
         assert e_grad <= GRAD_RTOL, (b, e_grad)
+        truth = device_frame_truth(b, pa[b], (h, w), sms[b], wgt[b, :, :h].permute(1, 2, 0).contiguous().numpy(), dmax, None)
+        gradbars.check_raw(grad[b], truth, p[b], 1.0, f"tallest canvas sample {b}")

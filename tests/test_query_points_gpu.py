@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import gradbars
+
 pytestmark = pytest.mark.gpu
 
 IMG_ATOL = 1e-4
@@ -82,7 +84,7 @@ def _eval64(sig, xy, col, H, W, dmax, pts, gout=None):
     return out.detach().numpy(), (sig.grad.numpy(), xy.grad.numpy(), col.grad.numpy())
 
 
-def _check(out, grads, want, gwant, tag=""):
+def _check(out, grads, want, gwant, tag="", sig=None, min_share=0.0):
     err = float(np.abs(out - want).max())
     rels = [_relmax(g, w) for g, w in zip(grads, gwant)]
     print(f"{tag}: max |value - reference| = {err:.3e}; gradient rel-max (sigmas, coords, colors) = " + ", ".join(f"{r:.3e}" for r in rels))
@@ -90,6 +92,8 @@ def _check(out, grads, want, gwant, tag=""):
     for g, rel, name in zip(grads, rels, ("sigmas", "coords", "colors")):
         assert np.isfinite(g).all(), (tag, name)
         assert rel <= GRAD_RTOL, (tag, name)
+    if sig is not None:      # every column to its own bar, element by element (tests/gradbars.py)
+        gradbars.check_kernel(grads, gwant, sig, min_share, tag)
 
 
 _ORACLE = {}
@@ -124,7 +128,7 @@ def test_query_against_refined_grid_oracle(m, dmax, cutoff, dev):
     k, gout, want, gwant = _refined_oracle(m, dmax)
     pts = (k.to(torch.float32) / m).to(dev)          # exact in float32
     out, grads = _query(sig, xy, col, H, W, dmax, pts, gout.to(dev), dev, cutoff)
-    _check(out, grads, want, gwant, f"m={m} dmax={dmax} cutoff={cutoff}")
+    _check(out, grads, want, gwant, f"m={m} dmax={dmax} cutoff={cutoff}", sig, gradbars.SYNTHETIC_SHARE)
 
 
 def _domain_points(H, W, n, seed):
@@ -150,7 +154,7 @@ def test_query_irrational_positions(case, dev):
     gout = torch.rand(3, n, generator=torch.Generator().manual_seed(8))
     out, grads = _query(sig, xy, col, H, W, dmax, pts.to(dev), gout.to(dev), dev)
     want, gwant = _eval64(sig, xy, col, H, W, dmax, pts, gout)
-    _check(out, grads, want, gwant, f"{case}")
+    _check(out, grads, want, gwant, f"{case}", sig, gradbars.SYNTHETIC_SHARE)
 
 
 def _with_small_gaussians():
@@ -182,7 +186,7 @@ def test_query_between_the_pixel_centres(dmax, cutoff, dev):
     gout = 0.5 + torch.rand(3, pts.shape[0], generator=torch.Generator().manual_seed(9))
     out, grads = _query(sig, xy, col, H, W, dmax, pts.to(dev), gout.to(dev), dev, cutoff)
     want, gwant = _eval64(sig, xy, col, H, W, dmax, pts, gout)
-    _check(out, grads, want, gwant, f"dmax={dmax} cutoff={cutoff}")
+    _check(out, grads, want, gwant, f"dmax={dmax} cutoff={cutoff}", sig, gradbars.SYNTHETIC_SHARE)
     # the centre is worth the small Gaussian's colour plus the background of the ordinary ones ...
     back = _eval64(sig[:n0], xy[:n0], col[:n0], H, W, dmax, pts[:64])
     assert np.abs(out[:, :64] - (small_col.numpy().T + back)).max() <= IMG_ATOL
@@ -305,6 +309,7 @@ def test_query_large_class_dead_and_invalid_points(dev):
         for got, wnt, name in zip(grads, gwant, ("sigmas", "coords", "colors")):
             assert np.isfinite(got).all(), name
             assert _relmax(got[live], wnt) <= GRAD_RTOL, name
+        gradbars.check_kernel([t[live] for t in grads], gwant, sig[live], 1.0, f"query large class dmax {dmax}")
         assert (grads[0][7] == 0).all() and (grads[2][9] == 0).all()
         # invalid points take no part in the backward: the same gradients without them
         vt = torch.from_numpy(valid)

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import gradbars
+
 pytestmark = pytest.mark.gpu
 
 IMG_ATOL = 1e-4
@@ -77,6 +79,7 @@ def test_sampled_against_oracle(dmax, cutoff, dev):
     for got, wnt, name in zip(grads, gref, ("sigmas", "coords", "colors")):
         assert np.isfinite(got).all(), name
         assert _relmax(got, wnt) <= GRAD_RTOL, name
+    gradbars.check_kernel(grads, gref, s, gradbars.SYNTHETIC_SHARE, f"sampled dmax {dmax} cutoff {cutoff}")
 
 
 @pytest.mark.parametrize("case", [(64, 64, 4.0, 1, 0.1, 2304), (24, 40, 2.5, 1, 0.5, 300), (12, 12, 4.0, 16, 0.5, 144),

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import gradbars
+
 pytestmark = pytest.mark.gpu
 IMG_ATOL = 1e-4
 GRAD_RTOL = 2e-4
@@ -34,7 +36,9 @@ def _row_tol(want, sig):
     return (5e-4 + 5e-6 / np.sqrt(kappa)) * np.abs(want).max(axis=1, keepdims=True) + 1e-5 * np.abs(want).max() + 1e-30
 
 
-def check_grads(got, want, sig, what=""):
+def check_grads(got, want, sig, what="", independent=False, min_share=0.0):
+    """`independent`: `want` is the float64 truth, not another kernel of this build -- then every column is held to its own bar,
+    element by element (tests/gradbars.py), besides the tensor and row bars"""
     for g, w, name in zip(got, want, ("sigmas", "coords", "colors")):
         g, w = np.asarray(g, np.float64), np.asarray(w, np.float64)
         assert np.isfinite(g).all(), name
@@ -43,6 +47,8 @@ def check_grads(got, want, sig, what=""):
         assert rel <= GRAD_RTOL, (what, name, rel)
         bad = np.abs(g - w) > _row_tol(w, sig)
         assert not bad.any(), (what, name, int(np.argwhere(bad)[0][0]), float(np.abs(g - w)[bad].max()), float(np.abs(w).max()))
+    if independent:
+        gradbars.check_kernel(got, want, sig, min_share, what)
 
 
 PALETTE = [(1.3, -0.4, 0.9), (0.35, 1.0, 2.5), (-1.0, 0.6, 1.1), (5.0, 0.08, 0.999), (0.7, 1.7, -0.2), (1.05, 0.2, 0.5)]
@@ -260,7 +266,8 @@ def test_dense_window_against_the_oracle(gpp, op, cutoff, kernel, dev):
     err = float(np.abs(got - ref).max())
     print(f"image max|err| {err:.3e} (largest value {np.abs(ref).max():.3f})")
     assert np.isfinite(got).all() and err <= IMG_ATOL
-    check_grads(gradients(plan, a, b, c, wgt.to(dev)), gref, sig.numpy(), f"{gpp}/{op}/{cutoff}/{kernel}")
+    check_grads(gradients(plan, a, b, c, wgt.to(dev)), gref, sig.numpy(), f"{gpp}/{op}/{cutoff}/{kernel}", independent=True,
+                min_share=gradbars.SYNTHETIC_SHARE)
 
 
 # ---- (7) fused step ------------------------------------------------------------------------------------------------------
@@ -377,6 +384,7 @@ def test_fused_step_view_backward_against_the_oracle(dmax, kernel, dev):
         rel = float(np.abs(have - want).max() / np.abs(want).max())
         print(f"d/d parameters rel err {rel:.3e}")
         assert np.isfinite(have).all() and rel <= GRAD_RTOL
+        gradbars.check_raw(have, want, p, gradbars.SYNTHETIC_SHARE, f"step view {kernel} dmax {dmax} chw {chw}")
     # the 8-bit step on dense input: at most one level off the quantised float window, only within 1e-4 of a rounding boundary
     got8, _ = _cabi.step_forward_u8(pg, None, h, w, dmax, scale_modify=sm.to(dev), view=(H, W, y0, x0))
     assert within_one_level(got8.cpu().numpy(), img.permute(1, 2, 0).cpu().numpy(), 255 * 1e-4)
