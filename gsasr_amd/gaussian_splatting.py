@@ -131,7 +131,13 @@ BACKWARD_KERNEL = "auto"
 
 
 def _backward_kernel(n_pixels: int, n_gaussians: int, shape=None) -> int:
-    """the C flag of the backward kernel the fused entry points plan for (FLAG_BWD_TILE / _GAUSSIAN / _HOME)"""
+    """the C flag of the backward kernel the fused entry points plan for (FLAG_BWD_TILE / _GAUSSIAN / _HOME): the forced one, a
+    choice registered for `shape()`, or the rule.  Measured through this API on MI355X (tools/e2e_modes.py,
+    profiles/history/r02_e2e_modes.txt): with >= 4 HR pixels per Gaussian (one Gaussian per LR pixel at x2 and up) the
+    tile-stationary backward is level or ahead end to end -- it reads the planar gradient in place, where the
+    Gaussian-stationary kernel needs it interleaved first -- and it is deterministic; at 16 Gaussians per LR pixel (the training
+    crops: ~1 pixel per Gaussian) a tile holds thousands of Gaussians and the Gaussian-stationary kernel is 15-50% faster.  Small
+    images have too few tiles to fill the chip."""
     from . import _cabi
     forced = {"tile": _cabi.FLAG_BWD_TILE, "gaussian": _cabi.FLAG_BWD_GAUSSIAN, "home": _cabi.FLAG_BWD_HOME}.get(BACKWARD_KERNEL)
     if forced is not None:
@@ -142,7 +148,7 @@ def _backward_kernel(n_pixels: int, n_gaussians: int, shape=None) -> int:
             for f in (_cabi.FLAG_BWD_TILE, _cabi.FLAG_BWD_GAUSSIAN, _cabi.FLAG_BWD_HOME):
                 if hit[0] & f:
                     return f
-    if _tile_backward(n_pixels, n_gaussians):
+    if n_pixels >= 4 * n_gaussians and n_pixels >= 128 * 1024:
         return _cabi.FLAG_BWD_TILE
     # round 6 (the library's own rule, splat_common.h:bwd_wants_home): denser than one Gaussian per two pixels on at least 1024 tiles
     # of 32 x 16 px -- through this API 1024^2 at 16 per LR pixel -5%, 1280^2 -7%, 1152^2 x3 -17%, a batch of 16 x 256^2 -4%
@@ -150,23 +156,6 @@ def _backward_kernel(n_pixels: int, n_gaussians: int, shape=None) -> int:
     if n_pixels < 2 * n_gaussians and n_pixels >= 1024 * 512:
         return _cabi.FLAG_BWD_HOME
     return _cabi.FLAG_BWD_GAUSSIAN
-
-
-def _tile_backward(n_pixels: int, n_gaussians: int, shape=None) -> bool:
-    """Measured through this API on MI355X (tools/e2e_modes.py, profiles/history/r02_e2e_modes.txt): with >= 4 HR pixels per
-    Gaussian (one Gaussian per LR pixel at x2 and up) the tile-stationary backward is level or ahead end to end -- it reads
-    the planar gradient in place, where the Gaussian-stationary kernel needs it interleaved first -- and it is
-    deterministic; at 16 Gaussians per LR pixel (the training crops: ~1 pixel per Gaussian) a tile holds thousands of
-    Gaussians and the Gaussian-stationary kernel is 15-50% faster.  Small images have too few tiles to fill the chip."""
-    if BACKWARD_KERNEL != "auto":
-        return BACKWARD_KERNEL == "tile"
-    if shape is not None:       # a choice measured and registered for this shape (gsasr_amd/tune.py) goes before the rule
-        from . import _cabi
-        if _cabi.kernel_choices_registered():
-            hit = _cabi.get_kernel_choice(shape())
-            if hit is not None and hit[0] & (_cabi.FLAG_BWD_TILE | _cabi.FLAG_BWD_GAUSSIAN):
-                return bool(hit[0] & _cabi.FLAG_BWD_TILE)
-    return n_pixels >= 4 * n_gaussians and n_pixels >= 128 * 1024
 
 
 def _step_shape(n, H, W, dm):
@@ -177,6 +166,26 @@ def _step_shape(n, H, W, dm):
 def _batch_shape(n_per, sizes, dm):
     from . import _cabi
     return lambda: _cabi.make_batch_dims(n_per, sizes, max(w for _, w in sizes), max(h for h, _ in sizes), dm)
+
+
+def _step_kernel(n, H, W, dm, window=None) -> int:
+    """`_backward_kernel` of a fused step: `n` Gaussians on the H x W grid, or on its `window` = (y0, x0, h, w) -- then for the
+    Gaussians the window can expect, as the library judges a view (no registered choice).  The Python and the C++ node both
+    plan with this flag."""
+    if window is None:
+        return _backward_kernel(H * W, n, _step_shape(n, H, W, dm))
+    h, w = window[2], window[3]
+    live = max(1, n * (h * w) // (H * W))
+    return _backward_kernel(h * w, live)
+
+
+def _canvas_kernel(n_per, B, sizes, dm, views=None) -> int:
+    """`_step_kernel` of a canvas of B samples of `n_per` Gaussians, `sizes[b]` the slot's image or, with `views`, its window"""
+    n_pixels = sum(h * w for h, w in sizes)
+    if views is None:
+        return _backward_kernel(n_pixels, B * n_per, _batch_shape(n_per, sizes, dm))
+    live = max(1, sum(n_per * (h * w) // (v[0] * v[1]) for (h, w), v in zip(sizes, views)))
+    return _backward_kernel(n_pixels, live)
 
 
 # The caller's scale factor as a HINT for the forward kernel (never for the numbers).  The C library sees pixels per Gaussian, which
@@ -196,12 +205,10 @@ def _forward_flag(scale, H: int, W: int) -> int:
 def _plan_flags(needs_grad: bool, kernel) -> int:
     """flags of a fused step's plan: the backward kernel is chosen HERE, explicitly (the library's own default would
     otherwise plan slots for large images that this module then never uses); planar gradient in, forward-only plans
-    for inference.  `kernel`: the C flag from _backward_kernel (or True / False = tile / Gaussian-stationary)"""
+    for inference.  `kernel`: the C flag from _backward_kernel"""
     from . import _cabi
     if not needs_grad:
         return _cabi.FLAG_FORWARD_ONLY
-    if isinstance(kernel, bool):
-        kernel = _cabi.FLAG_BWD_TILE if kernel else _cabi.FLAG_BWD_GAUSSIAN
     return _cabi.FLAG_CHW_GRAD | int(kernel)
 
 
@@ -218,20 +225,13 @@ class _FusedStep(torch.autograd.Function):
     @fp32_boundary_fwd
     def forward(ctx, gs_parameters, step, H, W, dmax, scale_modify=None, default_step=1.2, extra_flags=0, window=None):
         from . import _cabi
-        if window is not None:      # the h x w window at (y0, x0) of the H x W grid (generate_2D_gaussian_splatting_view)
-            y0, x0, h, w = window
-            # (the backward kernel for the Gaussians the window can expect, as the library judges a view; no registered choice)
-            live = max(1, gs_parameters.shape[0] * (h * w) // (H * W))
-            flags = _plan_flags(ctx.needs_input_grad[0], _backward_kernel(h * w, live)) | int(extra_flags)
-            img, plan = _cabi.step_forward(gs_parameters, step, h, w, dmax, flags, scale_modify, default_step, view=(H, W, y0, x0))
-            ctx.save_for_backward(gs_parameters, step)
-            ctx.plan = plan
-            return img
+        # `window`: the h x w window at (y0, x0) of the H x W grid (generate_2D_gaussian_splatting_view)
+        h, w, view = (H, W, None) if window is None else (window[2], window[3], (H, W, window[0], window[1]))
         # the planar gradient autograd hands back goes to the C call as it is (GSASR_FLAG_CHW_GRAD): the
         # tile-stationary backward stages the planes directly, the Gaussian-stationary one behind one interleaving
         # kernel inside the same call -- no torch permute / allocation on the host path either way
-        flags = _plan_flags(ctx.needs_input_grad[0], _backward_kernel(H * W, gs_parameters.shape[0], _step_shape(gs_parameters.shape[0], H, W, dmax))) | int(extra_flags)
-        img, plan = _cabi.step_forward(gs_parameters, step, H, W, dmax, flags, scale_modify, default_step)   # one C call: prologue + plan + splat
+        flags = _plan_flags(ctx.needs_input_grad[0], _step_kernel(gs_parameters.shape[0], H, W, dmax, window)) | int(extra_flags)
+        img, plan = _cabi.step_forward(gs_parameters, step, h, w, dmax, flags, scale_modify, default_step, view=view)   # one C call: prologue + plan + splat
         ctx.save_for_backward(gs_parameters, step)
         ctx.plan = plan
         return img
@@ -371,22 +371,32 @@ def _fused_ok(gs_parameters) -> bool:
         and gs_parameters.shape[1] == 9
 
 
-_STEP_TENSORS = {}      # (value, device) -> [1] float32 device tensor of a python-number step size (read-only)
+_STEP_TENSORS = {}      # (value(s), device, stream) -> float32 device tensor of python-number step sizes (read-only)
+
+
+def _cached_constant(value, dev):
+    """read-only float32 device tensor of python numbers -- a float: `[1]`, a tuple of floats: `[len]` -- made once per DISTINCT
+    value, device and stream (the tensor is filled asynchronously on the stream that first asks for the value); made afresh,
+    and not kept, while that stream is being captured"""
+    capturing = _capturing()
+    key = (value, dev, None if capturing else torch.cuda.current_stream(dev).cuda_stream)
+    t = None if capturing else _STEP_TENSORS.get(key)
+    if t is None:
+        if value.__class__ is float:
+            t = torch.full((1,), value, device=dev, dtype=torch.float32)
+        else:
+            t = torch.tensor(value, dtype=torch.float32, device=dev)
+        if not capturing:
+            if len(_STEP_TENSORS) > 256:
+                _STEP_TENSORS.clear()
+            _STEP_TENSORS[key] = t
+    return t
 
 
 def _step_tensor(step_size, dev):
     if torch.is_tensor(step_size):
         return step_size.detach().to(device=dev, dtype=torch.float32).reshape(1)   # stays on the device: no sync
-    # (keyed by the stream as well: the tensor is filled asynchronously on the stream that first asks for the value)
-    key = (float(step_size), dev, None if _capturing() else torch.cuda.current_stream(dev).cuda_stream)
-    t = _STEP_TENSORS.get(key)
-    if t is None or _capturing():
-        t = torch.full((1,), float(step_size), device=dev, dtype=torch.float32)
-        if not _capturing():
-            if len(_STEP_TENSORS) > 256:
-                _STEP_TENSORS.clear()
-            _STEP_TENSORS[key] = t
-    return t
+    return _cached_constant(float(step_size), dev)
 
 
 class _StepSource:
@@ -398,16 +408,13 @@ class _StepSource:
         self.scale_modify, self.default_step = scale_modify, default_step
 
 
-def _fused_render(gs_parameters, sr_size, step_size, dmax, scale=None):
-    """[3,H,W] through the fused prologue; `step_size` may be a python number, a (GPU) tensor or a `_StepSource`."""
-    H, W = _hw(sr_size)
-    dm = None if dmax is None else float(dmax)
+def _fused_step_args(step_size, dev):
+    """`(step, scale_modify, default_step, watch)` of a fused launch from what `_step_size(..., fused=True)` returned: the
+    caller's device pair and nothing evaluated (`watch`: count the call with `deferred_asserts.watch` AFTER the launch -- a
+    look covers this call's own pair), or the value (a python number or a tensor) as a `[1]` device tensor"""
     if step_size.__class__ is _StepSource:
-        out = _fused_step(gs_parameters.contiguous(), None, H, W, dm, step_size.scale_modify, step_size.default_step, _forward_flag(scale, H, W))
-        deferred_asserts.watch(gs_parameters.device)      # (after the launch: a look covers this call's own pair)
-        return out
-    step = _step_tensor(step_size, gs_parameters.device)
-    return _fused_step(gs_parameters.contiguous(), step, H, W, dm, extra_flags=_forward_flag(scale, H, W))
+        return None, step_size.scale_modify, step_size.default_step, True
+    return _step_tensor(step_size, dev), None, 1.2, False
 
 
 def _fused_step(gs_parameters, step, H, W, dm, scale_modify=None, default_step=1.2, extra_flags=0):
@@ -417,7 +424,7 @@ def _fused_step(gs_parameters, step, H, W, dm, scale_modify=None, default_step=1
     if _cpp_node.load() is None:
         return _FusedStep.apply(gs_parameters, step, H, W, dm, scale_modify, default_step, extra_flags)
     needs_grad = gs_parameters.requires_grad and torch.is_grad_enabled()
-    flags = _plan_flags(needs_grad, _backward_kernel(H * W, gs_parameters.shape[0], _step_shape(gs_parameters.shape[0], H, W, dm))) | int(extra_flags)
+    flags = _plan_flags(needs_grad, _step_kernel(gs_parameters.shape[0], H, W, dm)) | int(extra_flags)
     return _cpp_node.fused_step_apply(gs_parameters, step, H, W, dm, flags, scale_modify, default_step)
 
 
@@ -427,9 +434,8 @@ def _fused_batch(gs_parameters, steps, sizes, dm, scale_modify=None, default_ste
     if _cpp_node.load() is None:
         return _FusedBatch.apply(gs_parameters, steps, sizes, dm, scale_modify, default_step)
     needs_grad = gs_parameters.requires_grad and torch.is_grad_enabled()
-    tile = _backward_kernel(sum(h * w for h, w in sizes), gs_parameters.shape[0] * gs_parameters.shape[1],
-                            _batch_shape(gs_parameters.shape[1], sizes, dm))
-    return _cpp_node.fused_step_apply(gs_parameters, steps, 0, 0, dm, _plan_flags(needs_grad, tile), scale_modify, default_step, sizes=sizes)
+    flags = _plan_flags(needs_grad, _canvas_kernel(gs_parameters.shape[1], gs_parameters.shape[0], sizes, dm))
+    return _cpp_node.fused_step_apply(gs_parameters, steps, 0, 0, dm, flags, scale_modify, default_step, sizes=sizes)
 
 
 def rendering_cuda(sigma_x, sigma_y, rho, coords, colours_with_alpha, sr_size, step_size, device):
@@ -551,6 +557,14 @@ def _resolve_dmax(dmax, dmax_mode, sr_size):
     raise ValueError(f"dmax_mode-{dmax_mode} must be fix or dynamic")
 
 
+def _dmax_arg(dmax, dmax_mode, if_dmax, size):
+    """the `dmax` of the C calls: `_resolve_dmax` on the `size` grid as a float, or None -- the unbounded op -- with `if_dmax` off"""
+    if not if_dmax:
+        return None
+    d = _resolve_dmax(dmax, dmax_mode, size)
+    return None if d is None else float(d)
+
+
 def _sample(final_image, sample_coords):
     """reference :214-216: `stack([img[:, c[0], c[1]] for c in sample_coords], dim=1)` -> `[3, S]`.  An `[S,2]`
     integer tensor (what the datasets produce, continuous_bicubic_downsample_dataset.py:87-88) is gathered with
@@ -575,17 +589,17 @@ def generate_2D_gaussian_splatting_step(sr_size, gs_parameters, scale, scale_mod
     if fused:
         # fused prologue + splat (same maths as the unfused branch below, one kernel instead of ~15)
         H, W = _hw(sr_size)
-        dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, (H, W))
         pts = _as_points(sample_coords) if sample_coords is not None else None
-        if pts is not None and 0 < pts.shape[0] <= SAMPLED_MAX_FRACTION * H * W:
-            dm = None if dmax_eff is None else float(dmax_eff)
-            if step_size.__class__ is _StepSource:
-                out = _FusedStepSampled.apply(gs_parameters.contiguous(), None, H, W, dm, pts, step_size.scale_modify,
-                                              step_size.default_step)
-                deferred_asserts.watch(gs_parameters.device)
-                return out
-            return _FusedStepSampled.apply(gs_parameters.contiguous(), _step_tensor(step_size, gs_parameters.device), H, W, dm, pts)
-        return _sample(_fused_render(gs_parameters, (H, W), step_size, dmax_eff, scale), sample_coords)
+        sampled = pts is not None and 0 < pts.shape[0] <= SAMPLED_MAX_FRACTION * H * W
+        step, sm, default_step, watch = _fused_step_args(step_size, gs_parameters.device)
+        if sampled:
+            out = _FusedStepSampled.apply(gs_parameters.contiguous(), step, H, W, dm, pts, sm, default_step)
+        else:
+            out = _fused_step(gs_parameters.contiguous(), step, H, W, dm, sm, default_step, _forward_flag(scale, H, W))
+        if watch:
+            deferred_asserts.watch(gs_parameters.device)
+        return out if sampled else _sample(out, sample_coords)
     sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
     dev = sigma_x.device
     if cuda_rendering:
@@ -659,19 +673,18 @@ def generate_2D_gaussian_splatting_query(sr_size, gs_parameters, scale, scale_mo
     if gs_parameters.dim() != 2 or gs_parameters.shape[1] != 9:
         raise ValueError("gs_parameters must be [N,9]")
     H, W = _hw(sr_size)
-    dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
-    dm = None if dmax_eff is None else float(dmax_eff)
+    dm = _dmax_arg(dmax, dmax_mode, if_dmax, (H, W))
     fused = cuda_rendering and gs_parameters.is_cuda
     step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=fused)
     if fused:
         if qc.shape[0] == 0:
             empty = gs_parameters.new_zeros((3, 0)) + 0.0 * gs_parameters.sum()
             return empty + (0.0 * qc.sum()).to(empty) if qc.requires_grad else empty      # (a graph to both inputs)
-        if step_size.__class__ is _StepSource:
-            out = _FusedStepQuery.apply(gs_parameters.contiguous(), None, H, W, dm, qc, step_size.scale_modify, step_size.default_step)
+        step, sm, default_step, watch = _fused_step_args(step_size, gs_parameters.device)
+        out = _FusedStepQuery.apply(gs_parameters.contiguous(), step, H, W, dm, qc, sm, default_step)
+        if watch:
             deferred_asserts.watch(gs_parameters.device)
-            return out
-        return _FusedStepQuery.apply(gs_parameters.contiguous(), _step_tensor(step_size, gs_parameters.device), H, W, dm, qc)
+        return out
     sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
     sigmas, xy, col, H, W = _to_kernel_frame(sigma_x, sigma_y, rho, coords, colours_with_alpha, (H, W), step_size)
     return query_dense(sigmas, xy, col, H, W, dm, qc)
@@ -714,14 +727,13 @@ def generate_2D_gaussian_splatting_step_uint8(sr_size, gs_parameters, scale, sca
             raise RuntimeError("generate_2D_gaussian_splatting_step_uint8 needs gs_parameters [N,9] on the GPU (no fallback)")
         from . import _cabi
         step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=True)
-        dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
-        dm = None if dmax_eff is None else float(dmax_eff)
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, (H, W))
         gp, flags = gs_parameters.detach().contiguous(), _forward_flag(scale, h, w)
-        if step_size.__class__ is _StepSource:
-            out, _ = _cabi.step_forward_u8(gp, None, h, w, dm, crop, bgr, None, flags, step_size.scale_modify, step_size.default_step, view)
-            deferred_asserts.watch(gp.device)      # (after the launch: a look covers this call's own pair)
-            return out
-        return _cabi.step_forward_u8(gp, _step_tensor(step_size, gp.device), h, w, dm, crop, bgr, None, flags, view=view)[0]
+        step, sm, default_step, watch = _fused_step_args(step_size, gp.device)
+        out, _ = _cabi.step_forward_u8(gp, step, h, w, dm, crop, bgr, None, flags, sm, default_step, view)
+        if watch:
+            deferred_asserts.watch(gp.device)
+        return out
     step_size = _step_size(scale, scale_modify, default_step_size, mode)
     sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
     image = rendering_python(sigma_x, sigma_y, rho, coords, colours_with_alpha, sr_size, step_size, device=sigma_x.device)
@@ -782,15 +794,14 @@ def generate_2D_gaussian_splatting_view(sr_size, gs_parameters, scale, scale_mod
         sigma_x, sigma_y, rho, coords, colours_with_alpha = _activate(gs_parameters)
         image = rendering_python(sigma_x, sigma_y, rho, coords, colours_with_alpha, sr_size, step_size, device=sigma_x.device)
         return image[:, y0:y0 + h, x0:x0 + w]
-    dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
-    dm = None if dmax_eff is None else float(dmax_eff)
-    gp, win = gs_parameters.contiguous(), (y0, x0, h, w)
+    dm = _dmax_arg(dmax, dmax_mode, if_dmax, (H, W))
+    gp = gs_parameters.contiguous()
+    step, sm, default_step, watch = _fused_step_args(step_size, gp.device)
     # (the scale hint of the forward kernel reads the window's size: that is the image the kernels render)
-    if step_size.__class__ is _StepSource:
-        out = _FusedStep.apply(gp, None, H, W, dm, step_size.scale_modify, step_size.default_step, _forward_flag(scale, h, w), win)
-        deferred_asserts.watch(gp.device)      # (after the launch: a look covers this call's own pair)
-        return out
-    return _FusedStep.apply(gp, _step_tensor(step_size, gp.device), H, W, dm, None, 1.2, _forward_flag(scale, h, w), win)
+    out = _FusedStep.apply(gp, step, H, W, dm, sm, default_step, _forward_flag(scale, h, w), (y0, x0, h, w))
+    if watch:
+        deferred_asserts.watch(gp.device)
+    return out
 
 
 class _FusedBatch(torch.autograd.Function):
@@ -805,15 +816,7 @@ class _FusedBatch(torch.autograd.Function):
     @fp32_boundary_fwd
     def forward(ctx, gs_parameters, steps, sizes, dmax, scale_modify=None, default_step=1.2, views=None):
         from . import _cabi
-        if views is not None:
-            # (the backward kernel for the Gaussians the windows can expect, as the library judges views; no registered choice)
-            n_per = gs_parameters.shape[1]
-            live = max(1, sum(n_per * (h * w) // (v[0] * v[1]) for (h, w), v in zip(sizes, views)))
-            tile = _backward_kernel(sum(h * w for h, w in sizes), live)
-        else:
-            tile = _backward_kernel(sum(h * w for h, w in sizes), gs_parameters.shape[0] * gs_parameters.shape[1],
-                                    _batch_shape(gs_parameters.shape[1], sizes, dmax))
-        flags = _plan_flags(ctx.needs_input_grad[0], tile)
+        flags = _plan_flags(ctx.needs_input_grad[0], _canvas_kernel(gs_parameters.shape[1], gs_parameters.shape[0], sizes, dmax, views))
         img, plan = _cabi.batch_forward(gs_parameters, steps, sizes, dmax, flags, scale_modify, default_step, views=views)
         ctx.save_for_backward(gs_parameters, steps)
         ctx.plan = plan
@@ -838,15 +841,7 @@ def _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev):
         if all(torch.is_tensor(v) for v in vals):
             return torch.stack([v.reshape(()) for v in vals]).to(device=dev, dtype=torch.float32)
         # python numbers: one host-to-device copy per DISTINCT tuple of values, not per call
-        key = (tuple(float(v) for v in vals), dev, None if _capturing() else torch.cuda.current_stream(dev).cuda_stream)
-        t = _STEP_TENSORS.get(key)
-        if t is None or _capturing():
-            t = torch.tensor(key[0], dtype=torch.float32, device=dev)
-            if not _capturing():
-                if len(_STEP_TENSORS) > 256:
-                    _STEP_TENSORS.clear()
-                _STEP_TENSORS[key] = t
-        return t
+        return _cached_constant(tuple(float(v) for v in vals), dev)
     if mode == 'scale':
         final = col(list(scales))
     elif mode == 'scale_modify':
@@ -872,6 +867,42 @@ def max_canvas_batch(h_max: int) -> int:
     return max(1, min(64, 32767 // slot))
 
 
+def _batch_sizes(sr_sizes):
+    """`sr_sizes` as [(H_b, W_b)] ints; the [B,2] GPU tensor of gsasr_model.py:147 with ONE copy to the host"""
+    if torch.is_tensor(sr_sizes) and sr_sizes.dim() == 2:
+        return [(int(r[0]), int(r[1])) for r in sr_sizes.tolist()]
+    return [_hw(s) for s in sr_sizes]
+
+
+def _one_canvas(gs_parameters, cap, uniform_dmax) -> bool:
+    """does ONE batched canvas of at most `cap` slots apply: 2 or more samples `[B,N,9]` on the GPU, one dmax for all of them"""
+    return 1 < gs_parameters.shape[0] <= cap and gs_parameters.is_cuda and gs_parameters.dim() == 3 and gs_parameters.shape[2] == 9 \
+        and uniform_dmax
+
+
+def _batch_sm_source(scale_modifies, dev):
+    """the `[B,2]` device tensor of scale_modify pairs the plan's first kernel can read itself, or None.  A [B,2] tensor is read
+    in place as rows of stride >= 2 on the Gaussians' device: an `.expand(B, 2)` view -- row stride 0 -- or a tensor on another
+    GPU is evaluated instead"""
+    if torch.is_tensor(scale_modifies) and scale_modifies.dim() == 2 and _sm_source_ok(scale_modifies[0]) \
+            and scale_modifies.stride(0) >= 2 and scale_modifies.device == dev:
+        return scale_modifies
+    if not torch.is_tensor(scale_modifies) and all(_sm_source_ok(v) and v.device == dev for v in scale_modifies):
+        return torch.stack([v[:2] for v in scale_modifies])
+    return None
+
+
+def _canvas_step_args(scales, scale_modifies, default_step_size, mode, dev, source=True):
+    """`_fused_step_args` of a canvas, `(steps, scale_modify, default_step, watch)`: scale_modify pairs that are already on the
+    device go to the plan's first kernel as they are (one [B,2] tensor: no kernel at all; a list of [2] tensors: one
+    torch.stack) -- no division, comparison or copy here --, anything else as the `[B]` tensor of `_batch_step_sizes`.
+    `source=False`: the launch takes no `scale_modify` (the sampled and query canvases), the steps are evaluated"""
+    sm = _batch_sm_source(scale_modifies, dev) if source and mode == 'scale_modify' else None
+    if sm is not None:
+        return None, sm, float(default_step_size), True
+    return _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev), None, 1.2, False
+
+
 def _batch_windows(sizes, gs_parameters, scales, scale_modifies, windows, default_step_size, mode, if_dmax, dmax_mode, dmax,
                    uniform_dmax):
     """`generate_2D_gaussian_splatting_batch(windows=...)`: one canvas whose slots are the windows, each on its own full grid
@@ -881,27 +912,16 @@ def _batch_windows(sizes, gs_parameters, scales, scale_modifies, windows, defaul
         raise ValueError("one window per sample")
     wins = [_window(windows[b], *sizes[b]) for b in range(B)]
     h_max, w_max = max(w[2] for w in wins), max(w[3] for w in wins)
-    if 1 < B <= max_canvas_batch(h_max) and gs_parameters.is_cuda and gs_parameters.dim() == 3 and gs_parameters.shape[2] == 9 \
-            and uniform_dmax:
+    if _one_canvas(gs_parameters, max_canvas_batch(h_max), uniform_dmax):
         dev = gs_parameters.device
-        dmax_eff = _resolve_dmax(dmax, dmax_mode, sizes[0]) if if_dmax else None
-        dm = None if dmax_eff is None else float(dmax_eff)
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, sizes[0])
         wsizes = tuple((w[2], w[3]) for w in wins)
         views = tuple((H, W, w[0], w[1]) for (H, W), w in zip(sizes, wins))
-        gp = gs_parameters.contiguous()
-        if mode == 'scale_modify':      # (device pairs go to the plan's first kernel as they are: the plain batch's rule)
-            sm = None
-            if torch.is_tensor(scale_modifies) and scale_modifies.dim() == 2 and _sm_source_ok(scale_modifies[0]) \
-                    and scale_modifies.stride(0) >= 2 and scale_modifies.device == dev:
-                sm = scale_modifies
-            elif not torch.is_tensor(scale_modifies) and all(_sm_source_ok(v) and v.device == dev for v in scale_modifies):
-                sm = torch.stack([v[:2] for v in scale_modifies])
-            if sm is not None:
-                out = _FusedBatch.apply(gp, None, wsizes, dm, sm, float(default_step_size), views)
-                deferred_asserts.watch(dev)
-                return out
-        steps = _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev)
-        return _FusedBatch.apply(gp, steps, wsizes, dm, None, 1.2, views)
+        steps, sm, default_step, watch = _canvas_step_args(scales, scale_modifies, default_step_size, mode, dev)
+        out = _FusedBatch.apply(gs_parameters.contiguous(), steps, wsizes, dm, sm, default_step, views)
+        if watch:
+            deferred_asserts.watch(dev)
+        return out
     # per-sample path (a single sample, more samples than a canvas holds, a per-sample dmax, CPU tensors)
     outs = []
     for b in range(B):
@@ -938,10 +958,7 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
         query_coords = _as_query(query_coords, batched=True, coords_grad=coords_grad)
         if query_coords.shape[0] != B:
             raise ValueError("query_coords must be [B,S,2]")
-    if torch.is_tensor(sr_sizes) and sr_sizes.dim() == 2:      # e.g. the [B,2] GPU tensor of gsasr_model.py:147: ONE copy to the host
-        sizes = [(int(r[0]), int(r[1])) for r in sr_sizes.tolist()]
-    else:
-        sizes = [_hw(s) for s in sr_sizes]
+    sizes = _batch_sizes(sr_sizes)
     if not (len(sizes) == B == len(scales) == len(scale_modifies)):
         raise ValueError("one sr_size, scale and scale_modify per sample")
     if gs_parameters.dtype != torch.float32:
@@ -963,30 +980,19 @@ def generate_2D_gaussian_splatting_batch(sr_sizes, gs_parameters, scales, scale_
             h_max, w_max = max(h for h, _ in sizes), max(w for _, w in sizes)
             parts = [F.pad(o, (0, w_max - o.shape[3], 0, h_max - o.shape[2])) for o in parts]
         return torch.cat(parts)
-    if 1 < B <= cap and gs_parameters.is_cuda and gs_parameters.dim() == 3 and gs_parameters.shape[2] == 9 and uniform_dmax:
+    if _one_canvas(gs_parameters, cap, uniform_dmax):
         dev = gs_parameters.device
-        dmax_eff = _resolve_dmax(dmax, dmax_mode, sizes[0]) if if_dmax else None
-        dm = None if dmax_eff is None else float(dmax_eff)
-        if sample_coords is None and query_coords is None and mode == 'scale_modify':
-            # scale_modify pairs that are already on the device go to the plan's first kernel as they are (one [B,2]
-            # tensor: no kernel at all; a list of [2] tensors: one torch.stack): no division, comparison or copy here
-            sm = None
-            # (a [B,2] tensor is read in place as rows of stride >= 2 on the Gaussians' device: an `.expand(B, 2)` view --
-            # row stride 0 -- or a tensor on another GPU takes the evaluated path below)
-            if torch.is_tensor(scale_modifies) and scale_modifies.dim() == 2 and _sm_source_ok(scale_modifies[0]) \
-                    and scale_modifies.stride(0) >= 2 and scale_modifies.device == dev:
-                sm = scale_modifies
-            elif not torch.is_tensor(scale_modifies) and all(_sm_source_ok(v) and v.device == dev for v in scale_modifies):
-                sm = torch.stack([v[:2] for v in scale_modifies])
-            if sm is not None:
-                out = _fused_batch(gs_parameters.contiguous(), None, tuple(sizes), dm, sm, float(default_step_size))
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, sizes[0])
+        # (only the plain image launch takes the device pairs: the sampled and query canvases evaluate the steps)
+        plain = sample_coords is None and query_coords is None
+        steps, sm, default_step, watch = _canvas_step_args(scales, scale_modifies, default_step_size, mode, dev, source=plain)
+        if plain:
+            out = _fused_batch(gs_parameters.contiguous(), steps, tuple(sizes), dm, sm, default_step)
+            if watch:
                 deferred_asserts.watch(dev)
-                return out
-        steps = _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev)
+            return out
         if query_coords is not None and query_coords.shape[1] > 0:
             return _FusedBatchQuery.apply(gs_parameters.contiguous(), steps, tuple(sizes), dm, query_coords)
-        if sample_coords is None and query_coords is None:
-            return _fused_batch(gs_parameters.contiguous(), steps, tuple(sizes), dm)
         pts = None if sample_coords is None else sample_coords if torch.is_tensor(sample_coords) else torch.as_tensor(sample_coords)
         if pts is not None and pts.dim() == 3 and pts.shape[0] == B and pts.shape[2] == 2 and not pts.dtype.is_floating_point \
                 and 0 < pts.shape[1] <= SAMPLED_MAX_FRACTION * min(h * w for h, w in sizes):
@@ -1079,9 +1085,24 @@ def _add_ssim(loss, grad, img, plan, target, sizes, ssim_weight):
     return loss[0] + sl[0], loss[1:] + sl[1:], loss[0], sl[0]
 
 
+def _loss_outputs(ctx, loss, grad, img, plan, target, sizes, ssim_weight, want_image):
+    """the outputs of the two loss Functions, always `(total, per-sample totals, l_pix, l_ssim, img)`: the two terms are None
+    without the SSIM term and `img` is None unless `want_image`; all but the total are non-differentiable"""
+    if ssim_weight != 0.0:
+        total, per, l_pix, l_ssim = _add_ssim(loss, grad, img, plan, target, sizes, ssim_weight)
+    else:
+        total, per, l_pix, l_ssim = loss[0], loss[1:], None, None
+    if not want_image:
+        img = None
+    elif sizes is not None:
+        img = img[:, :, : max(h for h, _ in sizes)]          # the slot is h_max rounded up to whole 16-row tiles
+    ctx.mark_non_differentiable(*(t for t in (per, l_pix, l_ssim, img) if t is not None))
+    return total, per, l_pix, l_ssim, img
+
+
 class _FusedStepLoss(torch.autograd.Function):
-    """`_FusedStep` ending in the fused pixel loss: raw `gs_parameters[N,9]` and `target[3,h,w]` -> (L, `[1]` per-sample loss,
-    and with `want_image` the image), the image gradient kept in `ctx` for the existing backward."""
+    """`_FusedStep` ending in the fused pixel loss: raw `gs_parameters[N,9]` and `target[3,h,w]` -> `_loss_outputs` (`[1]`
+    per-sample loss), the image gradient kept in `ctx` for the existing backward."""
 
     @staticmethod
     @fp32_boundary_fwd
@@ -1089,28 +1110,13 @@ class _FusedStepLoss(torch.autograd.Function):
                 want_image, needs_grad, ssim_weight):
         from . import _cabi
         # (needs_grad: requires_grad AND grad mode, from the caller -- a Function's forward always runs with grad mode off)
-        if window is not None:
-            y0, x0, h, w = window
-            live = max(1, gs_parameters.shape[0] * (h * w) // (H * W))
-            flags = _loss_plan_flags(needs_grad, _backward_kernel(h * w, live)) | int(extra_flags)
-            view = (H, W, y0, x0)
-        else:
-            h, w, view = H, W, None
-            flags = _loss_plan_flags(needs_grad, _backward_kernel(H * W, gs_parameters.shape[0], _step_shape(gs_parameters.shape[0], H, W, dmax))) | int(extra_flags)
+        h, w, view = (H, W, None) if window is None else (window[2], window[3], (H, W, window[0], window[1]))
+        flags = _loss_plan_flags(needs_grad, _step_kernel(gs_parameters.shape[0], H, W, dmax, window)) | int(extra_flags)
         loss, grad, img, plan = _cabi.step_forward_loss(gs_parameters, step, h, w, dmax, target, kind, norm, weight, eps, flags,
                                                         scale_modify, default_step, view, want_image or ssim_weight != 0.0)
         ctx.save_for_backward(gs_parameters, step)
         ctx.plan, ctx.grad = plan, grad
-        if ssim_weight != 0.0:      # (total, per, l_pix, l_ssim[, img])
-            out = _add_ssim(loss, grad, img, plan, target, None, ssim_weight) + ((img,) if want_image else ())
-            ctx.mark_non_differentiable(*out[1:])
-            return out
-        total, per = loss[0], loss[1:]
-        if want_image:
-            ctx.mark_non_differentiable(per, img)
-            return total, per, img
-        ctx.mark_non_differentiable(per)
-        return total, per
+        return _loss_outputs(ctx, loss, grad, img, plan, target, None, ssim_weight, want_image)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -1121,37 +1127,19 @@ class _FusedStepLoss(torch.autograd.Function):
 
 class _FusedBatchLoss(torch.autograd.Function):
     """`_FusedBatch` ending in the fused pixel loss: `gs_parameters[B,N,9]` and `target[B,3,rows,w_max]` (read in place) ->
-    (L, `[B]` per-sample losses, and with `want_image` the images `[B,3,h_max,w_max]`)."""
+    `_loss_outputs` (`[B]` per-sample losses, with `want_image` the images `[B,3,h_max,w_max]`)."""
 
     @staticmethod
     @fp32_boundary_fwd
     def forward(ctx, gs_parameters, steps, target, sizes, dmax, scale_modify, default_step, views, kind, norm, weight, eps, want_image,
                 needs_grad, ssim_weight):
         from . import _cabi
-        if views is not None:
-            n_per = gs_parameters.shape[1]
-            live = max(1, sum(n_per * (h * w) // (v[0] * v[1]) for (h, w), v in zip(sizes, views)))
-            kernel = _backward_kernel(sum(h * w for h, w in sizes), live)
-        else:
-            kernel = _backward_kernel(sum(h * w for h, w in sizes), gs_parameters.shape[0] * gs_parameters.shape[1],
-                                      _batch_shape(gs_parameters.shape[1], sizes, dmax))
-        flags = _loss_plan_flags(needs_grad, kernel)
+        flags = _loss_plan_flags(needs_grad, _canvas_kernel(gs_parameters.shape[1], gs_parameters.shape[0], sizes, dmax, views))
         loss, grad, img, plan = _cabi.batch_forward_loss(gs_parameters, steps, sizes, dmax, target, kind, norm, weight, eps, flags,
                                                          scale_modify, default_step, views, want_image or ssim_weight != 0.0)
         ctx.save_for_backward(gs_parameters, steps)
         ctx.plan, ctx.grad = plan, grad
-        if ssim_weight != 0.0:      # (total, per, l_pix, l_ssim[, img])
-            out = _add_ssim(loss, grad, img, plan, target, sizes, ssim_weight)
-            out += (img[:, :, : max(h for h, _ in sizes)],) if want_image else ()
-            ctx.mark_non_differentiable(*out[1:])
-            return out
-        total, per = loss[0], loss[1:]
-        if want_image:
-            img = img[:, :, : max(h for h, _ in sizes)]
-            ctx.mark_non_differentiable(per, img)
-            return total, per, img
-        ctx.mark_non_differentiable(per)
-        return total, per
+        return _loss_outputs(ctx, loss, grad, img, plan, target, sizes, ssim_weight, want_image)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -1213,29 +1201,17 @@ def generate_2D_gaussian_splatting_loss(sr_size, gs_parameters, scale, scale_mod
     if not _fused_ok(gs_parameters):
         raise RuntimeError("generate_2D_gaussian_splatting_loss needs gs_parameters [N,9] on the GPU (no fallback)")
     step_size = _step_size(scale, scale_modify, default_step_size, mode, fused=True)
-    dmax_eff = _resolve_dmax(dmax, dmax_mode, (H, W)) if if_dmax else None
-    dm = None if dmax_eff is None else float(dmax_eff)
-    gp, hint = gs_parameters.contiguous(), _forward_flag(scale, h, w)
-    tail = (kind, norm, float(loss_weight), float(eps), bool(return_image), gp.requires_grad and torch.is_grad_enabled(), ssim_weight)
-    if step_size.__class__ is _StepSource:
-        out = _FusedStepLoss.apply(gp, None, target, H, W, dm, step_size.scale_modify, step_size.default_step, hint, win, *tail)
+    dm = _dmax_arg(dmax, dmax_mode, if_dmax, (H, W))
+    gp = gs_parameters.contiguous()
+    step, sm, default_step, watch = _fused_step_args(step_size, gp.device)
+    total, _, l_pix, l_ssim, image = _FusedStepLoss.apply(
+        gp, step, target, H, W, dm, sm, default_step, _forward_flag(scale, h, w), win, kind, norm, float(loss_weight), float(eps),
+        bool(return_image), gp.requires_grad and torch.is_grad_enabled(), ssim_weight)
+    if watch:
         deferred_asserts.watch(gp.device)
-    else:
-        out = _FusedStepLoss.apply(gp, _step_tensor(step_size, gp.device), target, H, W, dm, None, 1.2, hint, win, *tail)
-    if ssim_weight != 0.0:
-        return _loss_returns(out[0], out[4] if return_image else None, (out[2], out[3]) if return_terms else None)
-    terms = (out[0].detach(), torch.zeros_like(out[0])) if return_terms else None
-    return _loss_returns(out[0], out[2] if return_image else None, terms)
-
-
-def _batch_sm_source(scale_modifies, dev):
-    """the `[B,2]` device tensor of scale_modify pairs the plan's first kernel can read itself, or None"""
-    if torch.is_tensor(scale_modifies) and scale_modifies.dim() == 2 and _sm_source_ok(scale_modifies[0]) \
-            and scale_modifies.stride(0) >= 2 and scale_modifies.device == dev:
-        return scale_modifies
-    if not torch.is_tensor(scale_modifies) and all(_sm_source_ok(v) and v.device == dev for v in scale_modifies):
-        return torch.stack([v[:2] for v in scale_modifies])
-    return None
+    if return_terms and ssim_weight == 0.0:
+        l_pix, l_ssim = total.detach(), torch.zeros_like(total)
+    return _loss_returns(total, image, (l_pix, l_ssim) if return_terms else None)
 
 
 def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, scale_modifies, targets, loss='l1', loss_weight=1.0,
@@ -1260,10 +1236,7 @@ def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, s
         raise ValueError(f"eps-{eps} must be >= 0")
     ssim_weight = _ssim_weight(ssim_weight, reduction)
     B = gs_parameters.shape[0]
-    if torch.is_tensor(sr_sizes) and sr_sizes.dim() == 2:
-        sizes = [(int(r[0]), int(r[1])) for r in sr_sizes.tolist()]
-    else:
-        sizes = [_hw(s) for s in sr_sizes]
+    sizes = _batch_sizes(sr_sizes)
     if not (len(sizes) == B == len(scales) == len(scale_modifies)):
         raise ValueError("one sr_size, scale and scale_modify per sample")
     if windows is not None and len(windows) != B:
@@ -1287,25 +1260,19 @@ def generate_2D_gaussian_splatting_batch_loss(sr_sizes, gs_parameters, scales, s
         targets = torch.stack([F.pad(t, (0, w_max - t.shape[2], 0, h_max - t.shape[1])) for t in parts])
     uniform_dmax = (not if_dmax) or dmax_mode == 'fix' or len(set(sizes)) == 1
     cap = max_canvas_batch(h_max)
-    if 1 < B <= cap and gs_parameters.is_cuda and gs_parameters.dim() == 3 and gs_parameters.shape[2] == 9 and uniform_dmax:
-        dmax_eff = _resolve_dmax(dmax, dmax_mode, sizes[0]) if if_dmax else None
-        dm = None if dmax_eff is None else float(dmax_eff)
+    if _one_canvas(gs_parameters, cap, uniform_dmax):
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, sizes[0])
         views = None if wins is None else tuple((H, W, w[0], w[1]) for (H, W), w in zip(sizes, wins))
         gp = gs_parameters.contiguous()
-        tail = (kind, norm, float(loss_weight), float(eps), bool(return_images), gp.requires_grad and torch.is_grad_enabled(),
-                ssim_weight)
-        sm = _batch_sm_source(scale_modifies, dev) if mode == 'scale_modify' else None
-        if sm is not None:
-            out = _FusedBatchLoss.apply(gp, None, targets, wsizes, dm, sm, float(default_step_size), views, *tail)
+        steps, sm, default_step, watch = _canvas_step_args(scales, scale_modifies, default_step_size, mode, dev)
+        total, per, l_pix, l_ssim, images = _FusedBatchLoss.apply(
+            gp, steps, targets, wsizes, dm, sm, default_step, views, kind, norm, float(loss_weight), float(eps), bool(return_images),
+            gp.requires_grad and torch.is_grad_enabled(), ssim_weight)
+        if watch:
             deferred_asserts.watch(dev)
-        else:
-            steps = _batch_step_sizes(scales, scale_modifies, default_step_size, mode, dev)
-            out = _FusedBatchLoss.apply(gp, steps, targets, wsizes, dm, None, 1.2, views, *tail)
-        if ssim_weight != 0.0:
-            total, per, terms, images = out[0], out[1], (out[2], out[3]), (out[4] if return_images else None)
-        else:
-            total, per, images = out[0], out[1], (out[2] if return_images else None)
-            terms = (total.detach(), torch.zeros_like(total)) if return_terms else None
+        if return_terms and ssim_weight == 0.0:
+            l_pix, l_ssim = total.detach(), torch.zeros_like(total)
+        terms = (l_pix, l_ssim)
     else:
         # per-sample path (a single sample, more samples than a canvas holds, a per-sample dmax, CPU tensors): the same value
         vals, imgs, pix, ssm = [], [], [], []

@@ -20,7 +20,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from .gaussian_splatting import (_batch_step_sizes, _resolve_dmax, generate_2D_gaussian_splatting_batch,
+from .gaussian_splatting import (_batch_step_sizes, _dmax_arg, generate_2D_gaussian_splatting_batch,
                                  generate_2D_gaussian_splatting_step, generate_2D_gaussian_splatting_step_uint8, max_canvas_batch,
                                  quantise_uint8)
 
@@ -99,7 +99,7 @@ def _joined_tiles(lq_pad, nh, nw, stride, split_size, size_sr, stride_sr, scale_
     dm = None
     if on_gpu:
         from . import _cabi
-        dm = float(_resolve_dmax(dmax, dmax_mode, (size_sr, size_sr))) if if_dmax else None
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, (size_sr, size_sr))
     for group in _tile_groups(nh * nw, tile_batch, max_canvas_batch(size_sr)):
         params = []
         for k in group:
@@ -159,7 +159,7 @@ def _tiles_uint8(params, size_sr, scale_factor, scale_modify, default_step_size,
     if cuda_rendering and params and params[0].is_cuda:
         from . import _cabi
         per_canvas = max_canvas_batch(size_sr)
-        dm = float(_resolve_dmax(dmax, dmax_mode, (size_sr, size_sr))) if if_dmax else None
+        dm = _dmax_arg(dmax, dmax_mode, if_dmax, (size_sr, size_sr))
         for a in range(0, len(params), per_canvas):
             chunk = params[a: a + per_canvas]
             if len(chunk) == 1:

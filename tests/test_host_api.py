@@ -42,6 +42,40 @@ def test_prologue_accepts_tensor_sr_size_and_bad_modes():
     assert gsp._step_size(3.0, None, 1.2, "scale") == pytest.approx(0.4)
 
 
+def test_per_call_argument_helpers(monkeypatch):
+    """`_dmax_arg` is `_resolve_dmax` as a float, or None with `if_dmax` off (on the reference captures); `_fused_step_args` of what
+    `_step_size(..., fused=True)` returns: numbers and CPU tensors are a value, never a source left on the device"""
+    for path in PROLOGUE:
+        z = np.load(path)
+        args = (float(z["dmax_in"]), str(z["dmax_mode"]), z["sr_size"].tolist())
+        got = gsp._dmax_arg(args[0], args[1], True, args[2])
+        assert isinstance(got, float) and got == float(gsp._resolve_dmax(*args))
+        if bool(z["if_dmax"]):
+            assert abs(got - float(z["dmax_out"])) < 1e-12
+        assert gsp._dmax_arg(args[0], args[1], False, args[2]) is None
+    with pytest.raises(ValueError):
+        gsp._dmax_arg(0.1, "bogus", True, (8, 8))
+    cpu = torch.device("cpu")
+    step, sm, default_step, watch = gsp._fused_step_args(gsp._step_size(4.0, torch.tensor([4.0, 4.0]), 1.2, "scale_modify", fused=True), cpu)
+    assert (sm, default_step, watch) == (None, 1.2, False)
+    assert step.shape == (1,) and step.dtype == torch.float32 and float(step) == pytest.approx(0.3)
+    made = []
+    monkeypatch.setattr(gsp, "_step_tensor", lambda value, dev: made.append((value, dev)) or "step tensor")
+    for sc, pair, mode in ((4.0, (4.0, 4.0), "scale_modify"), (3.0, None, "scale"), (3.0, torch.tensor([3.0, 3.0]), "scale")):
+        value = gsp._step_size(sc, pair, 1.2, mode, fused=True)
+        assert value.__class__ is not gsp._StepSource
+        assert gsp._fused_step_args(value, cpu) == ("step tensor", None, 1.2, False)
+        assert made[-1] == (pytest.approx(1.2 / sc), cpu)
+    source = gsp._StepSource(torch.tensor([2.0, 2.0]), 1.5)      # (what a float32 CUDA pair becomes)
+    assert gsp._fused_step_args(source, cpu) == (None, source.scale_modify, 1.5, True)
+    with pytest.raises(AssertionError):
+        gsp._step_size(4.0, torch.tensor([4.0, 3.0]), 1.2, "scale_modify", fused=True)
+    with pytest.raises(AssertionError):
+        gsp._step_size(4.0, (4.0, 3.0), 1.2, "scale_modify", fused=True)
+    with pytest.raises(UnboundLocalError):
+        gsp._step_size(4.0, (4.0, 4.0), 1.2, "bogus", fused=True)
+
+
 RP = sorted(glob.glob(os.path.join(GOLDEN, "rendering_python_n*.npz")))
 
 

@@ -1,4 +1,4 @@
-"""gsasr_amd.tune.tune_step on the fused single-image entry point: does gaussian_splatting._tile_backward's rule still pick the faster
+"""gsasr_amd.tune.tune_step on the fused single-image entry point: does gaussian_splatting._backward_kernel's rule still pick the faster
 backward?   python tools/tune_step_demo.py   (GPU box)"""
 import os
 import sys
@@ -6,8 +6,10 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gsasr_amd import synthetic, tune  # noqa: E402
-from gsasr_amd.gaussian_splatting import _tile_backward  # noqa: E402
+from gsasr_amd import _cabi, synthetic, tune  # noqa: E402
+from gsasr_amd.gaussian_splatting import _backward_kernel  # noqa: E402
+
+RULE = {_cabi.FLAG_BWD_TILE: "tile", _cabi.FLAG_BWD_GAUSSIAN: "gaussian", _cabi.FLAG_BWD_HOME: "home"}
 
 dev = torch.device("cuda:0")
 print(f"{'shape':26s} {'rule':9s} {'default ms':>10s}  " + " ".join(f"{n:>16s}" for n in ("gaussian-search", "gaussian-lists", "tile-search", "tile-lists")) + "   picks")
@@ -18,6 +20,6 @@ for name, lr, scale, gpp, dmax in (("x4 1024^2 (config 2)", 256, 4, 1, 0.1), ("x
     p = synthetic.gs_parameters(lr, lr, seed=0, gpp=gpp).to(dev)
     step = torch.tensor([1.2 / scale], device=dev)
     res = tune.tune_step(p, step, H, W, dmax, register=False)
-    rule = "tile" if _tile_backward(H * W, p.shape[0]) else "gaussian"
+    rule = RULE[_backward_kernel(H * W, p.shape[0])]
     print(f"{name:26s} {rule:9s} {res.ms['default']:10.4f}  " + " ".join(f"{res.ms.get(n, float('nan')):16.4f}" for n in ("gaussian-search", "gaussian-lists", "tile-search", "tile-lists")) + f"   {res.name}", flush=True)
     tune.reset()
