@@ -75,6 +75,17 @@ class Metrics(ctypes.Structure):
                 ("crop_border", ctypes.c_int), ("flags", ctypes.c_uint), ("out", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
 
 
+class Resize(ctypes.Structure):
+    """struct gsasr_resize: MATLAB-compatible bicubic imresize of planar fp32 images and its adjoint (gsasr_imresize[_backward])"""
+    _fields_ = [("batch", ctypes.c_int), ("channels", ctypes.c_int), ("in_h", ctypes.c_int), ("in_w", ctypes.c_int),
+                ("sample_hw", ctypes.POINTER(ctypes.c_int)), ("scales", ctypes.POINTER(ctypes.c_double)),
+                ("out_h", ctypes.c_int), ("out_w", ctypes.c_int),
+                ("inp", ctypes.c_void_p), ("in_pitch", ctypes.c_size_t), ("in_plane", ctypes.c_size_t), ("in_stride", ctypes.c_size_t),
+                ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_size_t), ("out_plane", ctypes.c_size_t), ("out_stride", ctypes.c_size_t),
+                ("flags", ctypes.c_uint), ("scratch", ctypes.c_void_p)]
+
+
+RESIZE_NO_ANTIALIAS, RESIZE_ACCUMULATE, RESIZE_SHARED_SCALE = 1, 2, 4     # GSASR_RESIZE_*
 SSIM_GRAD_HWC, SSIM_ACCUMULATE = 1, 2                   # GSASR_SSIM_GRAD_HWC / _ACCUMULATE
 METRIC_PSNR, METRIC_SSIM, METRIC_Y, METRIC_BGR = 1, 2, 4, 8     # GSASR_METRIC_*
 LOSS_KINDS = {"l1": 0, "mse": 1, "charbonnier": 2}      # GSASR_LOSS_L1 / _MSE / _CHARBONNIER
@@ -82,6 +93,7 @@ LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
 _vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
+_rzp = ctypes.POINTER(Resize)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -149,6 +161,10 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     # PSNR / SSIM of an 8-bit picture (gsasr_metrics)
     "gsasr_metrics_scratch_bytes": (_sz, [_mp]),
     "gsasr_image_metrics": (_i, [_mp, _vp]),
+    # bicubic imresize of planar fp32 images and its adjoint (gsasr_resize)
+    "gsasr_resize_scratch_bytes": (_sz, [_rzp]),
+    "gsasr_imresize": (_i, [_rzp, _vp]),
+    "gsasr_imresize_backward": (_i, [_rzp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1213,6 +1229,73 @@ def image_metrics(img: torch.Tensor, ref: torch.Tensor, sizes=None, crop_border:
         d.img, d.ref, d.out, d.scratch = pi, pr, out.data_ptr(), scratch.data_ptr()
         check(lib().gsasr_image_metrics(ctypes.byref(d), _stream(dev)), "gsasr_image_metrics")
     return out
+
+
+# ---- bicubic imresize (include/gsasr_splat.h: gsasr_resize) ------------------------------------------------------
+def make_resize(batch: int, channels: int, in_h: int, in_w: int, out_h: int, out_w: int, scales, sizes=None, flags: int = 0) -> Resize:
+    """a gsasr_resize descriptor without pointers, dense pitches and strides; `scales`: one (scale_h, scale_w) for all samples or
+    one per sample; `sizes`: the (h_b, w_b) of every sample, None = all in_h x in_w"""
+    d = Resize(int(batch), int(channels), int(in_h), int(in_w))
+    d.out_h, d.out_w = int(out_h), int(out_w)
+    d.in_pitch, d.out_pitch = 4 * int(in_w), 4 * int(out_w)
+    d.in_plane, d.out_plane = int(in_h) * d.in_pitch, int(out_h) * d.out_pitch
+    d.in_stride, d.out_stride = int(channels) * d.in_plane, int(channels) * d.out_plane
+    flat = [float(v) for v in scales] if not isinstance(scales[0], (tuple, list)) else [float(v) for sc in scales for v in sc]
+    if len(flat) == 2:
+        flags |= RESIZE_SHARED_SCALE
+    elif len(flat) != 2 * batch:
+        raise RuntimeError("scales must hold one (scale_h, scale_w) pair, or one per sample")
+    d._sc = (ctypes.c_double * len(flat))(*flat)      # kept alive by the descriptor
+    d.scales = ctypes.cast(d._sc, ctypes.POINTER(ctypes.c_double))
+    if sizes is not None:
+        if len(sizes) != batch:
+            raise RuntimeError("sizes must hold one (h, w) per sample")
+        d._hw = (ctypes.c_int * (2 * batch))(*[int(v) for hw in sizes for v in hw])
+        d.sample_hw = ctypes.cast(d._hw, ctypes.POINTER(ctypes.c_int))
+    d.flags = int(flags)
+    return d
+
+
+def _planar(t: torch.Tensor, name: str):
+    """an fp32 CUDA `[B,C,h,w]` tensor whose rows are dense and whose strides are not negative -> (pointer, pitch, plane, stride) in bytes"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+        raise RuntimeError(f"{name} must be a float32 CUDA tensor [B,C,h,w]")
+    st = t.stride()
+    if (st[3] != 1 and t.shape[3] > 1) or (st[2] < t.shape[3] and t.shape[2] > 1) or st[0] < 0 or st[1] < 0:
+        raise RuntimeError(f"{name} has strides {st}: rows must be dense and at least w elements apart")
+    return t.data_ptr(), 4 * (st[2] if t.shape[2] > 1 else t.shape[3]), 4 * st[1], 4 * st[0]
+
+
+def imresize(x: torch.Tensor, out: torch.Tensor, scales, sizes=None, antialiasing: bool = True, backward: bool = False,
+             accumulate: bool = False, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gsasr_imresize: `x` fp32 `[B,C,H,W]` -> `out` `[B,C,out_h,out_w]` (windows of larger tensors are taken through their
+    strides); `scales`: (scale_h, scale_w), or one pair per sample; `sizes`: the samples' own (h_b, w_b) in their H x W slot.
+    `backward`: gsasr_imresize_backward -- `out` is read as grad_out and `x` written (`accumulate`: added to) as grad_in, on the
+    samples' own pixels only.  Returns the tensor written.  On the current stream; scratch from torch unless given."""
+    px, d_in = _planar(x, "x"), None
+    po = _planar(out, "out")
+    if x.shape[:2] != out.shape[:2] or x.device != out.device:
+        raise RuntimeError(f"x {tuple(x.shape)} and out {tuple(out.shape)} must agree on [B,C] and the device")
+    B, C, H, W = (int(v) for v in x.shape)
+    dev = x.device
+    flags = (0 if antialiasing else RESIZE_NO_ANTIALIAS) | (RESIZE_ACCUMULATE if accumulate else 0)
+    d = make_resize(B, C, H, W, int(out.shape[2]), int(out.shape[3]), scales, sizes, flags)
+    d.in_pitch, d.in_plane, d.in_stride = px[1:]
+    d.out_pitch, d.out_plane, d.out_stride = po[1:]
+    n = int(lib().gsasr_resize_scratch_bytes(ctypes.byref(d)))
+    if n == 0:
+        check(-1, "gsasr_resize_scratch_bytes")
+    with _on(dev):
+        if scratch is None:
+            scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        elif _chk(scratch, "scratch") == 0 or 4 * scratch.numel() < n or scratch.device != dev:
+            raise RuntimeError("scratch is smaller than gsasr_resize_scratch_bytes()")
+        d.inp, d.out, d.scratch = px[0], po[0], scratch.data_ptr()
+        if backward:
+            check(lib().gsasr_imresize_backward(ctypes.byref(d), _stream(dev)), "gsasr_imresize_backward")
+        else:
+            check(lib().gsasr_imresize(ctypes.byref(d), _stream(dev)), "gsasr_imresize")
+    return x if backward else out
 
 
 # ---- sampled pixels (SURVEY.md 8 row f4) ----------------------------------------------------------------

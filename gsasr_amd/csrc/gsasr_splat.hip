@@ -50,6 +50,8 @@
 //                        to the gradient the fused pixel loss wrote (GSASR's cri_ssim; splat_ssim.hip).
 //   metrics  k_metric_stats/reduce   PSNR and SSIM of an 8-bit picture against its 8-bit ground truth, cropped, in RGB or on the Y
 //                        channel (GSASR's val.metrics; splat_metrics.hip).
+//   resize   k_resize_weights/rows/cols (+ _adj)   MATLAB-compatible antialiased bicubic imresize of planar fp32 batches and its
+//                        adjoint in gather form (GSASR's degradation, matlab_functions.py; splat_resize.hip).
 //
 // No MFMA: this is gather/scatter-accumulate with one transcendental per pair, not a contraction.
 // This file is the WHOLE library as one translation unit (tools/mb.hip includes it); gsasr_amd/build.py compiles the parts
@@ -65,3 +67,4 @@
 #include "splat_shard.hip"
 #include "splat_ssim.hip"
 #include "splat_metrics.hip"
+#include "splat_resize.hip"

@@ -519,6 +519,65 @@ typedef struct gsasr_metrics {
 GSASR_API size_t gsasr_metrics_scratch_bytes(const gsasr_metrics *metrics);   /* 0 on bad arguments (img, ref, out and scratch are not looked at) */
 GSASR_API int gsasr_image_metrics(const gsasr_metrics *metrics, void *stream);
 
+/* MATLAB-compatible bicubic imresize and its adjoint (the degradation that defines the task: basicsr/utils/matlab_functions.py
+ * imresize / imresize_new, which basicsr/data/continuous_bicubic_downsample_dataset.py:70-72 applies to every GT crop), batched,
+ * on planar fp32 images.  No float atomics, no memset, no allocation, no host synchronisation: a call can be captured, and two
+ * calls on the same inputs give the same bits.
+ *
+ *   per axis   input length n, output length m, scale s: kw = 4 / s when s < 1 and antialiasing is on, else 4; p = ceil(kw) + 2
+ *              taps.  Output o = 1..m (1-based): u = o / s + 0.5 (1 - 1 / s), left = floor(u - kw / 2), taps k = left .. left + p - 1
+ *              with raw weight s cubic((u - k) s) in the antialiased-shrink case, else cubic(u - k);
+ *              cubic(x) = 1.5|x|^3 - 2.5|x|^2 + 1 (|x| <= 1), -0.5|x|^3 + 2.5|x|^2 - 4|x| + 2 (1 < |x| <= 2), 0 beyond.  The p
+ *              weights are divided by their sum.  u and the weights are computed in double and rounded once to float.
+ *   edges      a tap outside the input reads the symmetric extension, mirrored once: 0-based k < 0 -> -1 - k, k >= n -> 2n - 1 - k.
+ *              A tap with a non-zero weight that is still outside after one reflection is an argument error (the reference's
+ *              symmetric copy fails on such a call too)
+ *   order      rows (H) first, then columns (W); the intermediate [out_h, w_b] is fp32, each pass one fp32 dot product per
+ *              output in tap order
+ *   sizes      out_h, out_w are the caller's and shared by all samples: the formulas run for o = 1..out.  The reference's sizes
+ *              are ceil(n s) (imresize) and Python's round(n s) (imresize_new); the library does not compare
+ *   batch      1..GSASR_MAX_BATCH samples of `channels` >= 1 planes each (batch * channels <= 65535)
+ *   in_h, in_w the input slot, 1..32767 each (so are out_h, out_w)
+ *   sample_hw  HOST array [2 * batch] of (h_b, w_b), read during the call: sample b is the top-left h_b x w_b pixels of its
+ *              slot; NULL: every sample is in_h x in_w.  Pixels of a slot outside h_b x w_b are never read, and the backward
+ *              leaves them untouched (a caller that wants zeros there clears the buffer first)
+ *   scales     HOST array of doubles, read during the call: [2 * batch] = (scale_h, scale_w) of sample b, or with
+ *              GSASR_RESIZE_SHARED_SCALE [2], one pair for every sample.  Each finite and > 0
+ *   in, out    fp32 planar; pixel (y, x) of channel c of sample b at byte b * stride + c * plane + y * pitch + 4 x.  Pitches, plane
+ *              and sample strides are multiples of 4 bytes, the pitch at least the row (4 * in_w, 4 * out_w); the pointers 4-byte
+ *              aligned: either tensor may be a window of a larger one
+ *   flags      GSASR_RESIZE_NO_ANTIALIAS: antialiasing=False; GSASR_RESIZE_SHARED_SCALE: above; GSASR_RESIZE_ACCUMULATE (backward
+ *              only; an argument error in the forward): grad_in += ..., else stored
+ *   scratch    gsasr_resize_scratch_bytes(descriptor) bytes, 16-byte aligned: the weight tables and the row-pass intermediate.
+ *              Every word that is read was written by the same call
+ *   backward   gsasr_imresize_backward reads `out` as grad_out [batch, channels, out_h, out_w] and writes `in` (const cast away)
+ *              as grad_in = A^T grad_out on the h_b x w_b pixels of every sample, A being the forward's linear map with the
+ *              same float weights; gather form, fixed order
+ * GSASR_ERR_ARG before anything is enqueued: a null descriptor, null in / out / scratch / scales, batch outside
+ * 1..GSASR_MAX_BATCH, channels < 1 or batch * channels > 65535, in_h / in_w / out_h / out_w outside 1..32767, a sample with
+ * no pixel or larger than its slot, a pitch below the row, a pitch / plane / stride that is no multiple of 4, a misaligned
+ * pointer, a scale that is not finite and > 0, unknown flag bits, GSASR_RESIZE_ACCUMULATE in the forward, and the reflection
+ * condition above (e.g. 26 pixels at s = 1/16). */
+#define GSASR_RESIZE_NO_ANTIALIAS 1u
+#define GSASR_RESIZE_ACCUMULATE 2u     /* backward: grad_in += ... ; else stored */
+#define GSASR_RESIZE_SHARED_SCALE 4u   /* scales holds one (scale_h, scale_w) pair for all samples */
+typedef struct gsasr_resize {
+    int batch, channels;
+    int in_h, in_w;          /* the input slot */
+    const int *sample_hw;    /* HOST array [2*batch], or NULL */
+    const double *scales;    /* HOST array [2*batch], or [2] with GSASR_RESIZE_SHARED_SCALE */
+    int out_h, out_w;        /* every sample's output size */
+    const float *in;         /* backward: grad_in, written */
+    size_t in_pitch, in_plane, in_stride;      /* bytes between rows / channels / samples */
+    float *out;              /* backward: grad_out, read */
+    size_t out_pitch, out_plane, out_stride;
+    unsigned flags;          /* GSASR_RESIZE_* */
+    void *scratch;
+} gsasr_resize;
+GSASR_API size_t gsasr_resize_scratch_bytes(const gsasr_resize *resize);   /* 0 on bad arguments (sample_hw and scales are read; in, out and scratch are not looked at) */
+GSASR_API int gsasr_imresize(const gsasr_resize *resize, void *stream);
+GSASR_API int gsasr_imresize_backward(const gsasr_resize *resize, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate
