@@ -4,8 +4,9 @@ and against this file's own float64 restatement in NumPy (`taps_f64`, `dense_f64
 with the package), the accepted input kinds, both size rules, every ValueError, and every GSASR_ERR_ARG of the C entry points.
 
 Bars.  Each fixture records d_ref = max |reference - resize_f64| on its case: the reference's own float32 error.  A float32
-subject is held to max(1e-6, 4 * d_ref) against resize_f64 (the factor covers another summation order of up to 66 taps) and to
-that plus d_ref against the fixture; a float64 subject to 1e-12 against resize_f64 (66 taps * 2 passes * 2^-53 * sum|w| 1.25)."""
+subject is held to max(1e-6, 4 * d_ref) against resize_f64 (the factor covers another summation order of the taps: 7 to 66 on
+the first nine cases, 130 to 402 on the three that stage more than one chunk, whose reference sums as many) and to that plus
+d_ref against the fixture; a float64 subject to 1e-12 against resize_f64 (402 taps * 2 passes * 2^-53 * sum|w| 1.25 = 1.1e-13)."""
 import ctypes
 import math
 import os
@@ -34,6 +35,10 @@ CASES = {
     "20x31_up_round": dict(h=20, w=31, c=3, fn="imresize_new", scales=(2.5, 2.5), aa=True, kind="chw", out=(50, 78), seed=16),
     "97_to_48_no_aa": dict(h=97, w=97, c=3, fn="imresize_new", scales=(48 / 97, 48 / 97), aa=False, kind="chw", out=(48, 48), seed=13),
     "53_to_48_2d": dict(h=53, w=53, c=1, fn="imresize_new", scales=(48 / 53, 48 / 53), aa=True, kind="hw", out=(48, 48), seed=17),
+    # more than one staged chunk of 256 taps per W-pass tile: p = 258, 130, (402, 174)
+    "640_to_10": dict(h=640, w=640, c=1, fn="imresize", scales=(1 / 64,), aa=True, kind="chw", out=(10, 10), seed=18),
+    "288_to_9": dict(h=288, w=288, c=1, fn="imresize_new", scales=(1 / 32, 1 / 32), aa=True, kind="chw", out=(9, 9), seed=19),
+    "1100x129_by_100_43": dict(h=1100, w=129, c=1, fn="imresize_new", scales=(1 / 100, 1 / 43), aa=True, kind="chw", out=(11, 3), seed=20),
 }
 
 

@@ -2,12 +2,14 @@
 and the reference's fixtures of tests/test_imresize.py.
 
 Bars.  Forward, inputs in [0,1]: max(1e-6, 4 * d_ref) absolute against the float64 restatement, d_ref being the reference's own
-recorded distance from it on the case (the reference is the yardstick; 4 covers another summation order of up to 66 taps), and
-that plus d_ref against the reference's fixture.  Adjoint: 1e-5 * max|grad_out| against the float64 dense A^T -- each pass is a
-dot product of at most 66 fp32 terms with sum|w| <= 1.27, 66 * 6e-8 * 1.27 = 5e-6 per pass, two passes; there is no reference
-backward (the reference function is no_grad).  <A x, y> = <x, A^T y> to 1e-5 relative.  Every case prints what it measured.
-Shapes are the fixtures' (the smallest that reach each path: p = 7, 13, 66, an upscale, no antialiasing, 2-D) plus a padded
-batch of three sizes, a batch of 17 (past 16), and windows of larger tensors."""
+recorded distance from it on the case (the reference is the yardstick; 4 covers another summation order of the taps: up to 66
+on the first nine cases, 130, 258 and 402 on the three that stage more than one chunk), and that plus d_ref against the
+reference's fixture.  Adjoint (ADJOINT_CASES, at most 66 taps): 1e-5 * max|grad_out| against the float64 dense A^T -- each pass
+is a dot product of at most 66 fp32 terms with sum|w| <= 1.27, 66 * 6e-8 * 1.27 = 5e-6 per pass, two passes; there is no
+reference backward (the reference function is no_grad).  <A x, y> = <x, A^T y> to 1e-5 relative.  Every case prints what it
+measured.  Shapes are the fixtures' (the smallest that reach each path: p = 7, 13, 66, an upscale, no antialiasing, 2-D, and
+p = 130, 258, 402 / 174) plus a padded batch of three sizes, a batch of 17 (past 16), and windows of larger tensors.  Wider
+windows, every tile width and bars on each element's own scale: tests/test_imresize_wide_gpu.py."""
 import os
 import shutil
 import subprocess
