@@ -12,6 +12,7 @@ import threading
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -85,7 +86,18 @@ class Resize(ctypes.Structure):
                 ("flags", ctypes.c_uint), ("scratch", ctypes.c_void_p)]
 
 
+class Batch(ctypes.Structure):
+    """struct gsasr_batch: training batches from decoded 8-bit images (gsasr_batch_make / gsasr_batch_pick)"""
+    _fields_ = [("batch", ctypes.c_int), ("src", ctypes.POINTER(ctypes.c_void_p)), ("src_hw", ctypes.POINTER(ctypes.c_int)),
+                ("window", ctypes.POINTER(ctypes.c_int)), ("aug", ctypes.POINTER(ctypes.c_ubyte)),
+                ("gt_h", ctypes.c_int), ("gt_w", ctypes.c_int), ("gt", ctypes.c_void_p),
+                ("lr_h", ctypes.c_int), ("lr_w", ctypes.c_int), ("lq", ctypes.c_void_p),
+                ("flags", ctypes.c_uint), ("scratch", ctypes.c_void_p)]
+
+
 RESIZE_NO_ANTIALIAS, RESIZE_ACCUMULATE, RESIZE_SHARED_SCALE = 1, 2, 4     # GSASR_RESIZE_*
+BATCH_HFLIP, BATCH_VFLIP, BATCH_TRANSPOSE = 1, 2, 4     # GSASR_BATCH_* (aug bits)
+BATCH_BGR, BATCH_NO_ANTIALIAS = 1, 2                    # GSASR_BATCH_* (flags)
 SSIM_GRAD_HWC, SSIM_ACCUMULATE = 1, 2                   # GSASR_SSIM_GRAD_HWC / _ACCUMULATE
 METRIC_PSNR, METRIC_SSIM, METRIC_Y, METRIC_BGR = 1, 2, 4, 8     # GSASR_METRIC_*
 LOSS_KINDS = {"l1": 0, "mse": 1, "charbonnier": 2}      # GSASR_LOSS_L1 / _MSE / _CHARBONNIER
@@ -93,7 +105,7 @@ LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
 _vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
-_rzp = ctypes.POINTER(Resize)
+_rzp, _btp = ctypes.POINTER(Resize), ctypes.POINTER(Batch)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -165,6 +177,10 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_resize_scratch_bytes": (_sz, [_rzp]),
     "gsasr_imresize": (_i, [_rzp, _vp]),
     "gsasr_imresize_backward": (_i, [_rzp, _vp]),
+    # training batches from decoded 8-bit images (gsasr_batch)
+    "gsasr_batch_scratch_bytes": (_sz, [_btp]),
+    "gsasr_batch_make": (_i, [_btp, _vp]),
+    "gsasr_batch_pick": (_i, [_btp, _vp, _i, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1296,6 +1312,95 @@ def imresize(x: torch.Tensor, out: torch.Tensor, scales, sizes=None, antialiasin
         else:
             check(lib().gsasr_imresize(ctypes.byref(d), _stream(dev)), "gsasr_imresize")
     return x if backward else out
+
+
+# ---- training batches from decoded images (include/gsasr_splat.h: gsasr_batch) -----------------------------------
+def make_batch_desc(srcs, src_hw, windows, aug=None, gt_hw=(0, 0), lr_hw=(0, 0), flags: int = 0) -> Batch:
+    """a gsasr_batch descriptor without gt / lq / scratch: `srcs` device addresses, `src_hw` (h, w) and `windows`
+    (y0, x0, gh, gw) per sample, `aug` one byte of BATCH_HFLIP | _VFLIP | _TRANSPOSE per sample or None"""
+    n = len(srcs)
+    if len(src_hw) != n or len(windows) != n or (aug is not None and len(aug) != n):
+        raise RuntimeError("one source, (h, w), window and augmentation per sample")
+    d = Batch(n)
+    # (NumPy packs the host arrays in one conversion each; the descriptor keeps them alive)
+    d._src = np.array([int(p) if p else 0 for p in srcs] or [0], dtype=np.uint64)
+    d._hw = np.ascontiguousarray(np.array(src_hw if n else [(0, 0)], dtype=np.int32).reshape(-1, 2))
+    d._win = np.ascontiguousarray(np.array(windows if n else [(0, 0, 0, 0)], dtype=np.int32).reshape(-1, 4))
+    d.src = ctypes.cast(d._src.ctypes.data, ctypes.POINTER(ctypes.c_void_p))
+    d.src_hw = ctypes.cast(d._hw.ctypes.data, ctypes.POINTER(ctypes.c_int))
+    d.window = ctypes.cast(d._win.ctypes.data, ctypes.POINTER(ctypes.c_int))
+    if aug is not None:
+        d._aug = np.array(list(aug) or [0], dtype=np.uint8)
+        d.aug = ctypes.cast(d._aug.ctypes.data, ctypes.POINTER(ctypes.c_ubyte))
+    d.gt_h, d.gt_w = int(gt_hw[0]), int(gt_hw[1])
+    d.lr_h, d.lr_w = int(lr_hw[0]), int(lr_hw[1])
+    d.flags = int(flags)
+    return d
+
+
+def _sources(images):
+    """uint8 CUDA tensors `[h,w,3]`, contiguous, on one device -> (device, addresses, sizes)"""
+    dev = images[0].device
+    for t in images:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
+                and t.is_contiguous() and t.device == dev):
+            raise RuntimeError("images must be contiguous uint8 CUDA tensors [h,w,3] on one device")
+    return dev, [t.data_ptr() for t in images], [(int(t.shape[0]), int(t.shape[1])) for t in images]
+
+
+def batch_make(images, windows, aug, gt: Optional[torch.Tensor], lq: torch.Tensor, bgr: bool = True, antialiasing: bool = True,
+               scratch: Optional[torch.Tensor] = None):
+    """gsasr_batch_make: windows of the uint8 `images` -> `gt` fp32 `[B,3,Gh,Gw]` (augmented, zero-padded; None: not made) and
+    `lq` fp32 `[B,3,lh,lw]` (bicubic LR of the un-augmented window, then augmented), both written.  On the current stream;
+    scratch (a uint8 tensor of gsasr_batch_scratch_bytes()) from torch unless given."""
+    dev, ptrs, hw = _sources(images)
+    return _batch_make(dev, ptrs, hw, windows, aug, gt, lq, bgr, antialiasing, scratch)
+
+
+def _batch_make(dev, ptrs, hw, windows, aug, gt, lq, bgr=True, antialiasing=True, scratch=None):
+    """`batch_make` on sources that are already checked: their device, addresses and (h, w)"""
+    B = len(ptrs)
+    pg, pl = None if gt is None else _chk(gt, "gt"), _chk(lq, "lq")
+    if lq.dim() != 4 or tuple(lq.shape[:2]) != (B, 3) or lq.device != dev:
+        raise RuntimeError(f"lq {tuple(lq.shape)} must be [{B},3,h,w] on the images' device")
+    if gt is not None and (gt.dim() != 4 or tuple(gt.shape[:2]) != (B, 3) or gt.device != dev):
+        raise RuntimeError(f"gt {tuple(gt.shape)} must be [{B},3,h,w] on the images' device")
+    flags = (BATCH_BGR if bgr else 0) | (0 if antialiasing else BATCH_NO_ANTIALIAS)
+    gt_hw = gt.shape[2:] if gt is not None else (max(max(wd[2], wd[3]) for wd in windows),) * 2     # (any slot that holds the samples)
+    d = make_batch_desc(ptrs, hw, windows, aug, gt_hw, lq.shape[2:], flags)
+    n = int(lib().gsasr_batch_scratch_bytes(ctypes.byref(d)))
+    if n == 0:
+        check(-1, "gsasr_batch_scratch_bytes")
+    with _on(dev):
+        if scratch is None:
+            scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+        elif not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
+                  and scratch.numel() >= n and scratch.device == dev):
+            raise RuntimeError("scratch must be a contiguous uint8 tensor of at least gsasr_batch_scratch_bytes() on the images' device")
+        d.gt, d.lq, d.scratch = pg, pl, scratch.data_ptr()
+        check(lib().gsasr_batch_make(ctypes.byref(d), _stream(dev)), "gsasr_batch_make")
+    return gt, lq
+
+
+def batch_pick(images, windows, aug, points: torch.Tensor, out: torch.Tensor, bgr: bool = True) -> torch.Tensor:
+    """gsasr_batch_pick: `out` fp32 `[B,3,S]` = the augmented windows at the int32 `points` `[B,S,2]` = (row, column)"""
+    dev, ptrs, hw = _sources(images)
+    return _batch_pick(dev, ptrs, hw, windows, aug, points, out, bgr)
+
+
+def _batch_pick(dev, ptrs, hw, windows, aug, points, out, bgr=True):
+    """`batch_pick` on sources that are already checked"""
+    B = len(ptrs)
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.int32 and points.is_contiguous()
+            and points.dim() == 3 and points.shape[0] == B and points.shape[2] == 2 and points.device == dev):
+        raise RuntimeError(f"points must be a contiguous int32 tensor [{B},S,2] on the images' device")
+    S = int(points.shape[1])
+    if _chk(out, "out") == 0 or tuple(out.shape) != (B, 3, S) or out.device != dev:
+        raise RuntimeError(f"out must be a contiguous float32 tensor [{B},3,{S}] on the images' device")
+    d = make_batch_desc(ptrs, hw, windows, aug, flags=BATCH_BGR if bgr else 0)
+    with _on(dev):
+        check(lib().gsasr_batch_pick(ctypes.byref(d), points.data_ptr(), S, out.data_ptr(), _stream(dev)), "gsasr_batch_pick")
+    return out
 
 
 # ---- sampled pixels (SURVEY.md 8 row f4) ----------------------------------------------------------------

@@ -52,6 +52,8 @@
 //                        channel (GSASR's val.metrics; splat_metrics.hip).
 //   resize   k_resize_weights/rows/cols (+ _adj)   MATLAB-compatible antialiased bicubic imresize of planar fp32 batches and its
 //                        adjoint in gather form (GSASR's degradation, matlab_functions.py; splat_resize.hip).
+//   data     k_batch_crop/d4/pick   training batches from decoded 8-bit images: crop, /255, bicubic LR, flips / transposition,
+//                        BGR -> RGB, planar, zero padding or sampled pixels (GSASR's dataset __getitem__; splat_data.hip).
 //
 // No MFMA: this is gather/scatter-accumulate with one transcendental per pair, not a contraction.
 // This file is the WHOLE library as one translation unit (tools/mb.hip includes it); gsasr_amd/build.py compiles the parts
@@ -68,3 +70,4 @@
 #include "splat_ssim.hip"
 #include "splat_metrics.hip"
 #include "splat_resize.hip"
+#include "splat_data.hip"

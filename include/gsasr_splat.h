@@ -578,6 +578,64 @@ GSASR_API size_t gsasr_resize_scratch_bytes(const gsasr_resize *resize);   /* 0 
 GSASR_API int gsasr_imresize(const gsasr_resize *resize, void *stream);
 GSASR_API int gsasr_imresize_backward(const gsasr_resize *resize, void *stream);
 
+/* Training batches from decoded images (what basicsr/data/continuous_bicubic_downsample_dataset.py:46-111 does per sample on the
+ * host, and the DataLoader's collation): `batch` windows of `batch` 8-bit images resident on the device become, in one call, the
+ * float tensors a training step reads.  New entry points of ABI 7; no existing one changed.
+ *
+ *   sources    src: HOST array [batch] of DEVICE pointers to dense uint8 images [h, w, 3] (any byte alignment; the same image may
+ *              serve several samples); src_hw: HOST array [2 * batch] of (h, w), 1..32767 each.  Nothing outside an image's
+ *              h * w * 3 bytes is read
+ *   window     HOST array [4 * batch] of (y0, x0, gh, gw): sample b is rows y0 .. y0 + gh - 1, columns x0 .. x0 + gw - 1 of
+ *              its image; inside the image, at least one pixel
+ *   value      (float)byte / 255.0f, one correctly rounded division.  With GSASR_BATCH_BGR a pixel's bytes are b, g, r and
+ *              the planes come out r, g, b (the reference's img2tensor(bgr2rgb=True)); without it the planes keep the bytes' order
+ *   aug        HOST array [batch] of GSASR_BATCH_HFLIP | _VFLIP | _TRANSPOSE, or NULL for none.  The order is
+ *              basicsr/data/transforms.py:119-133's: horizontal flip, vertical flip, transposition -- pixel (r, c) of a transposed
+ *              sample is row c, column r of the flipped window, and the sample's extent is gw x gh
+ *   gt         fp32 [batch, 3, gt_h, gt_w], dense: the augmented sample in the top-left corner of its slot, every other pixel
+ *              of the slot written as 0 (the reference's F.pad to gt_size_max; no memset is launched).  NULL: only lq is made
+ *              (the sampled-pixel batch, whose GT comes from gsasr_batch_pick); gt_h x gt_w must hold the samples all the same
+ *   lq         fp32 [batch, 3, lr_h, lr_w], dense: gsasr_imresize of the UN-augmented float window with scales lr_h / gh,
+ *              lr_w / gw, then the same flips / transposition (resize first, augment second: the reference's order; a transposed
+ *              sample needs lr_h == lr_w)
+ *   flags      GSASR_BATCH_BGR: above; GSASR_BATCH_NO_ANTIALIAS: the resize's antialiasing=False
+ *   scratch    gsasr_batch_scratch_bytes(descriptor) bytes, 256-byte aligned: the planar float windows, the un-augmented LR
+ *              images and the resize's own scratch.  Every word that is read was written by the same call
+ *   pick       gsasr_batch_pick writes out [batch, 3, n_points] = the augmented sample at the integer points
+ *              [batch, n_points, 2] = (row, column) (device int32), read straight from the bytes: the float GT is not made.  The
+ *              points follow the sampled-pixel entry points' rule: a negative index wraps once, a point that is still out of the
+ *              sample's extent yields 0.  It reads src, src_hw, window, aug and GSASR_BATCH_BGR of the descriptor only
+ * All host arrays are read during the call.  The calls only enqueue work on `stream`: no allocation, no host synchronisation,
+ * and two calls on the same inputs give the same bits.  A call reads host arrays and, as a rule, new pointers on every step:
+ * it is not meant to be captured into a graph (a replay would repeat the windows and pointers of the capture).
+ * GSASR_ERR_ARG before anything is enqueued: a null descriptor; batch outside 1..GSASR_MAX_BATCH; a null src / src_hw / window
+ * array, source image, lq or scratch (pick: points or out); gt, lq, points or out not 4-byte aligned, scratch not 256-byte
+ * aligned; a source h or w, gt_h, gt_w, lr_h or lr_w outside 1..32767; a window outside its source, or with no pixel; a GT slot
+ * smaller than a sample's extent; a transposed sample with lr_h != lr_w; unknown flag or augmentation bits; n_points outside
+ * 1..2^24; and everything gsasr_imresize refuses on these windows, the reflection condition included (a 9-pixel window to
+ * lr 1 is one). */
+#define GSASR_BATCH_HFLIP 1u           /* aug bits */
+#define GSASR_BATCH_VFLIP 2u
+#define GSASR_BATCH_TRANSPOSE 4u
+#define GSASR_BATCH_BGR 1u             /* flags */
+#define GSASR_BATCH_NO_ANTIALIAS 2u
+typedef struct gsasr_batch {
+    int batch;
+    const unsigned char *const *src;   /* HOST array [batch] of device pointers */
+    const int *src_hw;                 /* HOST array [2*batch] */
+    const int *window;                 /* HOST array [4*batch]: y0, x0, gh, gw */
+    const unsigned char *aug;          /* HOST array [batch] of GSASR_BATCH_HFLIP | _VFLIP | _TRANSPOSE, or NULL */
+    int gt_h, gt_w;                    /* the GT slot */
+    float *gt;
+    int lr_h, lr_w;
+    float *lq;
+    unsigned flags;                    /* GSASR_BATCH_BGR | GSASR_BATCH_NO_ANTIALIAS */
+    void *scratch;
+} gsasr_batch;
+GSASR_API size_t gsasr_batch_scratch_bytes(const gsasr_batch *batch);   /* 0 on bad arguments (the host arrays are read; gt, lq and scratch are not looked at) */
+GSASR_API int gsasr_batch_make(const gsasr_batch *batch, void *stream);
+GSASR_API int gsasr_batch_pick(const gsasr_batch *batch, const int *points, int n_points, float *out, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate
