@@ -8,8 +8,9 @@ using namespace gsasr_detail;
 namespace {
 
 
-// (occupancy targets: the unrolled sweep fits 6 waves per SIMD at the price of five spilled dwords, -2.7% at config 4;
-// forcing the plain sweep to 8 costs more in spills than it gains)
+// (occupancy targets: the unrolled sweep at 6 waves per SIMD -- 76-79 VGPRs, nothing spilled --, the plain one at 7 -- 72 VGPRs, its
+// few spilled dwords all behind the large-class chunk loop; forcing the plain sweep to 8 costs more in spills than it gains.
+// Register / scratch lines of every kernel that inlines the sweep: profiles/early_loads_isa.txt)
 template <bool BOUNDED, bool UNROLL>
 __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(UNROLL ? BWD_UNROLL_OCC : BWD_OCC))) void k_render_bwd(Params P, PlanView V, const float *__restrict__ grad,
                                                     float *__restrict__ g_sigmas, float *__restrict__ g_coords,
@@ -701,8 +702,9 @@ int splat_backward(const float *sigmas, const float *coords, const float *colors
             return GSASR_OK;
         }
         const dim3 grid((unsigned)((dims->s + BWD_WAVES - 1) / BWD_WAVES)), block(64 * BWD_WAVES);
-        // Two instantiations of the same sweep (identical results): with the two-trip unrolled loop (88 VGPRs, 5 waves
-        // per SIMD) for windows of many trips, without it (70 VGPRs, 7 waves) for small windows.  The window sizes are on
+        // Two instantiations of the same sweep (identical results): with the two-trip unrolled loop (76-79 VGPRs, 6 waves
+        // per SIMD) for windows of many trips, without it (72 VGPRs, 7 waves; its first trip's loads go out with the tables:
+        // bwd_sweep) for small windows.  The window sizes are on
         // the device; GSASR's Gaussians are LR-pixel sized, so pixels per Gaussian is a good proxy (x4: 16, x8: 64).
         static const int unroll_env = dev_switch("GSASR_SPLAT_BWD_UNROLL") ? atoi(dev_switch("GSASR_SPLAT_BWD_UNROLL")) : -1;   // development: 0 | 1
         const bool unroll = unroll_env >= 0 ? unroll_env != 0 : (double)rows * (double)dims->w >= BWD_UNROLL_MIN * (double)pd.s;

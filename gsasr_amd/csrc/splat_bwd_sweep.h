@@ -116,6 +116,112 @@ __device__ __forceinline__ void bwd_trip(BwdRow &R, const Grad6 g, v2f dyn, v2f 
     R.kb2 = fmaf(g.b2, v.y, R.kb2);
 }
 
+// buffer resource over the gradient slab from row `rb` on (offsets stay far below 2^31 within a 64-row block)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t bwd_rsrc(const float *__restrict__ grad, int rb, const Params &P, unsigned pitchb)
+{
+    const char *blk = reinterpret_cast<const char *>(grad) + (unsigned long long)(unsigned)(rb - P.row0) * pitchb;
+    const unsigned long long left = (unsigned long long)(unsigned)(P.row1 - rb) * pitchb;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(blk), 0, (int)(left < 0x7fffffffu ? left : 0x7fffffffu), 0x00020000);
+}
+
+// what a lane keeps over one 64-column strip of the window
+struct BwdStrip {
+    bool inx;              // the lane has a column of the strip (and, with TEST, one inside the dmax box in x)
+    float u, rho_u, K0;
+    int voff;              // byte offset of the lane's first pixel in a row block
+};
+
+// One block of up to 64 rows [rb, min(r1, rb+63)] of a strip.  `pyv` is the lane's entry of the py table for the block, `rsrc` the
+// slab from row rb on.  FIRST (plain instantiation only) = the sweep's first block (strip 0, rb = r0): the two loads of its first
+// trip, e0, were issued by bwd_sweep together with the table loads and are consumed here in place of a load -- every later load,
+// and every later block, is as before.  (e0 is not read otherwise.)
+template <bool TEST, int LX, bool UNROLL, bool FIRST>
+__device__ __forceinline__ void bwd_block(BwdRow &R, const BwdStrip &S, int rb, int r1, int lane, float pyv, float y, float isy,
+                                          __amdgpu_buffer_rsrc_t rsrc, int halfb, const Grad6 &e0, float nK1,
+                                          float cr, float cg, float cb, float dmax, float *spy)
+{
+    static_assert(!(UNROLL && FIRST), "the early loads are the plain instantiation's (bwd_sweep)");
+    constexpr int RPI = 64 / LX, RPT = 2 * RPI;        // row slots of lanes; rows per trip
+    const int rsub = lane / LX;
+    const float K0 = S.K0, rho_u = S.rho_u;
+    const int voff = S.voff;
+    const int rend = min(r1, rb + 63);
+    __builtin_amdgcn_wave_barrier();
+    {   // per-row values of the block in LDS: v = dy/sy, and (TEST only) the raw dy for the exact box test
+        const float dyr = pyv - y;
+        spy[lane] = dyr * isy;
+        if (TEST) spy[64 + lane] = dyr;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const float *sp = spy + rsub;
+    int soff = 0;
+    // trip counts up front: the loops below count down (one scalar add + compare + branch per iteration)
+    const int nrows = rend - rb + 1, ntrip = nrows / RPT;
+    const int voff_b = voff + halfb;
+    // Lanes outside the window sit the trips out (exec mask): the backward is co-limited by the CU's
+    // vector-memory pipe (two 768-byte loads per trip and wave, four SIMDs behind one L1), and idle
+    // lanes would fetch gradient pixels only to multiply them by zero.
+    if (S.inx) {
+    // UNROLL: two trips per iteration, four gradient loads in flight before the first is consumed.  Pays
+    // for windows of many trips (x8 and up); costs 18 VGPRs = two waves per SIMD, which small windows
+    // (x4, 6 trips) need more: the host picks the instantiation (gsasr_splat_backward).
+    int t = ntrip;
+    for (; UNROLL && t >= 2; t -= 2, soff += 4 * halfb, sp += 4 * RPI) {
+        const Grad6 g0 = bwd_load(rsrc, voff, voff_b, soff);
+        const Grad6 g1 = bwd_load(rsrc, voff, voff_b, soff + 2 * halfb);
+        const v2f n0 = {sp[0], sp[RPI]}, n1 = {sp[2 * RPI], sp[3 * RPI]};
+        const v2f w0 = TEST ? (v2f){sp[64], sp[64 + RPI]} : n0, w1 = TEST ? (v2f){sp[64 + 2 * RPI], sp[64 + 3 * RPI]} : n1;
+        bwd_trip<TEST, false>(R, g0, n0, w0, true, true, K0, nK1, rho_u, cr, cg, cb, dmax);
+        bwd_trip<TEST, false>(R, g1, n1, w1, true, true, K0, nK1, rho_u, cr, cg, cb, dmax);
+    }
+    if (!UNROLL && t > 0) {
+        // The plain loop runs ONE TRIP AHEAD: the two loads of trip k+1 are in flight while trip k is summed (two
+        // register sets used alternately: no copies).  Left to the compiler every trip was a dependent round trip
+        // -- issue, wait, sum -- and a wave's life at x4 is six of them: -5% at config 2, -4% on the config-5 crops,
+        // at 71 VGPRs (seven waves per SIMD kept).  Two trips ahead spills (72-VGPR budget): +8%; the same rotation
+        // in the unrolled instantiation: no gain (profiles/history/r03_bwd_experiments.txt).
+#define GSASR_TRIP(G) { const v2f n0 = {sp[0], sp[RPI]}; const v2f w0 = TEST ? (v2f){sp[64], sp[64 + RPI]} : n0; \
+                bwd_trip<TEST, false>(R, G, n0, w0, true, true, K0, nK1, rho_u, cr, cg, cb, dmax); sp += 2 * RPI; }
+        Grad6 ga = FIRST ? e0 : bwd_load(rsrc, voff, voff_b, soff);
+        soff += 2 * halfb;
+        for (; t >= 3; t -= 2) {
+            const Grad6 gb = bwd_load(rsrc, voff, voff_b, soff);
+            soff += 2 * halfb;
+            GSASR_TRIP(ga)
+            ga = bwd_load(rsrc, voff, voff_b, soff);
+            soff += 2 * halfb;
+            GSASR_TRIP(gb)
+        }
+        if (t == 2) {
+            const Grad6 gb = bwd_load(rsrc, voff, voff_b, soff);
+            soff += 2 * halfb;
+            GSASR_TRIP(ga)
+            GSASR_TRIP(gb)
+        } else {
+            GSASR_TRIP(ga)
+        }
+#undef GSASR_TRIP
+        t = 0;
+    }
+    for (; t > 0; --t, soff += 2 * halfb, sp += 2 * RPI) {   // (odd trip of the unrolled instantiation)
+        const v2f n0 = {sp[0], sp[RPI]};
+        const v2f w0 = TEST ? (v2f){sp[64], sp[64 + RPI]} : n0;
+        bwd_trip<TEST, false>(R, bwd_load(rsrc, voff, voff_b, soff), n0, w0, true, true, K0, nK1, rho_u, cr,
+                              cg, cb, dmax);
+    }
+    if (nrows % RPT) {  // ragged last trip: rows past the window are masked (reads past the slab give 0)
+        const int Yb = rb + ntrip * RPT;
+        const int Ya = Yb + rsub, Yc = Ya + RPI;
+        const int ia = min(Ya, rend) - rb, ic = min(Yc, rend) - rb;
+        const v2f n0 = {spy[ia], spy[ic]};
+        const v2f w0 = TEST ? (v2f){spy[64 + ia], spy[64 + ic]} : n0;
+        // (first block: the early set is this trip's when no full trip precedes it)
+        const Grad6 g = FIRST && ntrip == 0 ? e0 : bwd_load(rsrc, voff, voff_b, soff);
+        bwd_trip<TEST, true>(R, g, n0, w0, Ya <= rend, Yc <= rend, K0, nK1, rho_u, cr, cg, cb, dmax);
+    }
+    }
+}
+
 // LX = 16 / 21 / 32 / 64 columns: 4 / 3 / 2 / 1 row slots of lanes, i.e. 8 / 6 / 4 / 2 rows per trip.  LX = 21 (round 5; 63 lanes, the
 // last one idle) is for the windows of 17..21 columns -- over half of GSASR's at x4 since the data-derived cutoff narrowed them:
 // 6 rows per trip instead of 4, so a 20-row window takes 4 trips instead of 5-6 and 21 of 21 columns work instead of 21 of 32.
@@ -126,122 +232,75 @@ __device__ __forceinline__ void bwd_sweep(int c0, int bw, int r0, int r1, int la
                                           float cb, float cinv, float rho, float kappa, float isx, float isy,
                                           float *spy, float (&acc)[8])
 {
-    constexpr int RPI = 64 / LX, RPT = 2 * RPI;        // row slots of lanes; rows per trip
+    constexpr int RPI = 64 / LX;        // row slots of lanes
     constexpr float HALF_LOG2E = 0.72134752044448170368f;
     const int col = lane % LX, rsub = lane / LX;
     const unsigned pitchb = (unsigned)P.w * 12u;   // bytes per gradient row (< 2^19); all offsets below are unsigned 32 x 32 -> 64
     const float nK1 = -HALF_LOG2E * cinv;
-    // issued together with the px load below: one round trip for both tables instead of two dependent ones
-    const float py_first = pyt[min(r0 + lane, r1)];
-    for (int strip = 0; strip < bw; strip += 64) {
-        const int cc = strip + col;
-        const int X = c0 + min(cc, bw - 1);
-        const float dx = pxt[X] - x;
-        // lanes outside the window (or, with TEST, outside the dmax box in x) are switched off through K0:
-        // the exponent becomes -inf, v = 0 exactly, and every product with it is 0
-        const bool inx = cc < bw && (LX * RPI == 64 || rsub < RPI) && (!TEST || fabsf(dx) <= P.dmax);
-        const float u = dx * isx, rho_u = rho * u;
-        const float K0 = inx ? -HALF_LOG2E * u * u : -INFINITY;
-        BwdRow R;
+    const int halfb = (int)((unsigned)RPI * pitchb);
+    // A lane's state for the strip that starts at column `strip` of the window; pxv = its entry of the px table.
+    // Lanes outside the window (or, with TEST, outside the dmax box in x) are switched off through K0:
+    // the exponent becomes -inf, v = 0 exactly, and every product with it is 0
+    auto strip_col = [&](int strip) { return c0 + min(strip + col, bw - 1); };
+    auto strip_on = [&](int strip) { return strip + col < bw && (LX * RPI == 64 || rsub < RPI); };
+    auto strip_open = [&](int strip, int X, float pxv, BwdRow &R) {
+        BwdStrip S;
+        const float dx = pxv - x;
+        S.inx = strip_on(strip) && (!TEST || fabsf(dx) <= P.dmax);
+        S.u = dx * isx;
+        S.rho_u = rho * S.u;
+        S.K0 = S.inx ? -HALF_LOG2E * S.u * S.u : -INFINITY;
+        S.voff = (int)((unsigned)X * 12u + (unsigned)rsub * pitchb);
         R.m1 = R.m2 = R.k01 = (v2f){0.f, 0.f};
         R.ka2 = R.kb0 = R.kb1 = R.kb2 = 0.f;
-        const int voff = (int)((unsigned)X * 12u + (unsigned)rsub * pitchb);
-        const int halfb = (int)((unsigned)RPI * pitchb);
-        for (int rb = r0; rb <= r1; rb += 64) {
-            const int rend = min(r1, rb + 63);
-            __builtin_amdgcn_wave_barrier();
-            {   // per-row values of the block in LDS: v = dy/sy, and (TEST only) the raw dy for the exact box test
-                const float dyr = (rb == r0 ? py_first : pyt[min(rb + lane, r1)]) - y;
-                spy[lane] = dyr * isy;
-                if (TEST) spy[64 + lane] = dyr;
-            }
-            __builtin_amdgcn_wave_barrier();
-            const float *sp = spy + rsub;
-            // buffer resource over the slab from row `rb` on (offsets stay far below 2^31 within a 64-row block)
-            const char *blk = reinterpret_cast<const char *>(grad) + (unsigned long long)(unsigned)(rb - P.row0) * pitchb;
-            const unsigned long long left = (unsigned long long)(unsigned)(P.row1 - rb) * pitchb;
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<char *>(blk), 0, (int)(left < 0x7fffffffu ? left : 0x7fffffffu), 0x00020000);
-            int soff = 0;
-            // trip counts up front: the loops below count down (one scalar add + compare + branch per iteration)
-            const int nrows = rend - rb + 1, ntrip = nrows / RPT;
-            const int voff_b = voff + halfb;
-            // Lanes outside the window sit the trips out (exec mask): the backward is co-limited by the CU's
-            // vector-memory pipe (two 768-byte loads per trip and wave, four SIMDs behind one L1), and idle
-            // lanes would fetch gradient pixels only to multiply them by zero.
-            if (inx) {
-            // UNROLL: two trips per iteration, four gradient loads in flight before the first is consumed.  Pays
-            // for windows of many trips (x8 and up); costs 18 VGPRs = two waves per SIMD, which small windows
-            // (x4, 6 trips) need more: the host picks the instantiation (gsasr_splat_backward).
-            int t = ntrip;
-            for (; UNROLL && t >= 2; t -= 2, soff += 4 * halfb, sp += 4 * RPI) {
-                const Grad6 g0 = bwd_load(rsrc, voff, voff_b, soff);
-                const Grad6 g1 = bwd_load(rsrc, voff, voff_b, soff + 2 * halfb);
-                const v2f n0 = {sp[0], sp[RPI]}, n1 = {sp[2 * RPI], sp[3 * RPI]};
-                const v2f w0 = TEST ? (v2f){sp[64], sp[64 + RPI]} : n0, w1 = TEST ? (v2f){sp[64 + 2 * RPI], sp[64 + 3 * RPI]} : n1;
-                bwd_trip<TEST, false>(R, g0, n0, w0, true, true, K0, nK1, rho_u, cr, cg, cb, P.dmax);
-                bwd_trip<TEST, false>(R, g1, n1, w1, true, true, K0, nK1, rho_u, cr, cg, cb, P.dmax);
-            }
-            if (!UNROLL && t > 0) {
-                // The plain loop runs ONE TRIP AHEAD: the two loads of trip k+1 are in flight while trip k is summed (two
-                // register sets used alternately: no copies).  Left to the compiler every trip was a dependent round trip
-                // -- issue, wait, sum -- and a wave's life at x4 is six of them: -5% at config 2, -4% on the config-5 crops,
-                // at 71 VGPRs (seven waves per SIMD kept).  Two trips ahead spills (72-VGPR budget): +8%; the same rotation
-                // in the unrolled instantiation: no gain (profiles/history/r03_bwd_experiments.txt).
-#define GSASR_TRIP(G) { const v2f n0 = {sp[0], sp[RPI]}; const v2f w0 = TEST ? (v2f){sp[64], sp[64 + RPI]} : n0; \
-                        bwd_trip<TEST, false>(R, G, n0, w0, true, true, K0, nK1, rho_u, cr, cg, cb, P.dmax); sp += 2 * RPI; }
-                Grad6 ga = bwd_load(rsrc, voff, voff_b, soff);
-                soff += 2 * halfb;
-                for (; t >= 3; t -= 2) {
-                    const Grad6 gb = bwd_load(rsrc, voff, voff_b, soff);
-                    soff += 2 * halfb;
-                    GSASR_TRIP(ga)
-                    ga = bwd_load(rsrc, voff, voff_b, soff);
-                    soff += 2 * halfb;
-                    GSASR_TRIP(gb)
-                }
-                if (t == 2) {
-                    const Grad6 gb = bwd_load(rsrc, voff, voff_b, soff);
-                    soff += 2 * halfb;
-                    GSASR_TRIP(ga)
-                    GSASR_TRIP(gb)
-                } else {
-                    GSASR_TRIP(ga)
-                }
-#undef GSASR_TRIP
-                t = 0;
-            }
-            for (; t > 0; --t, soff += 2 * halfb, sp += 2 * RPI) {   // (odd trip of the unrolled instantiation)
-                const v2f n0 = {sp[0], sp[RPI]};
-                const v2f w0 = TEST ? (v2f){sp[64], sp[64 + RPI]} : n0;
-                bwd_trip<TEST, false>(R, bwd_load(rsrc, voff, voff_b, soff), n0, w0, true, true, K0, nK1, rho_u, cr,
-                                      cg, cb, P.dmax);
-            }
-            if (nrows % RPT) {  // ragged last trip: rows past the window are masked (reads past the slab give 0)
-                const int Yb = rb + ntrip * RPT;
-                const int Ya = Yb + rsub, Yc = Ya + RPI;
-                const int ia = min(Ya, rend) - rb, ic = min(Yc, rend) - rb;
-                const v2f n0 = {spy[ia], spy[ic]};
-                const v2f w0 = TEST ? (v2f){spy[64 + ia], spy[64 + ic]} : n0;
-                bwd_trip<TEST, true>(R, bwd_load(rsrc, voff, voff_b, soff), n0, w0, Ya <= rend, Yc <= rend, K0, nK1,
-                                     rho_u, cr, cg, cb, P.dmax);
-            }
-            }
-        }
-        // Expand the column's three sums M0 = sum q, N1 = sum q B, N2 = sum q B^2 (u = dx/sx is a lane constant,
-        // A = u - rho v = u kappa - rho B, v = B + rho u):  sum qA, sum qB, sum q u A, sum q v B, sum q A B.
-        // Every difference is formed between quantities of its own size, so nothing cancels as |rho| -> 1
-        // (the plain monomial moments sum q dx^2, q dx dy, q dy^2 lose 1/(1-rho) digits there).
-        const float Kr = R.k01.x + R.kb0, Kg = R.k01.y + R.kb1, Kb = R.ka2 + R.kb2;
-        const float M0 = fmaf(Kb, cb, fmaf(Kg, cg, Kr * cr)), N1 = R.m1.x + R.m1.y, N2 = R.m2.x + R.m2.y;
-        // (switched-off lanes have M0 = N1 = N2 = 0, but their u is meaningless: use 0)
-        const float ue = inx ? u : 0.f, uk = ue * kappa;
-        const float sA = uk * M0 - rho * N1;
-        const float e[8] = {sA, N1, ue * sA, N2 + rho * ue * N1, uk * N1 - rho * N2,
-                            Kr, Kg, Kb};
-        // the first (usually only) 64-column strip assigns, so acc[] is not live during its sweep
+        return S;
+    };
+    // EARLY (the plain instantiation): the wave's first vector round trip carries BOTH tables AND the gradient pixels of the
+    // first trip.  Their addresses need the record alone -- c0, bw, r0, the pitch -- so they do not wait for the tables as they
+    // used to (record -> tables -> gradient was three dependent trips before the first FMA; now two): k_render_bwd -2.7% at
+    // config 2.  Only what is known without the tables can mask them: with TEST a lane outside the dmax box in x fetches its
+    // pixels and drops them.  Not in the unrolled instantiation: the first two trips' loads issued early cost it 2-4 VGPRs and
+    // spills at its six waves and made it 6-7% SLOWER (forced on config 2 30.4 -> 32.3 us, x8 1 339 -> 1 431 us;
+    // profiles/early_loads_ab.txt); it starts its walk at the first block, within one VGPR of what it was, and measures level.
+    constexpr bool EARLY = !UNROLL;
+    const int X0 = strip_col(0);
+    const int voff0 = (int)((unsigned)X0 * 12u + (unsigned)rsub * pitchb);
+    const __amdgpu_buffer_rsrc_t rsrc0 = bwd_rsrc(grad, r0, P, pitchb);
+    const float py_first = pyt[min(r0 + lane, r1)];
+    const float px_first = pxt[X0];
+    Grad6 e0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (EARLY && strip_on(0)) e0 = bwd_load(rsrc0, voff0, voff0 + halfb, 0);
+    BwdRow R;
+    BwdStrip S = strip_open(0, X0, px_first, R);
+    if constexpr (EARLY) bwd_block<TEST, LX, UNROLL, true>(R, S, r0, r1, lane, py_first, y, isy, rsrc0, halfb, e0, nK1, cr, cg, cb, P.dmax, spy);
+    // Every other block, in the order strip by strip, 64-row block by block.  Invariant at the top of the body: S and R are the
+    // open strip's state and sums, and the blocks of that strip before row rb are summed; rb > r1 closes the strip (its sums are
+    // expanded into acc[]) and opens the next one at rb = r0, or ends the sweep.  With EARLY the walk starts behind the first block.
+    for (int strip = 0, rb = EARLY ? r0 + 64 : r0;; rb += 64) {
+        if (rb > r1) {
+            // Expand the column's three sums M0 = sum q, N1 = sum q B, N2 = sum q B^2 (u = dx/sx is a lane constant,
+            // A = u - rho v = u kappa - rho B, v = B + rho u):  sum qA, sum qB, sum q u A, sum q v B, sum q A B.
+            // Every difference is formed between quantities of its own size, so nothing cancels as |rho| -> 1
+            // (the plain monomial moments sum q dx^2, q dx dy, q dy^2 lose 1/(1-rho) digits there).
+            const float Kr = R.k01.x + R.kb0, Kg = R.k01.y + R.kb1, Kb = R.ka2 + R.kb2;
+            const float M0 = fmaf(Kb, cb, fmaf(Kg, cg, Kr * cr)), N1 = R.m1.x + R.m1.y, N2 = R.m2.x + R.m2.y;
+            // (switched-off lanes have M0 = N1 = N2 = 0, but their u is meaningless: use 0)
+            const float ue = S.inx ? S.u : 0.f, uk = ue * kappa;
+            const float sA = uk * M0 - rho * N1;
+            const float e[8] = {sA, N1, ue * sA, N2 + rho * ue * N1, uk * N1 - rho * N2,
+                                Kr, Kg, Kb};
+            // the first (usually only) 64-column strip assigns, so acc[] is not live during its sweep
 #pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = strip == 0 ? e[k] : acc[k] + e[k];
+            for (int k = 0; k < 8; ++k) acc[k] = strip == 0 ? e[k] : acc[k] + e[k];
+            strip += 64;
+            if (strip >= bw) break;
+            const int X = strip_col(strip);
+            S = strip_open(strip, X, pxt[X], R);
+            rb = r0;
+        }
+        const float pyv = rb == r0 ? py_first : pyt[min(rb + lane, r1)];
+        bwd_block<TEST, LX, UNROLL, false>(R, S, rb, r1, lane, pyv, y, isy, bwd_rsrc(grad, rb, P, pitchb), halfb, e0, nK1, cr, cg, cb,
+                                           P.dmax, spy);
     }
 }
 
