@@ -1026,6 +1026,18 @@ def _loss_scratch(d: Dims, dev) -> torch.Tensor:
     return torch.empty(n // 4, dtype=torch.float32, device=dev)
 
 
+def _loss_grad(d0: Dims, shape, dev) -> torch.Tensor:
+    """A fresh buffer for the image gradient a fused loss writes.  The forward stores a sample's own pixels only, and the
+    Gaussian-stationary backward kernels load up to seven rows past a window's last row in their last trip and switch them off by
+    a factor of exactly 0 (bwd_block, splat_bwd_sweep.h): below a sample shorter than its slot those rows are padding nobody
+    wrote, and a NaN left there by whoever had the memory before makes 0 * NaN.  So a canvas WITH such padding starts as zeros;
+    every other shape -- one image, a batch of crops of whole 16-row tiles -- has none and stays uninitialised."""
+    pad = d0.__dict__.get("_loss_pad")
+    if pad is None:
+        pad = d0.__dict__["_loss_pad"] = d0.batch > 1 and any(d0.sample_hw[2 * b] < d0.slot for b in range(d0.batch))
+    return (torch.zeros if pad else torch.empty)(shape, dtype=torch.float32, device=dev)
+
+
 def forward_loss(p: Plan, target: torch.Tensor, kind: int, norm: int = 0, weight: float = 1.0, eps: float = 1e-12,
                  chw: bool = False, grad_chw: bool = False, want_grad: bool = True, want_image: bool = False, flags: int = 0,
                  grad: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
@@ -1053,7 +1065,7 @@ def forward_loss(p: Plan, target: torch.Tensor, kind: int, norm: int = 0, weight
             if _chk(grad, "grad") == 0 or tuple(grad.shape) != (planar if grad_chw else hwc) or grad.device != dev:
                 raise RuntimeError(f"grad has shape {tuple(grad.shape)}, expected {planar if grad_chw else hwc}")
         elif want_grad:
-            grad = torch.empty(planar if grad_chw else hwc, dtype=torch.float32, device=dev)
+            grad = _loss_grad(d0, planar if grad_chw else hwc, dev)
         img = torch.empty(planar if chw else hwc, dtype=torch.float32, device=dev) if want_image else None
         loss = torch.empty(1 + B, dtype=torch.float32, device=dev)
         if scratch is None:
@@ -1088,7 +1100,7 @@ def _step_loss(shape, pp: int, src, target: torch.Tensor, kind: int, norm: int, 
         grad = None
         if not (d.flags & FLAG_FORWARD_ONLY):
             hwc = (B, d.slot, d.w, 3) if d.batch > 1 else (d.h, d.w, 3)
-            grad = torch.empty(planar if d.flags & FLAG_CHW_GRAD else hwc, dtype=torch.float32, device=dev)
+            grad = _loss_grad(d0, planar if d.flags & FLAG_CHW_GRAD else hwc, dev)
         loss = torch.empty(1 + B, dtype=torch.float32, device=dev)
         scratch = torch.empty(nscratch // 4, dtype=torch.float32, device=dev)
         img = torch.empty(planar, dtype=torch.float32, device=dev) if want_image else None

@@ -373,7 +373,10 @@ GSASR_API int gsasr_step_backward_view(const float *gs_parameters, const float *
  *   GSASR_LOSS_MEAN   c_b = weight / (3 h_b w_b B) (one fp32 division by the integer product),  L_b = weight / (3 h_b w_b) * sum phi,
  *                     L = (1 / B) sum_b L_b
  *   GSASR_LOSS_SUM    c_b = weight,  L_b = weight * sum phi,  L = sum_b L_b
- *   grad_img[pixel, k] = c_b * phi'(d) on the sample's own pixels; the padding of a slot is not written (no backward reads it)
+ *   grad_img[pixel, k] = c_b * phi'(d) on the sample's own pixels; the padding of a slot is not written.  No backward takes a
+ *                     term from it, but the Gaussian-stationary kernels LOAD up to seven rows below a window's last row and
+ *                     multiply them by exactly 0: the rows below a sample shorter than its slot must hold finite values (zero
+ *                     the buffer once; a NaN left there turns into a NaN gradient)
  *   loss[0] = L, loss[1 + b] = L_b
  * Plain IEEE arithmetic, no special handling of NaN or Inf: a NaN pixel or target makes its sample's loss NaN; its gradient is
  * NaN for MSE and Charbonnier and 0 for L1 (both comparisons are false).

@@ -345,6 +345,34 @@ def test_parameter_gradients_batch_and_batched_windows(kernel, source, bounded, 
     gsp.deferred_asserts.flush()
 
 
+def test_stale_memory_below_a_short_sample_does_not_reach_the_gradient(dev):
+    """The fused forward writes a sample's own pixels of the gradient buffer only, and the Gaussian-stationary backward loads up
+    to seven rows below a window's last row to multiply them by 0 (bwd_block's last trip).  Below a sample shorter than its slot
+    those rows are padding: whatever the memory held before.  The caching allocator is primed with NaN blocks of the buffer's
+    size, as a test that fills its gradient buffers with NaN leaves it; the host path must hand the kernels a buffer whose
+    padding is finite.  (Shapes of tests/test_ssim_loss_gpu.py::test_fused_batch_and_batched_windows, where it showed.)"""
+    from gsasr_amd import gaussian_splatting as gsp, synthetic
+    sizes = [(11, 16), (24, 40), (17, 11)]
+    B, slot, w = len(sizes), 32, 40
+    p = torch.stack([synthetic.gs_parameters(12, 20, seed=40 + b) for b in range(B)]).to(dev)
+    scales, sms = [2.0] * B, [(2.0, 2.0)] * B
+    t = torch.rand(B, 3, 24, w, generator=torch.Generator().manual_seed(1)).to(dev)
+
+    def run(poison):
+        q = p.clone().requires_grad_(True)
+        if poison:
+            junk = [torch.full((B * slot * w * 3,), float("nan"), device=dev) for _ in range(16)]
+            del junk
+        gsp.generate_2D_gaussian_splatting_batch_loss(sizes, q, scales, sms, t, loss="l1", dmax=0.3).backward()
+        return q.grad
+
+    for kernel in ("gaussian", "tile", "home"):
+        with forced_backward(kernel):
+            dirty, clean = run(True), run(False)
+        assert bool(torch.isfinite(dirty).all()), kernel
+        assert float((dirty - clean).abs().max()) <= 1e-5 * float(clean.abs().max()), kernel      # (the same sums, atomics in another order)
+
+
 @pytest.mark.parametrize("shape", ["dense-16-per-LR-px", "config2"])
 def test_parameter_gradients_dense_and_config2(shape, dev):
     """one dense shape (16 Gaussians per LR pixel, a 48^2 LR crop at x4) and config 2 at full size (256^2 LR x4: 1024^2,
