@@ -95,6 +95,16 @@ class Batch(ctypes.Structure):
                 ("flags", ctypes.c_uint), ("scratch", ctypes.c_void_p)]
 
 
+class WindowAttn(ctypes.Structure):
+    """struct gsasr_window_attn: the decoder's window attention with its relative-position bias (gsasr_window_attn_forward / _backward)"""
+    _fields_ = [("windows", ctypes.c_int), ("heads", ctypes.c_int), ("nq", ctypes.c_int), ("nk", ctypes.c_int),
+                ("head_dim", ctypes.c_int), ("table_rows", ctypes.c_int), ("scale", ctypes.c_float), ("flags", ctypes.c_uint),
+                ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("table", ctypes.c_void_p),
+                ("index", ctypes.c_void_p), ("out", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("grad_out", ctypes.c_void_p),
+                ("g_q", ctypes.c_void_p), ("g_k", ctypes.c_void_p), ("g_v", ctypes.c_void_p), ("g_table", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p)]
+
+
 RESIZE_NO_ANTIALIAS, RESIZE_ACCUMULATE, RESIZE_SHARED_SCALE = 1, 2, 4     # GSASR_RESIZE_*
 BATCH_HFLIP, BATCH_VFLIP, BATCH_TRANSPOSE = 1, 2, 4     # GSASR_BATCH_* (aug bits)
 BATCH_BGR, BATCH_NO_ANTIALIAS = 1, 2                    # GSASR_BATCH_* (flags)
@@ -105,7 +115,7 @@ LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
 _vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
-_rzp, _btp = ctypes.POINTER(Resize), ctypes.POINTER(Batch)
+_rzp, _btp, _wap = ctypes.POINTER(Resize), ctypes.POINTER(Batch), ctypes.POINTER(WindowAttn)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -181,6 +191,10 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_batch_scratch_bytes": (_sz, [_btp]),
     "gsasr_batch_make": (_i, [_btp, _vp]),
     "gsasr_batch_pick": (_i, [_btp, _vp, _i, _vp, _vp]),
+    # the decoder's window attention (gsasr_window_attn)
+    "gsasr_window_attn_scratch_bytes": (_sz, [_wap]),
+    "gsasr_window_attn_forward": (_i, [_wap, _vp]),
+    "gsasr_window_attn_backward": (_i, [_wap, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1195,6 +1209,60 @@ def ssim_loss(img: torch.Tensor, target: torch.Tensor, sizes=None, weight: float
         d.loss, d.scratch = loss.data_ptr(), scratch.data_ptr()
         check(lib().gsasr_ssim_loss(ctypes.byref(d), _stream(dev)), "gsasr_ssim_loss")
     return loss, grad
+
+
+# ---- the decoder's window attention (include/gsasr_splat.h: gsasr_window_attn) ----------------------------------
+def make_window_attn(windows: int, heads: int, nq: int, nk: int, head_dim: int, table_rows: int, scale: float) -> WindowAttn:
+    """a gsasr_window_attn descriptor without pointers"""
+    d = WindowAttn(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(table_rows))
+    d.scale, d.flags = float(scale), 0
+    return d
+
+
+def _window_attn(q, k, v, table, index, scale: float) -> WindowAttn:
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (table, "bias_table")):
+        _chk(t, name)
+    if index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous():
+        raise RuntimeError("bias_index must be a contiguous int32 CUDA tensor")
+    heads = int(table.shape[1])
+    d = make_window_attn(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, table.shape[0], scale)
+    d.q, d.k, d.v, d.table, d.index = q.data_ptr(), k.data_ptr(), v.data_ptr(), table.data_ptr(), index.data_ptr()
+    return d
+
+
+def window_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table: torch.Tensor, index: torch.Tensor, scale: float,
+                        want_stats: bool = True):
+    """gsasr_window_attn_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `table` `[T,H]` fp32 contiguous, `index` int32
+    `[nq,nk]` (validated by the caller) -> (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None)"""
+    d = _window_attn(q, k, v, table, index, scale)
+    dev = q.device
+    with _on(dev):
+        out = torch.empty_like(q)
+        stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
+        d.out, d.stats = out.data_ptr(), None if stats is None else stats.data_ptr()
+        check(lib().gsasr_window_attn_forward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_forward")
+    return out, stats
+
+
+def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_out, need=(True, True, True, True)):
+    """gsasr_window_attn_backward -> (g_q, g_k, g_v, g_table), None where `need` is False"""
+    d = _window_attn(q, k, v, table, index, scale)
+    for t, name in ((out, "out"), (stats, "stats"), (grad_out, "grad_out")):
+        _chk(t, name)
+    if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq):
+        raise RuntimeError("out / grad_out must have q's shape and stats [W,H,nq]")
+    dev = q.device
+    with _on(dev):
+        grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, table), need)]
+        d.out, d.stats, d.grad_out = out.data_ptr(), stats.data_ptr(), grad_out.data_ptr()
+        d.g_q, d.g_k, d.g_v, d.g_table = [None if g is None else g.data_ptr() for g in grads]
+        n = int(lib().gsasr_window_attn_scratch_bytes(ctypes.byref(d)))
+        if n == 0:
+            check(-1, "gsasr_window_attn_scratch_bytes")
+        scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        d.scratch = scratch.data_ptr()
+        check(lib().gsasr_window_attn_backward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_backward")
+    return tuple(grads)
 
 
 # ---- validation metrics of an 8-bit picture (include/gsasr_splat.h: gsasr_metrics) -----------------------------

@@ -1,0 +1,167 @@
+"""The window attention of GSASR's Fea2GS decoder (`WindowCrossAttn` and `GSSelfAttn`, utils/fea2gs.py:162-194, 321-350: 38
+layers in every shipped configuration), fused:
+
+    window_attention(q, k, v, bias_table, bias_index, scale=None)      # == window_attention_torch, one HIP call
+    use_hip_attention(model)                                            # switch a model's attention modules to it
+    constant_key_attention(mha, row)                                    # the layers' attention to the scale embedding, closed form
+
+CUDA tensors: gsasr_window_attn_forward / _backward (hand-written HIP, csrc/splat_attn.hip) as one autograd node on the current
+stream, or an error -- no torch fallback.  CPU tensors: the torch expression `window_attention_torch` below, which is also the
+contract.  include/gsasr_splat.h has the formulas.  fp32 only: under autocast the inputs are cast to fp32 at the node's boundary
+(bf16 compute is not implemented).
+"""
+import types
+import weakref
+
+import torch
+
+from ._amp import fp32_boundary_bwd, fp32_boundary_fwd
+
+MAX_TOKENS = 256        # queries or keys per window
+MAX_HEAD_DIM = 32
+
+
+def window_attention_torch(q, k, v, bias_table, bias_index, scale=None):
+    """`q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]` (channel h*d + j = head h, component j), `bias_table` `[T,H]`, `bias_index`
+    integer `[nq,nk]` -> `[W,nq,H*d]`: softmax(scale q k^T + bias_table[bias_index]) v per window and head, in the inputs' dtype"""
+    W, nq, C = q.shape
+    nk, H = k.shape[1], bias_table.shape[1]
+    d = C // H
+    scale = d ** -0.5 if scale is None else scale
+    qh = q.view(W, nq, H, d).permute(0, 2, 1, 3) * scale
+    kh = k.view(W, nk, H, d).permute(0, 2, 1, 3)
+    vh = v.view(W, nk, H, d).permute(0, 2, 1, 3)
+    attn = qh @ kh.transpose(-2, -1) + bias_table[bias_index.long()].permute(2, 0, 1)
+    return (torch.softmax(attn, dim=-1) @ vh).transpose(1, 2).reshape(W, nq, C)
+
+
+_INDEX_CACHE = {}       # id(index tensor) -> (weak reference, its version, table rows, device, the int32 copy)
+
+
+def _checked_index(bias_index, rows: int, device):
+    """the contiguous int32 copy of `bias_index` on `device`, its range checked against `rows` -- once per index tensor (the
+    check reads the extrema on the host; a training step hits the cache and has no host synchronisation)"""
+    key = id(bias_index)
+    hit = _INDEX_CACHE.get(key)
+    if hit is not None and hit[0]() is bias_index and hit[1:4] == (bias_index._version, rows, device):
+        return hit[4]
+    lo, hi = (int(x) for x in torch.aminmax(bias_index)) if bias_index.numel() else (0, 0)
+    if lo < 0 or hi >= rows:
+        raise ValueError(f"bias_index has values in [{lo}, {hi}], bias_table {rows} rows")
+    copy = bias_index.detach().to(device=device, dtype=torch.int32).contiguous()
+    if len(_INDEX_CACHE) > 4096:        # (dead entries of models long gone)
+        for stale in [i for i, e in _INDEX_CACHE.items() if e[0]() is None]:
+            del _INDEX_CACHE[stale]
+    _INDEX_CACHE[key] = (weakref.ref(bias_index), bias_index._version, rows, device, copy)
+    return copy
+
+
+class _WindowAttention(torch.autograd.Function):
+    """(q, k, v, table, int32 index, scale, keep) -> out; `keep`: save the row statistic for a backward"""
+
+    @staticmethod
+    @fp32_boundary_fwd
+    def forward(ctx, q, k, v, table, index, scale, keep):
+        from . import _cabi
+        q, k, v, table = q.contiguous(), k.contiguous(), v.contiguous(), table.contiguous()
+        out, stats = _cabi.window_attn_forward(q, k, v, table, index, scale, want_stats=keep)
+        if keep:
+            ctx.save_for_backward(q, k, v, table, index, out, stats)
+            ctx.scale = scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @fp32_boundary_bwd
+    def backward(ctx, grad_out):
+        from . import _cabi
+        q, k, v, table, index, out, stats = ctx.saved_tensors
+        g = _cabi.window_attn_backward(q, k, v, table, index, ctx.scale, out, stats, grad_out.to(torch.float32).contiguous(),
+                                       need=tuple(ctx.needs_input_grad[:4]))
+        return (*g, None, None, None)
+
+
+def window_attention(q, k, v, bias_table, bias_index, scale=None):
+    """softmax(scale q k^T + bias_table[bias_index]) v per window and head (`window_attention_torch` has the shapes), as ONE
+    differentiable call: gradients to `q`, `k`, `v` and `bias_table`.  Limits: 1 <= nq, nk <= 256, 1 <= d <= 32; anything else,
+    a non-integer or out-of-range index, or mismatched shapes: ValueError before any launch.  `scale`: default d ** -0.5."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (bias_table, "bias_table")):
+        if not (torch.is_tensor(t) and t.dtype.is_floating_point):
+            raise ValueError(f"{name} must be a floating-point tensor")
+    if not torch.is_tensor(bias_index) or bias_index.dtype.is_floating_point or bias_index.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError("bias_index must be an integer tensor")
+    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: expected [W,nq,C], [W,nk,C], [W,nk,C]")
+    W, nq, C = (int(s) for s in q.shape)
+    nk = int(k.shape[1])
+    if bias_table.dim() != 2 or bias_table.shape[0] < 1 or bias_table.shape[1] < 1:
+        raise ValueError(f"bias_table has shape {tuple(bias_table.shape)}, expected [T,H]")
+    T, H = (int(s) for s in bias_table.shape)
+    if C % H or C == 0:
+        raise ValueError(f"{C} channels are not {H} heads (the bias_table's columns) times a head dimension")
+    d = C // H
+    if W < 1 or not 1 <= nq <= MAX_TOKENS or not 1 <= nk <= MAX_TOKENS:
+        raise ValueError(f"need W >= 1 and 1 <= nq, nk <= {MAX_TOKENS} (got W {W}, nq {nq}, nk {nk})")
+    if d > MAX_HEAD_DIM:
+        raise ValueError(f"head dimension {d} exceeds {MAX_HEAD_DIM}")
+    if tuple(bias_index.shape) != (nq, nk):
+        raise ValueError(f"bias_index has shape {tuple(bias_index.shape)}, expected [{nq}, {nk}]")
+    scale = float(d ** -0.5 if scale is None else scale)
+    if not (q.device == k.device == v.device == bias_table.device):
+        raise ValueError("q, k, v and bias_table must be on one device")
+    index = _checked_index(bias_index, T, q.device)
+    if not q.is_cuda:
+        return window_attention_torch(q, k, v, bias_table, index, scale)
+    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, bias_table))
+    q, k, v, bias_table = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, bias_table))
+    return _WindowAttention.apply(q, k, v, bias_table, index, scale, keep)
+
+
+_ATTRS = ("qhead", "khead", "vhead", "proj", "relative_position_bias_table", "relative_position_index", "num_heads")
+
+
+def _module_forward(self, gs, feat=None):
+    """the module's own Linears around window_attention: `forward(gs)` (self attention) or `forward(gs, feat)` (keys and values
+    from `feat`)"""
+    src = gs if feat is None else feat
+    c = gs.shape[-1]
+    scale = getattr(self, "scale", None)
+    x = window_attention(self.qhead(gs), self.khead(src), self.vhead(src), self.relative_position_bias_table,
+                         self.relative_position_index, (c // self.num_heads) ** -0.5 if scale is None else scale)
+    return self.proj(x)
+
+
+def use_hip_attention(model) -> int:
+    """give every module of `model` that carries the decoder's attention attributes (qhead, khead, vhead, proj,
+    relative_position_bias_table, relative_position_index, num_heads: WindowCrossAttn and GSSelfAttn) a `forward` that runs
+    its three Linears, `window_attention` and `proj` with the module's own parameters -> the number of modules switched.
+    Parameters, buffers and state dicts are untouched."""
+    n = 0
+    for m in model.modules():
+        if all(hasattr(m, a) for a in _ATTRS):
+            m.forward = types.MethodType(_module_forward, m)
+            n += 1
+    return n
+
+
+def constant_key_attention(mha, row):
+    """`mha(x, keys, keys)[0][:, :1]` for ANY query `x` when every key / value row of a batch element is the same `row`
+    (`[B,c]` or `[B,1,c]`) -> `[B,1,c]`: identical keys give every query uniform weights, so each head returns its value
+    projection of `row` and the output is out_proj(v_proj(row)), independent of the query (which gets a zero gradient).
+    Differentiable in `row` and in `mha`'s value and output projections.  Valid ONLY because the keys are identical.
+    Needs batch_first, no dropout, no bias_k / bias_v / zero-attention rows (and is called without masks)."""
+    if not isinstance(mha, torch.nn.MultiheadAttention):
+        raise ValueError("mha must be an nn.MultiheadAttention")
+    if not mha.batch_first or mha.dropout != 0 or mha.bias_k is not None or mha.bias_v is not None or mha.add_zero_attn:
+        raise ValueError("constant_key_attention needs batch_first=True, dropout == 0 and no bias_k / bias_v / add_zero_attn")
+    if row.dim() == 2:
+        row = row[:, None, :]
+    c = mha.embed_dim
+    if row.dim() != 3 or row.shape[1] != 1 or row.shape[2] != (c if mha._qkv_same_embed_dim else mha.vdim):
+        raise ValueError(f"row has shape {tuple(row.shape)}, expected [B,1,{c}]")
+    if mha._qkv_same_embed_dim:
+        wv = mha.in_proj_weight[2 * c:]
+    else:
+        wv = mha.v_proj_weight
+    bv = None if mha.in_proj_bias is None else mha.in_proj_bias[2 * c:]
+    return mha.out_proj(torch.nn.functional.linear(row, wv, bv))

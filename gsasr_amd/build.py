@@ -16,7 +16,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 # the translation units of the library (csrc/gsasr_splat.hip is the same code as ONE unit: the micro-benchmark tools/mb.hip builds that)
 PARTS = ["splat_api", "splat_plan", "splat_forward", "splat_backward", "splat_backward_home", "splat_step", "splat_sampled", "splat_shard", "splat_ssim",
-         "splat_metrics", "splat_resize", "splat_data"]
+         "splat_metrics", "splat_resize", "splat_data", "splat_attn"]
 INC = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG, "lib")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")

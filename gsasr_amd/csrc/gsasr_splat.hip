@@ -54,8 +54,12 @@
 //                        adjoint in gather form (GSASR's degradation, matlab_functions.py; splat_resize.hip).
 //   data     k_batch_crop/d4/pick   training batches from decoded 8-bit images: crop, /255, bicubic LR, flips / transposition,
 //                        BGR -> RGB, planar, zero padding or sampled pixels (GSASR's dataset __getitem__; splat_data.hip).
+//   attn     k_attn_fwd/bwd_q/bwd_kv/table_sum   the Fea2GS decoder's window attention with its relative-position bias, fused: one
+//                        workgroup per (window, head), K / V in LDS, scores in registers, and its gradient in q, k, v and the
+//                        bias table (WindowCrossAttn / GSSelfAttn; splat_attn.hip).
 //
-// No MFMA: this is gather/scatter-accumulate with one transcendental per pair, not a contraction.
+// No MFMA in the rasterizer: it is gather/scatter-accumulate with one transcendental per pair, not a contraction (the attention
+// part is one, and runs on the exact-fp32 MFMA).
 // This file is the WHOLE library as one translation unit (tools/mb.hip includes it); gsasr_amd/build.py compiles the parts
 // below separately and links them.
 #include "splat_common.h"
@@ -71,3 +75,4 @@
 #include "splat_metrics.hip"
 #include "splat_resize.hip"
 #include "splat_data.hip"
+#include "splat_attn.hip"

@@ -1,0 +1,527 @@
+// splat_attn.hip -- the window attention of GSASR's Fea2GS decoder (WindowCrossAttn / GSSelfAttn, utils/fea2gs.py:162-194, 321-350)
+// as fused kernels: per window w and head h
+//     out[w, :, h] = softmax(scale q[w, :, h] k[w, :, h]^T + table[index, h]) v[w, :, h]
+// with q, k, v and out in the interleaved [windows, tokens, heads * head_dim] layout the Linears produce, and its gradient in
+// q, k, v and the table: gsasr_window_attn_forward / _backward (one translation unit of libgsasr_splat.so; include/gsasr_splat.h
+// has the contract).
+//
+// All products run on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32 (lane l supplies A[row l & 15][k = l >> 4] and
+// B[k = l >> 4][col l & 15]; it receives D[row 4 (l >> 4) + reg][col l & 15], reg = 0..3).  The head's slice of a window is
+// zero-padded to 32 columns in LDS rows of 36 floats: the 4 x 16 reads of a B operand (row 4 (l >> 4) + r, column l & 15) are
+// conflict-free, the 16 x 4 reads of an A operand (row l & 15, column 4 s + (l >> 4)) collide two by two on ds_read_b32's 32 banks
+// (DESIGN.md 3.2i has the counters and the 8-byte form that would not).  The head's column of the table is staged in LDS as
+// well (tables up to ATT_TAB_LDS rows), so a bias is an LDS read behind one 16-byte load of four indices.
+//
+//   k_attn_fwd     one workgroup (4 waves; 3 when the query tiles divide by 3 and not by 4) per (window, head), K and V in LDS.
+//                  A wave takes 16 queries at a time and computes
+//                  S^T = K (scale Q)^T: the lane then holds, for ITS query l & 15, the keys 16 t + 4 (l >> 4) + r of every key
+//                  tile t -- the whole score row is in the registers of four lanes, so the softmax is exact (one maximum, one
+//                  sum, two xor shuffles each), the bias is gathered from table[index[i, j], h] into the same registers, and
+//                  P is already the A operand of O = P V when the MFMA's k index g is read as key 16 t + 4 g + r (V's rows
+//                  are fetched in that order): no score leaves the registers.  Optional row statistic log-sum-exp.
+//   k_attn_bwd_q   same geometry; P recomputed from the statistic, dP^T = V dO^T, dS = P (dP - delta) with
+//                  delta = rowsum(dO o O), dq = scale dS K with dS as the A operand in place.  d table: dS is binned with LDS
+//                  float adds into the workgroup's copy of the head's table column; a workgroup walks the windows
+//                  b, b + stride, ... of its head and writes ONE partial column at the end (k_attn_table_sum adds the
+//                  partials in a fixed order).  Tables above ATT_TAB_LDS rows: global float atomics on a zeroed g_table.
+//   k_attn_bwd_kv  one workgroup per (window, head) with scale Q, dO, the statistic and delta in LDS; a wave takes 16 KEYS at a
+//                  time and computes S = (scale Q) K^T and dP = dO V^T with the key on the lane: P^T and dS^T are then the A
+//                  operands of dv = P^T dO and dk = dS^T (scale Q) in place.
+// Every workgroup owns its window-head whole: dq, dk, dv are written once, without atomics, and two runs give the same bits.
+// Both backward kernels form S exactly as the forward did (same chain, then the bias): the statistic is of those bits.
+// The table gradient depends on the order of the LDS float adds.
+#include "splat_common.h"
+
+using namespace gsasr_detail;
+
+namespace {
+
+typedef float att_f4 __attribute__((ext_vector_type(4)));
+
+constexpr int ATT_LD = 36;            // floats per LDS row (32 columns + 4: see above)
+constexpr int ATT_MAX_N = 256;        // tokens per window, queries or keys
+constexpr int ATT_MAX_D = 32;         // head dimension
+constexpr int ATT_TAB_LDS = 4096;     // table rows up to which d table is binned in LDS
+constexpr int ATT_TAB_WG = 256;       // window slots (workgroups per head) of k_attn_bwd_q = partial columns per head, at most
+
+struct AttnArgs {
+    const float *q, *k, *v, *table, *out, *grad_out;
+    const int *index;
+    float *o, *stats, *g_q, *g_k, *g_v, *g_table, *part;
+    int windows, heads, nq, nk, d, rows, wslots;
+    bool vec;       // index rows can be read 16 bytes at a time
+    float scale;
+};
+
+__device__ __forceinline__ att_f4 att_mfma(float a, float b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// rows [0, n) x columns [0, d) of the head's slice of `src` (row pitch C floats) times `mul` into s[rows_pad][ATT_LD], zero elsewhere
+__device__ __forceinline__ void att_stage(float *s, const float *__restrict__ src, int n, int rows_pad, int d, int C, float mul)
+{
+    // eight loads in flight per thread before the first LDS store (one load per round trip made the staging the kernels' largest cost)
+    const int nthr = blockDim.x;      // (a multiple of 64)
+    for (int e0 = threadIdx.x; e0 < rows_pad * 32; e0 += 8 * nthr) {
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + nthr * u, j = e >> 5, c = e & 31;
+            x[u] = (j < n && c < d) ? src[(size_t)j * C + c] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + nthr * u;
+            if (e < rows_pad * 32) s[(e >> 5) * ATT_LD + (e & 31)] = x[u] * mul;
+        }
+    }
+}
+
+// head h's column of the table into LDS (TLDS kernels: table_rows <= ATT_TAB_LDS), so that a bias is an LDS read
+__device__ __forceinline__ void att_stage_table(float *s_tb, const AttnArgs &A, int h)
+{
+    for (int t = threadIdx.x; t < A.rows; t += blockDim.x) s_tb[t] = A.table[(size_t)t * A.heads + h];
+}
+
+template <bool TLDS>
+__device__ __forceinline__ float att_bias(const float *s_tb, const AttnArgs &A, int h, int ix)
+{
+    return TLDS ? s_tb[ix] : A.table[(size_t)ix * A.heads + h];
+}
+
+// index[row][j0 .. j0 + 3] with j0 a multiple of 4; entries past nk repeat a valid one (their scores are masked).  `vec`: nk is a
+// multiple of 4 and the array 16-byte aligned -- one 16-byte load.  Always unconditional: loads under a lane mask are not batched
+__device__ __forceinline__ void att_load_index(int (&ix)[4], const int *__restrict__ irow, int j0, int nk, bool vec)
+{
+    if (vec) {
+        const int4 v = *reinterpret_cast<const int4 *>(irow + min(j0, nk - 4));
+        ix[0] = v.x; ix[1] = v.y; ix[2] = v.z; ix[3] = v.w;
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ix[r] = irow[min(j0 + r, nk - 1)];
+    }
+}
+
+// exp(x) as v_exp_f32(x log2 e): the rounding of the product moves p by at most |x| 2^-24 p <= 2.2e-8 (|x| e^-|x| peaks at 1)
+__device__ __forceinline__ float att_exp(float x) { return __expf(x); }
+
+// the sum / maximum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (one score row)
+__device__ __forceinline__ float att_row_sum(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }
+__device__ __forceinline__ float att_row_max(float v) { v = fmaxf(v, __shfl_xor(v, 16)); return fmaxf(v, __shfl_xor(v, 32)); }
+
+// the eight A / B values of a row-operand kept in registers: x[row][4 s + g], s = 0..7 (0 past d columns or when !valid)
+__device__ __forceinline__ void att_load_row(float (&r)[8], const float *__restrict__ row, int g, int d, bool valid, float mul)
+{
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int c = 4 * s + g;
+        r[s] = (valid && c < d) ? row[c] * mul : 0.f;
+    }
+}
+
+// D = sum_s A_lds[row0 + (l & 15)][4 s + g] * b[s]: a 16 x 16 tile over the 32 padded columns
+__device__ __forceinline__ att_f4 att_tile(const float *s_a, int row0, int c16, int g, const float (&b)[8])
+{
+    att_f4 acc = {0.f, 0.f, 0.f, 0.f};
+    const float *p = s_a + (row0 + c16) * ATT_LD + g;
+    float a[8];         // (all eight reads before the first product: a product that waits for its own LDS read runs at LDS latency)
+#pragma unroll
+    for (int s = 0; s < 8; ++s) a[s] = p[4 * s];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) acc = att_mfma(a[s], b[s], acc);
+    return acc;
+}
+
+template <int MAXT, bool STATS, bool TLDS>
+__global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
+    const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    const int nt = (nk + 15) >> 4, nkp = nt << 4;
+    float *s_k = s_mem, *s_v = s_mem + nkp * ATT_LD, *s_tb = s_v + nkp * ATT_LD;
+    att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+    att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+    if (TLDS) att_stage_table(s_tb, A, h);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const int nqt = (nq + 15) >> 4;
+    for (int qt = wave; qt < nqt; qt += nwaves) {
+        const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
+        float qr[8];
+        att_load_row(qr, A.q + ((size_t)w * nq + ic) * C + h * d, g, d, true, A.scale);
+        att_f4 sc[MAXT];
+        const int *irow = A.index + (size_t)ic * nk;
+        float m = -INFINITY;
+        // the biases of the whole row first, for every tile the instantiation has (indices past nk are clamped, so nothing here
+        // depends on nt and all the loads are in flight together).  They are ADDED to the finished products, as the torch
+        // expression does: as the chains' initial accumulators a bias of 50 costs the eight products their low bits
+        att_f4 bs[MAXT];
+#pragma unroll
+        for (int t = 0; t < MAXT; ++t) {
+            int ix[4];
+            att_load_index(ix, irow, 16 * t + 4 * g, nk, A.vec);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bs[t][r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+        }
+#pragma unroll
+        for (int t = 0; t < MAXT; ++t) {
+            if (t < nt) {
+                sc[t] = att_tile(s_k, 16 * t, c16, g, qr);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sc[t][r] = 16 * t + 4 * g + r < nk ? sc[t][r] + bs[t][r] : -INFINITY;
+                    m = fmaxf(m, sc[t][r]);
+                }
+            }
+        }
+        m = att_row_max(m);
+        float l = 0.f;
+        att_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < MAXT; ++t) {
+            if (t < nt) {
+                const float *vr = s_v + (16 * t + 4 * g) * ATT_LD + c16;
+                float v0[4], v1[4], p[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    v0[r] = vr[r * ATT_LD];
+                    v1[r] = vr[r * ATT_LD + 16];
+                    p[r] = att_exp(sc[t][r] - m);
+                    l += p[r];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    o0 = att_mfma(p[r], v0[r], o0);
+                    o1 = att_mfma(p[r], v1[r], o1);       // (always: the padded columns are zero, and a branch per product blocks the scheduler)
+                }
+            }
+        }
+        l = att_row_sum(l);
+        if (STATS && g == 0 && i < nq) A.stats[((size_t)w * A.heads + h) * nq + i] = m + logf(l);
+        const float linv = 1.f / l;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {       // the tile's row 4 g + r belongs to the query on lane 4 g + r
+            const float f = __shfl(linv, 4 * g + r);
+            const int io = qt * 16 + 4 * g + r;
+            if (io < nq) {
+                float *po = A.o + ((size_t)w * nq + io) * C + h * d;
+                if (c16 < d) po[c16] = o0[r] * f;
+                if (c16 + 16 < d) po[c16 + 16] = o1[r] * f;
+            }
+        }
+    }
+}
+
+// TAB: 0 no table gradient, 1 binned in LDS -> a partial column, 2 global atomics on g_table
+template <int TAB, bool TLDS>
+__global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const int slot = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
+    const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    const int nt = (nk + 15) >> 4, nkp = nt << 4, nqt = (nq + 15) >> 4;
+    float *s_k = s_mem, *s_v = s_mem + nkp * ATT_LD, *s_tb = s_v + nkp * ATT_LD, *s_tab = s_tb + (TLDS ? A.rows : 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    if (TAB == 1) for (int t = threadIdx.x; t < A.rows; t += blockDim.x) s_tab[t] = 0.f;
+    if (TLDS) att_stage_table(s_tb, A, h);
+    for (int w = slot; w < A.windows; w += A.wslots) {
+        __syncthreads();        // (the previous window's reads of s_k / s_v are done; s_tab is zeroed)
+        att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+        att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+        __syncthreads();
+        for (int qt = wave; qt < nqt; qt += nwaves) {
+            const int i = qt * 16 + c16, ic = min(i, nq - 1);
+            const bool iv = i < nq;
+            const size_t qoff = ((size_t)w * nq + ic) * C + h * d;
+            float qr[8], gr[8], orow[8];
+            att_load_row(qr, A.q + qoff, g, d, true, A.scale);
+            att_load_row(gr, A.grad_out + qoff, g, d, iv, 1.f);
+            att_load_row(orow, A.out + qoff, g, d, iv, 1.f);
+            float delta = 0.f;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) delta = fmaf(gr[s], orow[s], delta);
+            delta = att_row_sum(delta);
+            const float lse = A.stats[((size_t)w * A.heads + h) * nq + ic];
+            const int *irow = A.index + (size_t)ic * nk;
+            att_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};
+            // the tile's indices are loaded one tile ahead and its biases before its products: the dependent round trips run
+            // under the MFMAs
+            int ix[4], ix1[4];
+            att_load_index(ix, irow, 4 * g, nk, A.vec);
+            att_load_index(ix1, irow, 16 + 4 * g, nk, A.vec);
+            for (int t = 0; t < nt; ++t) {
+                float b[4];
+                int ixn[4];     // (two tiles ahead: one tile's products are shorter than a round trip to L2)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+                att_load_index(ixn, irow, 16 * t + 32 + 4 * g, nk, A.vec);
+                const float *kr = s_k + (16 * t + 4 * g) * ATT_LD + c16;
+                float k0[4], k1[4], ds[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    k0[r] = kr[r * ATT_LD];
+                    k1[r] = kr[r * ATT_LD + 16];
+                }
+                // (S exactly as the forward formed it -- the same chain, then the bias: the statistic is of THOSE bits, and at
+                // scores of a few hundred one ulp of S is 3e-5 of P)
+                const att_f4 sc = att_tile(s_k, 16 * t, c16, g, qr);
+                const att_f4 dp = att_tile(s_v, 16 * t, c16, g, gr);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int j = 16 * t + 4 * g + r;
+                    const bool valid = iv && j < nk;
+                    const float p = valid ? att_exp((sc[r] + b[r]) - lse) : 0.f;
+                    ds[r] = p * (dp[r] - delta);
+                    if (TAB == 1 && valid) atomicAdd(&s_tab[ix[r]], ds[r]);
+                    if (TAB == 2 && valid) atomicAdd(&A.g_table[(size_t)ix[r] * A.heads + h], ds[r]);
+                    ix[r] = ix1[r];
+                    ix1[r] = ixn[r];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    dq0 = att_mfma(ds[r], k0[r], dq0);
+                    dq1 = att_mfma(ds[r], k1[r], dq1);
+                }
+            }
+            if (A.g_q) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int io = qt * 16 + 4 * g + r;
+                    if (io < nq) {
+                        float *po = A.g_q + ((size_t)w * nq + io) * C + h * d;
+                        if (c16 < d) po[c16] = dq0[r] * A.scale;
+                        if (c16 + 16 < d) po[c16 + 16] = dq1[r] * A.scale;
+                    }
+                }
+            }
+        }
+    }
+    if (TAB == 1) {
+        __syncthreads();
+        float *part = A.part + ((size_t)slot * A.heads + h) * A.rows;
+        for (int t = threadIdx.x; t < A.rows; t += blockDim.x) part[t] = s_tab[t];
+    }
+}
+
+// g_table[t, h] = the partial columns of head h added in a fixed order: 32 entries per workgroup, eight threads per entry
+// each adding the slots s = slice, slice + 8, ... (short chains of independent loads), then the eight sums in slice order
+__global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgs A)
+{
+    __shared__ float s_sum[8][32];
+    const int e = blockIdx.x * 32 + (threadIdx.x & 31), slice = threadIdx.x >> 5;
+    const bool ev = e < A.rows * A.heads;
+    const int h = ev ? e / A.rows : 0, t = ev ? e % A.rows : 0;
+    float a = 0.f;
+    if (ev) for (int s = slice; s < A.wslots; s += 8) a += A.part[((size_t)s * A.heads + h) * A.rows + t];
+    s_sum[slice][threadIdx.x & 31] = a;
+    __syncthreads();
+    if (slice == 0 && ev) {
+        for (int u = 1; u < 8; ++u) a += s_sum[u][threadIdx.x];
+        A.g_table[(size_t)t * A.heads + h] = a;
+    }
+}
+
+template <bool TLDS>
+__global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
+    const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    const int nqt = (nq + 15) >> 4, nqp = nqt << 4, nkt = (nk + 15) >> 4;
+    float *s_q = s_mem, *s_g = s_mem + nqp * ATT_LD, *s_lse = s_g + nqp * ATT_LD, *s_delta = s_lse + nqp, *s_tb = s_delta + nqp;
+    const size_t qbase = (size_t)w * nq * C + h * d;
+    att_stage(s_q, A.q + qbase, nq, nqp, d, C, A.scale);
+    att_stage(s_g, A.grad_out + qbase, nq, nqp, d, C, 1.f);
+    if (TLDS) att_stage_table(s_tb, A, h);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nqp; i += blockDim.x) {
+        float a = 0.f;
+        if (i < nq) {
+            const float *po = A.out + qbase + (size_t)i * C;
+            for (int c = 0; c < d; ++c) a = fmaf(s_g[i * ATT_LD + c], po[c], a);
+        }
+        s_delta[i] = a;
+        s_lse[i] = i < nq ? A.stats[((size_t)w * A.heads + h) * nq + i] : 0.f;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    for (int kt = wave; kt < nkt; kt += nwaves) {
+        const int j = kt * 16 + c16, jc = min(j, nk - 1);
+        const bool jv = j < nk;
+        const size_t koff = ((size_t)w * nk + jc) * C + h * d;
+        float kr[8], vr[8];
+        att_load_row(kr, A.k + koff, g, d, jv, 1.f);
+        att_load_row(vr, A.v + koff, g, d, jv, 1.f);
+        att_f4 dk0 = {0.f, 0.f, 0.f, 0.f}, dk1 = dk0, dv0 = dk0, dv1 = dk0;
+        int ix[4], ix1[4];      // (loaded two tiles ahead, unconditionally: as in k_attn_bwd_q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            ix[r] = A.index[(size_t)min(4 * g + r, nq - 1) * nk + jc];
+            ix1[r] = A.index[(size_t)min(16 + 4 * g + r, nq - 1) * nk + jc];
+        }
+        for (int t = 0; t < nqt; ++t) {
+            float b[4];
+            int ixn[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+                ixn[r] = A.index[(size_t)min(16 * t + 32 + 4 * g + r, nq - 1) * nk + jc];
+            }
+            const float *gq = s_g + (16 * t + 4 * g) * ATT_LD + c16, *qq = s_q + (16 * t + 4 * g) * ATT_LD + c16;
+            float g0[4], g1[4], q0[4], q1[4], lse[4], dl[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                g0[r] = gq[r * ATT_LD]; g1[r] = gq[r * ATT_LD + 16];
+                q0[r] = qq[r * ATT_LD]; q1[r] = qq[r * ATT_LD + 16];
+                lse[r] = s_lse[16 * t + 4 * g + r]; dl[r] = s_delta[16 * t + 4 * g + r];
+            }
+            const att_f4 sc = att_tile(s_q, 16 * t, c16, g, kr);       // [query 16 t + 4 g + r][key j], the forward's bits
+            const att_f4 dp = att_tile(s_g, 16 * t, c16, g, vr);
+            float p[4], ds[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = 16 * t + 4 * g + r;
+                p[r] = (jv && i < nq) ? att_exp((sc[r] + b[r]) - lse[r]) : 0.f;
+                ds[r] = p[r] * (dp[r] - dl[r]);
+                ix[r] = ix1[r];
+                ix1[r] = ixn[r];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                dv0 = att_mfma(p[r], g0[r], dv0);
+                dk0 = att_mfma(ds[r], q0[r], dk0);
+                dv1 = att_mfma(p[r], g1[r], dv1);
+                dk1 = att_mfma(ds[r], q1[r], dk1);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int jo = kt * 16 + 4 * g + r;
+            if (jo < nk) {
+                const size_t off = ((size_t)w * nk + jo) * C + h * d;
+                if (A.g_k) {
+                    if (c16 < d) A.g_k[off + c16] = dk0[r];
+                    if (c16 + 16 < d) A.g_k[off + c16 + 16] = dk1[r];
+                }
+                if (A.g_v) {
+                    if (c16 < d) A.g_v[off + c16] = dv0[r];
+                    if (c16 + 16 < d) A.g_v[off + c16 + 16] = dv1[r];
+                }
+            }
+        }
+    }
+}
+
+int attn_geometry_check(const gsasr_window_attn *a)
+{
+    if (!a) return fail(GSASR_ERR_ARG, "null window-attention descriptor");
+    if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
+    if (a->nq < 1 || a->nq > ATT_MAX_N || a->nk < 1 || a->nk > ATT_MAX_N) return fail(GSASR_ERR_ARG, "need 1 <= nq, nk <= 256");
+    if (a->head_dim < 1 || a->head_dim > ATT_MAX_D) return fail(GSASR_ERR_ARG, "need 1 <= head_dim <= 32");
+    if (a->table_rows < 1) return fail(GSASR_ERR_ARG, "table_rows must be at least 1");
+    if (a->flags) return fail(GSASR_ERR_ARG, "unknown flags (none are defined)");
+    if (!(a->scale == a->scale)) return fail(GSASR_ERR_ARG, "scale is NaN");
+    if ((long long)a->windows * a->heads > 0x7fffffffLL || (long long)a->table_rows * a->heads > 0x7fffffffLL)
+        return fail(GSASR_ERR_ARG, "windows * heads or table_rows * heads exceeds 2^31 - 1");
+    return GSASR_OK;
+}
+
+inline int attn_wslots(const gsasr_window_attn *a) { return a->windows < ATT_TAB_WG ? a->windows : ATT_TAB_WG; }
+
+AttnArgs attn_args(const gsasr_window_attn *a)
+{
+    AttnArgs A;
+    A.q = a->q; A.k = a->k; A.v = a->v; A.table = a->table; A.index = a->index; A.out = a->out; A.o = a->out; A.stats = a->stats;
+    A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.g_table = a->g_table; A.part = (float *)a->scratch;
+    A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.rows = a->table_rows;
+    A.wslots = attn_wslots(a);
+    A.vec = a->nk % 4 == 0 && ((uintptr_t)a->index & 15) == 0;
+    A.scale = a->scale;
+    return A;
+}
+
+// waves per workgroup, one 16-row tile per wave and turn: three when that deals the tiles evenly and four do not (144 tokens = 9 tiles)
+inline int attn_waves(int n)
+{
+    const int tiles = (n + 15) / 16;
+    return tiles % 4 != 0 && tiles % 3 == 0 ? 3 : 4;
+}
+
+inline bool attn_tlds(const gsasr_window_attn *a) { return a->table_rows <= ATT_TAB_LDS; }
+
+template <typename K>
+int attn_launch(K kernel, unsigned grid, int waves, size_t lds, hipStream_t st, const AttnArgs &A)
+{
+    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, A);
+    HIP_TRY(hipGetLastError());
+    return GSASR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *a)
+{
+    if (attn_geometry_check(a)) return 0;
+    // the partial table columns of the backward (one per window slot and head); never 0 for a valid descriptor
+    const bool part = a->g_table && a->table_rows <= ATT_TAB_LDS;
+    return 256 + (part ? align_up((size_t)attn_wslots(a) * a->heads * a->table_rows * sizeof(float), 256) : 0);
+}
+
+int gsasr_window_attn_forward(const gsasr_window_attn *a, void *stream)
+{
+    if (int rc = attn_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out) return fail(GSASR_ERR_ARG, "null q, k, v, table, index or out pointer");
+    const AttnArgs A = attn_args(a);
+    const int nt = (a->nk + 15) / 16;
+    const bool tlds = attn_tlds(a), stats = a->stats != nullptr;
+    const size_t lds = ((size_t)2 * nt * 16 * ATT_LD + (tlds ? a->table_rows : 0)) * sizeof(float);
+    const unsigned grid = (unsigned)(a->windows * a->heads);
+    const int waves = attn_waves(a->nq);
+    hipStream_t st = (hipStream_t)stream;
+#define ATT_FWD(T) (stats ? (tlds ? attn_launch(k_attn_fwd<T, true, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, true, false>, grid, waves, lds, st, A)) \
+                          : (tlds ? attn_launch(k_attn_fwd<T, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, false, false>, grid, waves, lds, st, A)))
+    if (nt <= 3) return ATT_FWD(3);
+    if (nt <= 9) return ATT_FWD(9);
+    return ATT_FWD(16);
+#undef ATT_FWD
+}
+
+int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream)
+{
+    if (int rc = attn_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out || !a->stats || !a->grad_out)
+        return fail(GSASR_ERR_ARG, "null q, k, v, table, index, out, stats or grad_out pointer");
+    const AttnArgs A = attn_args(a);
+    hipStream_t st = (hipStream_t)stream;
+    const bool tlds = attn_tlds(a);
+    const int tab = !a->g_table ? 0 : tlds ? 1 : 2;
+    if (tab == 1 && !a->scratch) return fail(GSASR_ERR_ARG, "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)");
+    if (a->g_q || tab) {
+        const size_t lds = ((size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD + (tlds ? a->table_rows : 0) + (tab == 1 ? a->table_rows : 0)) * sizeof(float);
+        const unsigned grid = (unsigned)(A.wslots * a->heads);
+        const int waves = attn_waves(a->nq);
+        int rc;
+        if (tab == 2) {
+            HIP_TRY(hipMemsetAsync(a->g_table, 0, (size_t)a->table_rows * a->heads * sizeof(float), st));
+            rc = attn_launch(k_attn_bwd_q<2, false>, grid, waves, lds, st, A);
+        } else if (tab == 1) rc = attn_launch(k_attn_bwd_q<1, true>, grid, waves, lds, st, A);
+        else rc = tlds ? attn_launch(k_attn_bwd_q<0, true>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_q<0, false>, grid, waves, lds, st, A);
+        if (rc) return rc;
+        if (tab == 1) {
+            hipLaunchKernelGGL(k_attn_table_sum, dim3((unsigned)((a->table_rows * a->heads + 31) / 32)), dim3(256), 0, st, A);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (a->g_k || a->g_v) {
+        const int nqp = (a->nq + 15) / 16 * 16;
+        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp + (tlds ? a->table_rows : 0)) * sizeof(float);
+        const unsigned grid = (unsigned)(a->windows * a->heads);
+        const int waves = attn_waves(a->nk);
+        if (int rc = tlds ? attn_launch(k_attn_bwd_kv<true>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_kv<false>, grid, waves, lds, st, A)) return rc;
+    }
+    return GSASR_OK;
+}
+
+}  // extern "C"

@@ -639,6 +639,46 @@ GSASR_API size_t gsasr_batch_scratch_bytes(const gsasr_batch *batch);   /* 0 on 
 GSASR_API int gsasr_batch_make(const gsasr_batch *batch, void *stream);
 GSASR_API int gsasr_batch_pick(const gsasr_batch *batch, const int *points, int n_points, float *out, void *stream);
 
+/* Window attention with a relative-position bias: the core of every layer of GSASR's Fea2GS decoder (WindowCrossAttn and
+ * GSSelfAttn, utils/fea2gs.py:162-194, 321-350), fused -- no [windows, heads, nq, nk] score tensor and no head split / merge copy
+ * ever touches memory.  For window w and head h, with x[w, :, h] the columns h * head_dim .. (h + 1) * head_dim - 1 of x:
+ *
+ *   S = scale q[w, :, h] k[w, :, h]^T + B_h,  B_h[i, j] = table[index[i, j], h],  P = softmax over j of S,  out[w, :, h] = P v[w, :, h]
+ *   stats[w, h, i] = log sum_j exp(S[i, j])                                   (the row statistic a backward recomputes P from)
+ *   backward, given grad_out = d L / d out:  delta_i = sum_c grad_out[i, c] out[i, c],  dP = grad_out v^T,  dS = P o (dP - delta),
+ *   g_v = P^T grad_out,  g_q = scale dS k,  g_k = scale dS^T q,  g_table[t, h] = sum over w and all (i, j) with index[i, j] = t of dS[i, j]
+ *
+ * fp32 throughout: the products run on the exact-fp32 matrix instruction (a k-ordered chain of fmaf), the softmax sees the
+ * whole row at once (one maximum, one sum; no online rescaling).  out, g_q, g_k and g_v are written once by the workgroup that
+ * owns the (window, head) -- no atomics, two calls give the same bits.  g_table is binned with float adds in LDS whose order is
+ * not fixed: its last bits may differ between two calls; a row that no (i, j) uses is exactly 0.  Nothing is read on the host and
+ * everything is enqueued on `stream`: the calls can be captured into a graph.
+ *
+ *   q, out, grad_out, g_q   [windows, nq, heads * head_dim], contiguous;  k, v, g_k, g_v   [windows, nk, heads * head_dim]
+ *   table, g_table          [table_rows, heads];  index   int [nq, nk] with 0 <= index < table_rows -- NOT checked here (the
+ *                           kernels read table[index]): the caller validates it, as gsasr_amd.window_attention does once per tensor
+ *   stats                   float [windows, heads, nq]; forward: NULL = not stored; backward: what the forward stored
+ *   g_q, g_k, g_v, g_table  each NULL = not wanted (its work is skipped where that saves a kernel)
+ *   scratch                 gsasr_window_attn_scratch_bytes(descriptor) bytes, 256-byte aligned, for the backward when g_table is set
+ *                           (set g_table before asking): per-workgroup partial tables, every word written before it is read
+ * GSASR_ERR_ARG before anything is enqueued: windows, heads or table_rows below 1, nq or nk outside 1..256, head_dim outside
+ * 1..32, flags other than 0, a NaN scale, a null pointer among those the call needs. */
+typedef struct gsasr_window_attn {
+    int windows, heads, nq, nk, head_dim, table_rows;
+    float scale;
+    unsigned flags;       /* 0 (none defined) */
+    const float *q, *k, *v, *table;
+    const int *index;
+    float *out;           /* written by the forward, read by the backward */
+    float *stats;
+    const float *grad_out;
+    float *g_q, *g_k, *g_v, *g_table;
+    void *scratch;
+} gsasr_window_attn;
+GSASR_API size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *attn);   /* 0 on bad arguments (only g_table among the pointers is looked at) */
+GSASR_API int gsasr_window_attn_forward(const gsasr_window_attn *attn, void *stream);
+GSASR_API int gsasr_window_attn_backward(const gsasr_window_attn *attn, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate

@@ -97,9 +97,9 @@ class _BiasedWindowAttention(nn.Module):
     """multi-head attention of `nq` query tokens on an n x n grid over `nk` key tokens on an m x m grid of the same window,
     with a learned bias per head and relative offset (both grids scaled to a common lattice)"""
 
-    def __init__(self, c, heads, n, m):
+    def __init__(self, c, heads, n, m, attention="torch"):
         super().__init__()
-        self.heads = heads
+        self.heads, self.attention = heads, attention
         self.q, self.k, self.v, self.o = nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c)
         # offsets between query cell centres and key cell centres on the lattice of n * m points per side
         qy, qx = torch.meshgrid(torch.arange(n), torch.arange(n), indexing="ij")
@@ -120,6 +120,9 @@ class _BiasedWindowAttention(nn.Module):
     def forward(self, xq, xk):
         b, nq, c = xq.shape
         h = self.heads
+        if self.attention == "hip":        # the fused op on the Linears' outputs as they come: no head split, no [b, h, nq, nk] scores
+            from gsasr_amd.attention import window_attention
+            return self.o(window_attention(self.q(xq), self.k(xk), self.v(xk), self.bias, self.index))
         q = self.q(xq).view(b, nq, h, c // h).transpose(1, 2)
         k = self.k(xk).view(b, -1, h, c // h).transpose(1, 2)
         v = self.v(xk).view(b, -1, h, c // h).transpose(1, 2)
@@ -132,18 +135,22 @@ class _SeedLayer(nn.Module):
     """one decoder layer: seeds attend to the scale embedding, FFN, window attention (to image features, or among the seeds),
     FFN -- pre-norm residuals.  `cross`: keys are the window's image features; else the seeds themselves."""
 
-    def __init__(self, c, heads, win, shift, cross):
+    def __init__(self, c, heads, win, shift, cross, attention="torch", scale_attention="mha"):
         super().__init__()
-        self.win, self.shift, self.cross = win, shift, cross
+        self.win, self.shift, self.cross, self.scale_attention = win, shift, cross, scale_attention
         self.n1, self.n2, self.n3, self.n4 = (nn.LayerNorm(c) for _ in range(4))
         self.to_scale = nn.MultiheadAttention(c, heads, batch_first=True)
         self.f1, self.f2 = _FFN(c), _FFN(c)
-        self.attn = _BiasedWindowAttention(c, heads, win, win)
+        self.attn = _BiasedWindowAttention(c, heads, win, win, attention)
 
     def forward(self, x, pos, feat, scale_emb, grid):
         b, m, n = grid                                               # images, windows per column / row
         y = self.n1(x)
-        x = x + self.to_scale(y + pos, scale_emb, scale_emb, need_weights=False)[0]
+        if self.scale_attention == "constant":     # every key is the same row: the attention is out_proj(v_proj(row)) for every query
+            from gsasr_amd.attention import constant_key_attention
+            x = x + constant_key_attention(self.to_scale, scale_emb[:, :1])
+        else:
+            x = x + self.to_scale(y + pos, scale_emb, scale_emb, need_weights=False)[0]
         x = x + self.f1(self.n2(x))
         y = self.n3(x)
         w = self.win
@@ -168,10 +175,11 @@ class _SeedLayer(nn.Module):
 
 
 class _SeedBlock(nn.Module):
-    def __init__(self, c, heads, win, layers, cross):
+    def __init__(self, c, heads, win, layers, cross, attention="torch", scale_attention="mha"):
         super().__init__()
         self.norm = nn.LayerNorm(c)
-        self.layers = nn.ModuleList([_SeedLayer(c, heads, win, 0 if i % 2 == 0 else win // 2, cross) for i in range(layers)])
+        self.layers = nn.ModuleList([_SeedLayer(c, heads, win, 0 if i % 2 == 0 else win // 2, cross, attention, scale_attention)
+                                     for i in range(layers)])
         self.mlp = _FFN(c)
 
     def forward(self, x, pos, feat, scale_emb, grid):
@@ -183,18 +191,25 @@ class _SeedBlock(nn.Module):
 
 class Fea2GSDecoder(nn.Module):
     """[B,c,h,w] (h, w multiples of the window), scale[B] -> [B, 16 h w, 9]: the reference decoder's architecture (module
-    docstring), one seed per LR pixel, 16 Gaussians per seed after the two pixel shuffles, raster order of the 4h x 4w grid"""
+    docstring), one seed per LR pixel, 16 Gaussians per seed after the two pixel shuffles, raster order of the 4h x 4w grid.
+    `attention`: "torch" (F.scaled_dot_product_attention with the bias as mask, the default) | "hip" (gsasr_amd.window_attention);
+    `scale_attention`: "mha" (nn.MultiheadAttention over the repeated scale embedding, the default) | "constant"
+    (gsasr_amd.attention.constant_key_attention).  Same parameters and state dict in every mode."""
     UP = 4
 
-    def __init__(self, inchannel=64, channel=180, heads=6, window=12, cross_layers=2, self_blocks=6, self_layers=6):
+    def __init__(self, inchannel=64, channel=180, heads=6, window=12, cross_layers=2, self_blocks=6, self_layers=6,
+                 attention="torch", scale_attention="mha"):
         super().__init__()
+        if attention not in ("torch", "hip") or scale_attention not in ("mha", "constant"):
+            raise ValueError('attention must be "torch" or "hip", scale_attention "mha" or "constant"')
+        mode = (attention, scale_attention)
         self.c, self.win = channel, window
         self.seed = nn.Parameter(torch.randn(window * window, channel))
         self.pos = nn.Parameter(torch.randn(window * window, channel))
         self.proj = nn.Sequential(nn.Conv2d(inchannel, channel, 3, 1, 1), nn.ReLU(), nn.Conv2d(channel, channel, 3, 1, 1))
         self.scale_mlp = nn.Sequential(nn.Linear(1, 4 * channel), nn.ReLU(), nn.Linear(4 * channel, channel))
-        self.cross = nn.ModuleList([_SeedBlock(channel, heads, window, cross_layers, True)])
-        self.selfs = nn.ModuleList([_SeedBlock(channel, heads, window, self_layers, False) for _ in range(self_blocks)])
+        self.cross = nn.ModuleList([_SeedBlock(channel, heads, window, cross_layers, True, *mode)])
+        self.selfs = nn.ModuleList([_SeedBlock(channel, heads, window, self_layers, False, *mode) for _ in range(self_blocks)])
         self.up = nn.Sequential(nn.Conv2d(channel, channel * 4, 3, 1, 1), nn.PixelShuffle(2),
                                 nn.Conv2d(channel, channel * 4, 3, 1, 1), nn.PixelShuffle(2))
         self.sigma, self.rho, self.alpha = _head(channel, 2), _head(channel, 1), _head(channel, 1)
