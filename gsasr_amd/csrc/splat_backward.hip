@@ -365,41 +365,18 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu((BT_CHU
         if (tid < 3) s_cnt[tid] = 0u;
     }
 
-    // ---- segment table of the tile (every wave builds the same one; cf. fwd_block) ------------------------
-    const unsigned *__restrict__ cs = V.cell_start;
-    const int rx = (int)V.hdr[8], ry = (int)V.hdr[9];
-    int nseg = 0;
-    unsigned sbeg = 0, send = 0;
-    if (rx > 0) {
-        const int cx0 = max(bx0 - rx, 0) >> CELL_SHIFT, cx1 = min((bx1 + rx) >> CELL_SHIFT, P.ncx - 1);
-        const int cy0 = max(by0 - ry, 0) >> CELL_SHIFT, cy1 = min((by1 + ry) >> CELL_SHIFT, P.ncy - 1);
-        nseg = cy1 - cy0 + 1;
-        if (lane < nseg) {
-            sbeg = cs[(cy0 + lane) * P.ncx + cx0];
-            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
-        }
-    }
-    if (lane == nseg) {
-        sbeg = cs[P.ncells];
-        send = cs[P.ncells + 1];
-    }
-    ++nseg;
-    const unsigned len = send - sbeg;
-    unsigned pin = len;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)pin, o);
-        if (lane >= o) pin += v;
-    }
-    const unsigned pex = pin - len;
-    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)pin, nseg - 1);
+    // ---- segment table of the tile (every wave builds the same one); its last segment is the large class ----
+    const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
+    const int nseg = T.nseg;
+    const unsigned total = T.total;
     // the tile's list, if the plan wrote one that holds everything; else (and for the large class, which no list holds) the walk
     const unsigned lcnt = LISTS ? (unsigned)__builtin_amdgcn_readfirstlane((int)V.tl_cursor[(size_t)tt * TL_STRIDE]) : 0u;
     const bool uselist = LISTS && lcnt <= (unsigned)P.tl_cap;
     const uint2 *__restrict__ ent = V.tl_entries + (size_t)tt * (size_t)P.tl_cap;
-    const unsigned nlarge_c = uselist ? (((unsigned)__builtin_amdgcn_readlane((int)len, nseg - 1) + 63u) >> 6) : 0u;   // chunks of the large segment
+    const unsigned nlarge_c = uselist ? (((unsigned)__builtin_amdgcn_readlane((int)T.len, nseg - 1) + 63u) >> 6) : 0u;   // chunks of the large segment
     const unsigned lchunks = (lcnt + 63u) >> 6;
     const unsigned nchunks = uselist ? lchunks + nlarge_c : (total + 63u) >> 6;
-    const unsigned large_q0 = (unsigned)__builtin_amdgcn_readlane((int)pex, nseg - 1);     // where the large segment starts in the flat walk
+    const unsigned large_q0 = (unsigned)__builtin_amdgcn_readlane((int)T.pex, nseg - 1);     // where the large segment starts in the flat walk
     const unsigned long long below = (1ull << lane) - 1ull;
     int rseg = 0;
     __syncthreads();
@@ -423,9 +400,9 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu((BT_CHU
             }
             if (uselist) {                          // behind the list: the large class alone, walked as ever
                 const unsigned q = large_q0 + (c - lchunks) * 64u + (unsigned)lane;
-                cj[k] = (c < nchunks && q < total) ? (unsigned)__builtin_amdgcn_readlane((int)sbeg, nseg - 1) + (q - large_q0) : 0xffffffffu;
+                cj[k] = (c < nchunks && q < total) ? (unsigned)__builtin_amdgcn_readlane((int)T.sbeg, nseg - 1) + (q - large_q0) : 0xffffffffu;
             } else {
-                cj[k] = c < nchunks ? fwd_candidate(c, lane, nseg, rseg, sbeg, pex, pin) : 0xffffffffu;
+                cj[k] = c < nchunks ? fwd_candidate(c, lane, T, rseg) : 0xffffffffu;
             }
             if (cj[k] != 0xffffffffu) cw[k] = V.win[cj[k]];
         }

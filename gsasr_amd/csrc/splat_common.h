@@ -1024,25 +1024,182 @@ struct StepSrc {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-// Candidate index of this lane in flat chunk `c` of the concatenated segments.  The segment table lives in
-// lanes (lane r: start `sbeg`, exclusive/inclusive prefix of the lengths `pex`/`pin`); `r` is the first
-// segment that reaches into the chunk (wave-uniform, advanced monotonically).  Returns 0xffffffff for
-// lanes past the end.  A chunk overlaps one or two segments at 16 Gaussians per cell and 3-5 when cells
-// are sparse (x12 inference), so every chunk is full instead of one mostly-empty chunk per segment.
-__device__ __forceinline__ unsigned fwd_candidate(unsigned c, int lane, int nseg, int &r, unsigned sbeg, unsigned pex,
-                                                  unsigned pin)
+// ---------------------------------------------------------------------------------------------------
+// How the render kernels FIND their Gaussians (the forward kernels and the tile backward): a segment table over the plan's
+// cells, walked in chunks of 64 candidates, each tested against a tile (coarse_pass) and a sub-tile (fine_test).  Written
+// once here; what differs from kernel to kernel is a parameter.
+// ---------------------------------------------------------------------------------------------------
+
+// Segment table of a pixel rectangle: lane r holds the candidates [sbeg, sbeg + len) of cell row cy0 + r restricted to the
+// columns a normal-class Gaussian can reach the rectangle from (reach (rx, ry): the largest half-extents, plan header words
+// 8, 9), one more lane holds the large class; pex / pin = exclusive / inclusive prefix sum of the lengths over the lanes.
+// One vector round trip instead of a dependent scalar load per row.  nseg and total are wave-uniform.
+struct SegTable {
+    unsigned sbeg, len, pex, pin;
+    int nseg;
+    unsigned total;     // candidates in all: chunks() full chunks of 64 (the last one ragged)
+    __device__ __forceinline__ unsigned chunks() const { return (total + 63u) >> 6; }
+};
+
+// (x0, x1, y0, y1): the rectangle, inclusive -- the workgroup's tile where a coarse pass follows, the wave's own sub-tile in the
+// one-level walks.  rx == 0: the large class alone (what a kernel that reads the plan's tile lists still has to scan).
+__device__ __forceinline__ SegTable seg_table(const Params &P, const PlanView &V, int x0, int x1, int y0, int y1, int rx, int ry, int lane)
+{
+    const unsigned *__restrict__ cs = V.cell_start;
+    SegTable T;
+    T.nseg = 0;
+    T.sbeg = 0;
+    unsigned send = 0;
+    if (rx > 0) {
+        const int cx0 = max(x0 - rx, 0) >> CELL_SHIFT, cx1 = min((x1 + rx) >> CELL_SHIFT, P.ncx - 1);
+        const int cy0 = max(y0 - ry, 0) >> CELL_SHIFT, cy1 = min((y1 + ry) >> CELL_SHIFT, P.ncy - 1);
+        T.nseg = cy1 - cy0 + 1;
+        if (lane < T.nseg) {
+            T.sbeg = cs[(cy0 + lane) * P.ncx + cx0];
+            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
+        }
+    }
+    if (lane == T.nseg) {
+        T.sbeg = cs[P.ncells];
+        send = cs[P.ncells + 1];
+    }
+    ++T.nseg;
+    T.len = send - T.sbeg;
+    unsigned pin = T.len;  // inclusive prefix sum of the segment lengths over the lanes
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = (unsigned)__shfl_up((int)pin, o);
+        if (lane >= o) pin += v;
+    }
+    T.pin = pin;
+    T.pex = pin - T.len;
+    T.total = (unsigned)__builtin_amdgcn_readlane((int)pin, T.nseg - 1);
+    return T;
+}
+
+// Candidate index of this lane in flat chunk `c` of the concatenated segments; `r` is the first segment that reaches into
+// the chunk (wave-uniform, advanced monotonically).  Returns 0xffffffff for lanes past the end.  A chunk overlaps one or two
+// segments at 16 Gaussians per cell and 3-5 when cells are sparse (x12 inference), so every chunk is full instead of one
+// mostly-empty chunk per segment.
+__device__ __forceinline__ unsigned fwd_candidate(unsigned c, int lane, const SegTable &T, int &r)
 {
     const unsigned q0 = c * 64u, q = q0 + (unsigned)lane;
-    while (r < nseg && (unsigned)__builtin_amdgcn_readlane((int)pin, r) <= q0) ++r;
+    while (r < T.nseg && (unsigned)__builtin_amdgcn_readlane((int)T.pin, r) <= q0) ++r;
     unsigned j = 0xffffffffu;
-    for (int rr = r; rr < nseg; ++rr) {
-        const unsigned p0 = (unsigned)__builtin_amdgcn_readlane((int)pex, rr);
+    for (int rr = r; rr < T.nseg; ++rr) {
+        const unsigned p0 = (unsigned)__builtin_amdgcn_readlane((int)T.pex, rr);
         if (p0 >= q0 + 64u) break;
-        const unsigned p1 = (unsigned)__builtin_amdgcn_readlane((int)pin, rr);
-        const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)sbeg, rr);
+        const unsigned p1 = (unsigned)__builtin_amdgcn_readlane((int)T.pin, rr);
+        const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)T.sbeg, rr);
         if (q >= p0 && q < p1) j = b + (q - p0);
     }
     return j;
+}
+
+// Coarse pass ("phase A" of a two-level walk).  Measured: finding a sub-tile's hits -- fetching the 24-byte windows of every
+// Gaussian binned within reach and testing them, 64 per wave and round trip -- is HALF of the forward's time (the candidates
+// come from cells within the class' MAXIMUM extent, 4-5x more than hit).  The waves of a workgroup render sub-tiles side by
+// side, and their candidate sets are almost the same, so the workgroup walks the candidates of its tile ONCE, cooperatively:
+// each of the WAVES waves that share a round tests its CHUNKS chunks of the round (chunk base + wv + WAVES k) against the
+// whole tile (bx0..by1, inclusive; window only: the 8 bytes per candidate of PlanView::win, all loads of the round in flight
+// together) and appends the survivors to the shared list in LDS -- one ballot and one atomicAdd per chunk.  Rounds of
+// WAVES * CHUNKS * 64 candidates (1024 in the 8 x 16 forward) bound the list.  Returns the survivors of the round, n, behind
+// the barrier that completes the list; the counter is double-buffered (the other one is reset here: nobody touches it before
+// the next barrier), and the CALLER closes the round with a barrier of its own before the list is rewritten.
+template <int WAVES, int CHUNKS>
+__device__ __forceinline__ unsigned coarse_pass(const PlanView &V, const SegTable &T, int &rseg, int bx0, int bx1, int by0, int by1,
+                                                unsigned base, unsigned round, int wv, int lane, unsigned *s_list, unsigned *s_cnt)
+{
+    const unsigned nchunks = T.chunks();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned *cnt = s_cnt + (round & 1u);
+    unsigned cj[CHUNKS];
+    uint2 cw[CHUNKS];
+#pragma unroll
+    for (int k = 0; k < CHUNKS; ++k) {
+        const unsigned c = base + (unsigned)wv + (unsigned)(WAVES * k);
+        cj[k] = c < nchunks ? fwd_candidate(c, lane, T, rseg) : 0xffffffffu;
+        cw[k] = make_uint2(0x7fffu, 0x7fffu);
+        if (cj[k] != 0xffffffffu) cw[k] = V.win[cj[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < CHUNKS; ++k) {
+        const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
+        const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
+        const bool hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
+        const unsigned long long m = __ballot(hit);
+        if (m) {
+            unsigned at = 0;
+            if (lane == 0) at = atomicAdd(cnt, (unsigned)__builtin_popcountll(m));
+            at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
+            if (hit) s_list[at + (unsigned)__builtin_popcountll(m & below)] = cj[k];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0u;
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)*cnt);
+}
+
+// Fine test of one candidate against one sub-tile.  The candidate's window record (PlanView::bbox): the first 24 of its 32
+// bytes, or for "no candidate" (0xffffffff) the dead box c0 = r0 = 32767 > c1 = r1 = 0, which overlaps no sub-tile.
+struct FineBox {
+    uint4 bb;
+    uint2 bs;
+};
+__device__ __forceinline__ FineBox fine_load(const uint4 *__restrict__ bbox, unsigned j)
+{
+    FineBox b{make_uint4(0x7fffu, 0x7fffu, 0u, 0u), make_uint2(0u, 0u)};
+    if (j != 0xffffffffu) {
+        b.bb = bbox[2 * (size_t)j];
+        b.bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
+    }
+    return b;
+}
+
+// The sub-tile: its pixel rectangle (inclusive, clipped to the image) and its place in the units of k_bin's spans -- wtx in
+// 8-px columns, wty in 16-row bands counted from row0 (the 8 x 8 sub-tiles of k_render_fwd8 share a band in pairs).
+struct SubTile {
+    int x0, x1, y0, y1, wtx, wty;
+};
+struct FineHit {
+    bool hit, needs;    // the window (and the ellipse's span on the sub-tile's band) meets the sub-tile; it is cut by the dmax box
+    int r0, r1;         // the window's rows (the wide kernels sort their hits by them)
+};
+// UNITS: the 8-column units a sub-tile is wide (1: the 8 x 16 and 8 x 8 sub-tiles, 2: 16 x 16).
+template <bool BOUNDED, int UNITS>
+__device__ __forceinline__ FineHit fine_test(const FineBox &b, const SubTile &S, int row0)
+{
+    const uint4 bb = b.bb;
+    const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
+    FineHit h;
+    h.r0 = (int)(bb.y & 0x7fffu);
+    h.r1 = (int)(bb.y >> 16);
+    h.hit = (c0 <= S.x1) & (c1 >= S.x0) & (h.r0 <= S.y1) & (h.r1 >= S.y0);
+    if (bb.y & 0x8000u) {  // per-16-row-band column spans (k_bin), in 8-column units from the window's first
+        const unsigned t = (unsigned)(S.wty - ((h.r0 - row0) >> SUBY_SHIFT)) & 7u, sh = (t & 3u) * 8u;
+        const unsigned lo = t < 4u ? bb.z : b.bs.x, hi = t < 4u ? bb.w : b.bs.y;
+        const int txr = S.wtx - (c0 >> SUBX_SHIFT);
+        h.hit &= (txr + (UNITS - 1) >= (int)((lo >> sh) & 0xffu)) & (txr <= (int)((hi >> sh) & 0xffu));
+    }
+    h.needs = BOUNDED && (bb.x & 0x8000u) != 0u;
+    return h;
+}
+
+// Survivor walk ("phase B"): every wave runs the fine test over the round's n survivors only, 64 at a time from `start` in
+// steps of `stride` (two waves per sub-tile take alternate chunks), the NEXT chunk's window record in flight while
+// body(j, hit) deals with the current one.
+template <bool BOUNDED, int UNITS, typename Body>
+__device__ __forceinline__ void survivor_walk(const uint4 *__restrict__ bbox, const unsigned *s_list, unsigned n, unsigned start,
+                                              unsigned stride, int lane, const SubTile &S, int row0, Body &&body)
+{
+    unsigned j = start + (unsigned)lane < n ? s_list[start + lane] : 0xffffffffu;
+    FineBox b = fine_load(bbox, j);
+    for (unsigned q = start; q < n; q += stride) {
+        const unsigned nq = q + stride + (unsigned)lane;
+        const unsigned nj = nq < n ? s_list[nq] : 0xffffffffu;
+        const FineBox nb = fine_load(bbox, nj);
+        body(j, fine_test<BOUNDED, UNITS>(b, S, row0));
+        j = nj; b = nb;
+    }
 }
 
 // XCD-aware tile order: blocks are dealt round-robin to the 8 XCDs (block b -> XCD b%8), so give each XCD

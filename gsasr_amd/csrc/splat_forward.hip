@@ -233,6 +233,17 @@ __device__ __forceinline__ void fwd_stage_eval(float4 *stage, bool hit, bool nee
     }
 }
 
+// the 32-byte record of candidate j where it is a hit (zeros elsewhere): loaded only once the fine test has said so
+__device__ __forceinline__ void fwd_record(const float4 *__restrict__ rec, unsigned j, bool hit, float4 &ra, float4 &rb)
+{
+    ra = rb = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (hit) {
+        const float4 *src = rec + 2 * (size_t)j;
+        ra = src[0];
+        rb = src[1];
+    }
+}
+
 // One wave, one 8x16 sub-tile at (sx0, sy0): accumulate every Gaussian binned near it into ar/ag/ab
 // (lane = column sx0 + lane%8, rows sy0 + lane/8 and +8).  With nparts > 1 the 64-candidate chunks are
 // dealt round-robin to `nparts` waves and the caller adds their partial sums.
@@ -248,94 +259,35 @@ __device__ __forceinline__ void fwd_tile(const Params &P, const PlanView &V, int
     const v2f py = {V.py[min(Y0, P.h - 1)], V.py[min(Y1, P.h - 1)]};
 
     const float4 *__restrict__ rec = V.rec;
-    const uint4 *__restrict__ bbox = V.bbox;
-    const unsigned *__restrict__ cs = V.cell_start;
-    const int wty = (sy0 - P.row0) >> SUBY_SHIFT, wtx = sx0 >> SUBX_SHIFT;
-
-    // Segment table: lane r holds [beg,end) of cell row cy0+r restricted to the columns a normal-class
-    // Gaussian can reach this sub-tile from (max half-extent from the plan header); one more lane holds
-    // the large class.  One vector round trip instead of a dependent scalar load per row.
-    const int rx = LARGE_ONLY ? 0 : (int)V.hdr[8], ry = LARGE_ONLY ? 0 : (int)V.hdr[9];
-    int nseg = 0;
-    unsigned sbeg = 0, send = 0;
-    if (rx > 0) {
-        const int cx0 = max(sx0 - rx, 0) >> CELL_SHIFT, cx1 = min((sx1 + rx) >> CELL_SHIFT, P.ncx - 1);
-        const int cy0 = max(sy0 - ry, 0) >> CELL_SHIFT, cy1 = min((sy1 + ry) >> CELL_SHIFT, P.ncy - 1);
-        nseg = cy1 - cy0 + 1;
-        if (lane < nseg) {
-            sbeg = cs[(cy0 + lane) * P.ncx + cx0];
-            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
-        }
-    }
-    if (lane == nseg) {
-        sbeg = cs[P.ncells];
-        send = cs[P.ncells + 1];
-    }
-    ++nseg;
+    // one level: table and fine test on the wave's own sub-tile (its band of spans: sy0's)
+    const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (sy0 - P.row0) >> SUBY_SHIFT};
+    const SegTable T = seg_table(P, V, sx0, sx1, sy0, sy1, LARGE_ONLY ? 0 : (int)V.hdr[8], LARGE_ONLY ? 0 : (int)V.hdr[9], lane);
 
     // Flat walk over full 64-candidate chunks of the concatenated segments (this wave takes chunks
     // part, part+nparts, ...), software-pipelined: the window record of the NEXT chunk is in flight while
     // the hits of the current one are evaluated.
-    const unsigned len = send - sbeg;
-    unsigned pin = len;  // inclusive prefix sum of the segment lengths over the lanes
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)pin, o);
-        if (lane >= o) pin += v;
-    }
-    const unsigned pex = pin - len;
-    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)pin, nseg - 1);
-    const unsigned nchunks = (total + 63u) >> 6;
-    const uint4 dead = make_uint4(0x7fffu, 0x7fffu, 0u, 0u);  // c0 = r0 = 32767 > c1 = r1 = 0: overlaps no tile
+    const unsigned nchunks = T.chunks();
     int rseg = 0;
     unsigned c = part;
-    unsigned j = c < nchunks ? fwd_candidate(c, lane, nseg, rseg, sbeg, pex, pin) : 0xffffffffu;
-    uint4 bb = dead;
-    uint2 bs = make_uint2(0u, 0u);
-    if (j != 0xffffffffu) {
-        bb = bbox[2 * (size_t)j];
-        bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
-    }
+    unsigned j = c < nchunks ? fwd_candidate(c, lane, T, rseg) : 0xffffffffu;
+    FineBox b = fine_load(V.bbox, j);
     while (c < nchunks) {
         const unsigned nc = c + nparts;
-        const unsigned nj = nc < nchunks ? fwd_candidate(nc, lane, nseg, rseg, sbeg, pex, pin) : 0xffffffffu;
-        uint4 nbb = dead;
-        uint2 nbs = make_uint2(0u, 0u);
-        if (nj != 0xffffffffu) {
-            nbb = bbox[2 * (size_t)nj];
-            nbs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)nj + 1);
-        }
-
-        const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
-        const int r0 = (int)(bb.y & 0x7fffu), r1 = (int)(bb.y >> 16);
-        bool hit = (c0 <= sx1) & (c1 >= sx0) & (r0 <= sy1) & (r1 >= sy0);
-        if (bb.y & 0x8000u) {  // per-tile-row column spans (k_bin)
-            const unsigned t = (unsigned)(wty - ((r0 - P.row0) >> SUBY_SHIFT)) & 7u, sh = (t & 3u) * 8u;
-            const unsigned lo = t < 4u ? bb.z : bs.x, hi = t < 4u ? bb.w : bs.y;
-            const int txr = wtx - (c0 >> SUBX_SHIFT);
-            hit &= (txr >= (int)((lo >> sh) & 0xffu)) & (txr <= (int)((hi >> sh) & 0xffu));
-        }
-        const bool needs = BOUNDED && (bb.x & 0x8000u) != 0u;
+        const unsigned nj = nc < nchunks ? fwd_candidate(nc, lane, T, rseg) : 0xffffffffu;
+        const FineBox nb = fine_load(V.bbox, nj);
+        const FineHit h = fine_test<BOUNDED, 1>(b, S, P.row0);
         // Compact the hits' records into this wave's LDS stage (untested ones first), then every lane
         // evaluates all of them from broadcast LDS reads.
-        float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-        if (hit) {
-            const float4 *src = rec + 2 * (size_t)j;
-            ra = src[0];
-            rb = src[1];
-        }
-        fwd_stage_eval<BOUNDED, PAIR>(stage, hit, needs, ra, rb, lane, px, py, P.dmax, ar, ag, ab);
-        c = nc; j = nj; bb = nbb; bs = nbs;
+        float4 ra, rb;
+        fwd_record(rec, j, h.hit, ra, rb);
+        fwd_stage_eval<BOUNDED, PAIR>(stage, h.hit, h.needs, ra, rb, lane, px, py, P.dmax, ar, ag, ab);
+        c = nc; j = nj; b = nb;
     }
 }
 
 // ---- two-level walk (large images) ---------------------------------------------------------------------
-// Measured: finding a sub-tile's hits -- fetching the 24-byte windows of every Gaussian binned within reach and
-// testing them, 64 per wave and round trip -- is HALF of the forward's time (the candidates come from cells within
-// the class' MAXIMUM extent, 4-5x more than hit).  The four waves of a workgroup render four sub-tiles side by side,
-// and their candidate sets are almost the same, so the workgroup walks the candidates of its 32x16 tile ONCE,
-// cooperatively: each wave tests a quarter of the chunks against the whole tile (window only, 8 bytes per
-// candidate) and appends the survivors to a shared list in LDS; after a barrier every wave runs the full test
-// (window + ellipse span) over that list only.  Rounds of 1024 candidates bound the list.
+// The four waves of a workgroup render four sub-tiles side by side: the workgroup walks the candidates of its 32x16 tile
+// once (coarse_pass), then every wave runs the full test (window + ellipse span) over the survivors only (survivor_walk).
 constexpr int COARSE_CHUNKS = 4;                          // coarse chunks per wave and round
 constexpr int COARSE_LIST = 4 * COARSE_CHUNKS * 64;       // candidates per round and part = capacity of the shared list
 
@@ -355,109 +307,21 @@ __device__ __forceinline__ void fwd_block(const Params &P, const PlanView &V, in
     const int Y0 = by0 + (lane >> 3);
     const v2f py = {V.py[min(Y0, P.h - 1)], V.py[min(Y0 + 8, P.h - 1)]};
     const float4 *__restrict__ rec = V.rec;
-    const uint4 *__restrict__ bbox = V.bbox;
-    const unsigned *__restrict__ cs = V.cell_start;
-    const int wtx = sx0 >> SUBX_SHIFT;
-
-    // segment table of the 32x16 tile (every wave builds the same one: a single vector round trip)
-    const int rx = (int)V.hdr[8], ry = (int)V.hdr[9];
-    int nseg = 0;
-    unsigned sbeg = 0, send = 0;
-    if (rx > 0) {
-        const int cx0 = max(bx0 - rx, 0) >> CELL_SHIFT, cx1 = min((bx1 + rx) >> CELL_SHIFT, P.ncx - 1);
-        const int cy0 = max(by0 - ry, 0) >> CELL_SHIFT, cy1 = min((by1 + ry) >> CELL_SHIFT, P.ncy - 1);
-        nseg = cy1 - cy0 + 1;
-        if (lane < nseg) {
-            sbeg = cs[(cy0 + lane) * P.ncx + cx0];
-            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
-        }
-    }
-    if (lane == nseg) {
-        sbeg = cs[P.ncells];
-        send = cs[P.ncells + 1];
-    }
-    ++nseg;
-    const unsigned len = send - sbeg;
-    unsigned pin = len;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)pin, o);
-        if (lane >= o) pin += v;
-    }
-    const unsigned pex = pin - len;
-    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)pin, nseg - 1);
-    const unsigned nchunks = (total + 63u) >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    // table and coarse pass on the 32x16 tile (every wave builds the same table), fine test on the wave's 8x16 sub-tile
+    const SubTile S{sx0, sx1, by0, by1, sx0 >> SUBX_SHIFT, (by0 - P.row0) >> SUBY_SHIFT};
+    const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
+    const unsigned nchunks = T.chunks();
     int rseg = 0;
 
     for (unsigned base = 0, round = 0; base < nchunks; base += 4u * PARTS * COARSE_CHUNKS, ++round) {
-        unsigned *cnt = s_cnt + (round & 1u);
-        // ---- phase A: this wave's share of the round's chunks against the whole tile -------------------
-        unsigned cj[COARSE_CHUNKS];
-        uint2 cw[COARSE_CHUNKS];
-#pragma unroll
-        for (int k = 0; k < COARSE_CHUNKS; ++k) {     // all loads of the round in flight together
-            const unsigned c = base + (unsigned)wv + 4u * PARTS * (unsigned)k;
-            cj[k] = c < nchunks ? fwd_candidate(c, lane, nseg, rseg, sbeg, pex, pin) : 0xffffffffu;
-            cw[k] = make_uint2(0x7fffu, 0x7fffu);
-            if (cj[k] != 0xffffffffu) cw[k] = V.win[cj[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < COARSE_CHUNKS; ++k) {
-            const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
-            const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
-            const bool hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
-            const unsigned long long m = __ballot(hit);
-            if (m) {
-                unsigned at = 0;
-                if (lane == 0) at = atomicAdd(cnt, (unsigned)__builtin_popcountll(m));
-                at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
-                if (hit) s_list[at + (unsigned)__builtin_popcountll(m & below)] = cj[k];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0u;   // nobody touches the other counter before the next barrier
-        const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)*cnt);
-        // ---- phase B: the full test of the tile's survivors against this wave's sub-tile(s) -------------
-        const int sy0 = by0, sy1 = by1;
-        const int wty = (sy0 - P.row0) >> SUBY_SHIFT;
+        const unsigned n = coarse_pass<4 * PARTS, COARSE_CHUNKS>(V, T, rseg, bx0, bx1, by0, by1, base, round, wv, lane, s_list, s_cnt);
+        // the wave's part of the survivors: chunks part, part + PARTS, ...
         if (live) {
-            const unsigned q0 = part * 64u;
-            unsigned j = q0 + lane < n ? s_list[q0 + lane] : 0xffffffffu;
-            const uint4 dead = make_uint4(0x7fffu, 0x7fffu, 0u, 0u);
-            uint4 bb = dead;
-            uint2 bs = make_uint2(0u, 0u);
-            if (j != 0xffffffffu) {
-                bb = bbox[2 * (size_t)j];
-                bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
-            }
-            for (unsigned q = q0; q < n; q += 64u * PARTS) {
-                const unsigned nq = q + 64u * PARTS + (unsigned)lane;
-                const unsigned nj = nq < n ? s_list[nq] : 0xffffffffu;
-                uint4 nbb = dead;
-                uint2 nbs = make_uint2(0u, 0u);
-                if (nj != 0xffffffffu) {
-                    nbb = bbox[2 * (size_t)nj];
-                    nbs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)nj + 1);
-                }
-                const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
-                const int r0 = (int)(bb.y & 0x7fffu), r1 = (int)(bb.y >> 16);
-                bool hit = (c0 <= sx1) & (c1 >= sx0) & (r0 <= sy1) & (r1 >= sy0);
-                if (bb.y & 0x8000u) {  // per-tile-row column spans (k_bin)
-                    const unsigned t = (unsigned)(wty - ((r0 - P.row0) >> SUBY_SHIFT)) & 7u, sh = (t & 3u) * 8u;
-                    const unsigned lo = t < 4u ? bb.z : bs.x, hi = t < 4u ? bb.w : bs.y;
-                    const int txr = wtx - (c0 >> SUBX_SHIFT);
-                    hit &= (txr >= (int)((lo >> sh) & 0xffu)) & (txr <= (int)((hi >> sh) & 0xffu));
-                }
-                const bool needs = BOUNDED && (bb.x & 0x8000u) != 0u;
-                float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-                if (hit) {
-                    const float4 *src = rec + 2 * (size_t)j;
-                    ra = src[0];
-                    rb = src[1];
-                }
-                fwd_stage_eval<BOUNDED, PAIR>(stage, hit, needs, ra, rb, lane, px, py, P.dmax, ar, ag, ab);
-                j = nj; bb = nbb; bs = nbs;
-            }
+            survivor_walk<BOUNDED, 1>(V.bbox, s_list, n, part * 64u, 64u * PARTS, lane, S, P.row0, [&](unsigned j, const FineHit h) {
+                float4 ra, rb;
+                fwd_record(rec, j, h.hit, ra, rb);
+                fwd_stage_eval<BOUNDED, PAIR>(stage, h.hit, h.needs, ra, rb, lane, px, py, P.dmax, ar, ag, ab);
+            });
         }
         __syncthreads();   // the list is rewritten in the next round
     }
@@ -670,6 +534,63 @@ __device__ __forceinline__ void fwd_store_px(const Params &P, float *__restrict_
     else { o[0] += r; o[1] += g; o[2] += b; }
 }
 
+// ---- what the two wide kernels (k_render_fwd16, k_render_fwd16_list) do with a chunk's hits, and with the finished pixels ----
+// Row-pair class of a candidate on the 16 x 16 sub-tile at row sy0: the hits are sorted by the row pairs their window reaches --
+// 0 both, 1 only the upper eight rows of the sub-tile (pair A), 2 only the lower eight (pair B); 3: windows cut by the dmax box
+// (exact in-kernel test) stay one list on both; 4: no hit.  (The list kernel reads the same classes off its quadrant masks.)
+__device__ __forceinline__ int wide_class(const FineHit &h, int sy0)
+{
+    return !h.hit ? 4 : h.needs ? 3 : h.r1 < sy0 + 8 ? 1 : h.r0 >= sy0 + 8 ? 2 : 0;
+}
+
+// stage the records (ra, rb) of one chunk's hits sorted by class and evaluate them: a window that ends in the upper half
+// costs one row part, not two (fwd_eval_lds16)
+template <bool BOUNDED>
+__device__ __forceinline__ void wide_stage_eval(float4 *stage, int cls, const float4 ra, const float4 rb, float px, v2f pyA, v2f pyB,
+                                                float dmax, v2f (&acc)[6], int lane)
+{
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2);
+    const unsigned long long m3 = BOUNDED ? __ballot(cls == 3) : 0ull;
+    const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1), n2 = __builtin_popcountll(m2);
+    const int n3 = __builtin_popcountll(m3);
+    if (n0 + n1 + n2 + n3 == 0) return;
+    __builtin_amdgcn_wave_barrier();
+    if (cls < 4) {
+        const unsigned long long mine = cls == 0 ? m0 : cls == 1 ? m1 : cls == 2 ? m2 : m3;
+        const int base = cls == 0 ? 0 : cls == 1 ? n0 : cls == 2 ? n0 + n1 : n0 + n1 + n2;
+        const int slot = base + __builtin_popcountll(mine & below);
+        stage[2 * slot] = ra;
+        stage[2 * slot + 1] = rb;
+    }
+    __builtin_amdgcn_wave_barrier();
+    fwd_eval_lds16<false, 3>(stage, 0, n0, px, pyA, pyB, dmax, acc);
+    fwd_eval_lds16<false, 1>(stage, n0, n0 + n1, px, pyA, pyB, dmax, acc);
+    fwd_eval_lds16<false, 2>(stage, n0 + n1, n0 + n1 + n2, px, pyA, pyB, dmax, acc);
+    if (BOUNDED) fwd_eval_lds16<true, 3>(stage, n0 + n1 + n2, n0 + n1 + n2 + n3, px, pyA, pyB, dmax, acc);
+}
+
+// the lane's four finished pixels (X, Y + {0, 4 | 8, 12}) of a live sub-tile (wave-uniform call; single images only reach the
+// wide kernels): the loss form of the store, one partial per 16 x 16 sub-tile (sub_row, sub_col), and / or the image
+__device__ __forceinline__ void wide_finish(const Params &P, float *__restrict__ img, int X, int Y, int sub_row, int sub_col,
+                                            const v2f (&acc)[6], int lane)
+{
+    if (P.loss_target) {
+        const Geo g = Geo{P.h, P.w, 0, 0};
+        const float c = fwd_loss_coef(P, g);
+        const float phi = (fwd_loss_px(P, g, 0, c, X, Y, acc[0].x, acc[1].x, acc[2].x) + fwd_loss_px(P, g, 0, c, X, Y + 4, acc[0].y, acc[1].y, acc[2].y)) +
+                          (fwd_loss_px(P, g, 0, c, X, Y + 8, acc[3].x, acc[4].x, acc[5].x) + fwd_loss_px(P, g, 0, c, X, Y + 12, acc[3].y, acc[4].y, acc[5].y));
+        fwd_loss_flush(P, sub_row, sub_col, phi, lane);
+        if (!img) return;
+    }
+    if (X < P.w) {
+        fwd_store_px(P, img, X, Y, acc[0].x, acc[1].x, acc[2].x);
+        fwd_store_px(P, img, X, Y + 4, acc[0].y, acc[1].y, acc[2].y);
+        fwd_store_px(P, img, X, Y + 8, acc[3].x, acc[4].x, acc[5].x);
+        fwd_store_px(P, img, X, Y + 12, acc[3].y, acc[4].y, acc[5].y);
+    }
+}
+
 // FINE forward (round 6): the two-level walk of fwd_block with EIGHT waves per 32 x 16-px tile, each an 8 x 8-px sub-tile, ONE
 // pixel per lane, the evaluation packed over record PAIRS.  Why: the forward is bound by VALU issue and at x4 its instructions
 // are evaluations -- a ~20-px window is evaluated on every 8 x 16 sub-tile it touches, 57 hits per sub-tile = 57 evaluations per
@@ -765,107 +686,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const float px = V.px[min(X, P.w - 1)], py = V.py[min(Y, P.h - 1)];
     float4 *stage = s_stage[wv];
     const float4 *__restrict__ rec = V.rec;
-    const uint4 *__restrict__ bbox = V.bbox;
-    const unsigned *__restrict__ cs = V.cell_start;
-    const int wtx = sx0 >> SUBX_SHIFT, wty = (by0 - P.row0) >> SUBY_SHIFT;     // in the units of k_bin's spans (8 columns, 16 rows)
-
-    // segment table of the 32x16 tile (every wave builds the same one; cf. fwd_block)
-    const int rx = (int)V.hdr[8], ry = (int)V.hdr[9];
-    int nseg = 0;
-    unsigned sbeg = 0, send = 0;
-    if (rx > 0) {
-        const int cx0 = max(bx0 - rx, 0) >> CELL_SHIFT, cx1 = min((bx1 + rx) >> CELL_SHIFT, P.ncx - 1);
-        const int cy0 = max(by0 - ry, 0) >> CELL_SHIFT, cy1 = min((by1 + ry) >> CELL_SHIFT, P.ncy - 1);
-        nseg = cy1 - cy0 + 1;
-        if (lane < nseg) {
-            sbeg = cs[(cy0 + lane) * P.ncx + cx0];
-            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
-        }
-    }
-    if (lane == nseg) {
-        sbeg = cs[P.ncells];
-        send = cs[P.ncells + 1];
-    }
-    ++nseg;
-    const unsigned len = send - sbeg;
-    unsigned pin = len;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)pin, o);
-        if (lane >= o) pin += v;
-    }
-    const unsigned pex = pin - len;
-    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)pin, nseg - 1);
-    const unsigned nchunks = (total + 63u) >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    // table and coarse pass on the 32x16 tile, fine test on the wave's 8x8 sub-tile (whose band of spans is the TILE's: by0)
+    const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (by0 - P.row0) >> SUBY_SHIFT};
+    const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
+    const unsigned nchunks = T.chunks();
     int rseg = 0;
     v2f acc[3] = {(v2f){0.f, 0.f}, (v2f){0.f, 0.f}, (v2f){0.f, 0.f}};
 
     for (unsigned base = 0, round = 0; base < nchunks; base += (unsigned)(FW * COARSE_CHUNKS), ++round) {
-        unsigned *cnt = s_cnt + (round & 1u);
-        // ---- phase A: this wave's share of the round's chunks against the whole tile (window only, 8 bytes per candidate) ----
-        unsigned cj[COARSE_CHUNKS];
-        uint2 cw[COARSE_CHUNKS];
-#pragma unroll
-        for (int k = 0; k < COARSE_CHUNKS; ++k) {
-            const unsigned c = base + (unsigned)wv + (unsigned)(FW * k);
-            cj[k] = c < nchunks ? fwd_candidate(c, lane, nseg, rseg, sbeg, pex, pin) : 0xffffffffu;
-            cw[k] = make_uint2(0x7fffu, 0x7fffu);
-            if (cj[k] != 0xffffffffu) cw[k] = V.win[cj[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < COARSE_CHUNKS; ++k) {
-            const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
-            const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
-            const bool hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
-            const unsigned long long m = __ballot(hit);
-            if (m) {
-                unsigned at = 0;
-                if (lane == 0) at = atomicAdd(cnt, (unsigned)__builtin_popcountll(m));
-                at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
-                if (hit) s_list[at + (unsigned)__builtin_popcountll(m & below)] = cj[k];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0u;   // nobody touches the other counter before the next barrier
-        const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)*cnt);
-        // ---- phase B: the full test of the tile's survivors against this wave's 8 x 8 sub-tile ----------------------
+        const unsigned n = coarse_pass<FW, COARSE_CHUNKS>(V, T, rseg, bx0, bx1, by0, by1, base, round, wv, lane, s_list, s_cnt);
         if (live) {
-            unsigned j = (unsigned)lane < n ? s_list[lane] : 0xffffffffu;
-            const uint4 dead = make_uint4(0x7fffu, 0x7fffu, 0u, 0u);
-            uint4 bb = dead;
-            uint2 bs = make_uint2(0u, 0u);
-            if (j != 0xffffffffu) {
-                bb = bbox[2 * (size_t)j];
-                bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
-            }
-            for (unsigned q = 0; q < n; q += 64u) {
-                const unsigned nq = q + 64u + (unsigned)lane;
-                const unsigned nj = nq < n ? s_list[nq] : 0xffffffffu;
-                uint4 nbb = dead;
-                uint2 nbs = make_uint2(0u, 0u);
-                if (nj != 0xffffffffu) {
-                    nbb = bbox[2 * (size_t)nj];
-                    nbs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)nj + 1);
-                }
-                const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
-                const int r0 = (int)(bb.y & 0x7fffu), r1 = (int)(bb.y >> 16);
-                bool hit = (c0 <= sx1) & (c1 >= sx0) & (r0 <= sy1) & (r1 >= sy0);
-                if (bb.y & 0x8000u) {  // per-16-row-band column spans (k_bin)
-                    const unsigned tb = (unsigned)(wty - ((r0 - P.row0) >> SUBY_SHIFT)) & 7u, sh = (tb & 3u) * 8u;
-                    const unsigned lo = tb < 4u ? bb.z : bs.x, hi = tb < 4u ? bb.w : bs.y;
-                    const int txr = wtx - (c0 >> SUBX_SHIFT);
-                    hit &= (txr >= (int)((lo >> sh) & 0xffu)) & (txr <= (int)((hi >> sh) & 0xffu));
-                }
-                const bool needs = BOUNDED && (bb.x & 0x8000u) != 0u;
-                float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-                if (hit) {
-                    const float4 *src = rec + 2 * (size_t)j;
-                    ra = src[0];
-                    rb = src[1];
-                }
-                fwd_stage_eval1<BOUNDED>(stage, hit, needs, ra, rb, lane, px, py, P.dmax, acc);
-                j = nj; bb = nbb; bs = nbs;
-            }
+            survivor_walk<BOUNDED, 1>(V.bbox, s_list, n, 0u, 64u, lane, S, P.row0, [&](unsigned j, const FineHit h) {
+                float4 ra, rb;
+                fwd_record(rec, j, h.hit, ra, rb);
+                fwd_stage_eval1<BOUNDED>(stage, h.hit, h.needs, ra, rb, lane, px, py, P.dmax, acc);
+            });
         }
         __syncthreads();   // the list is rewritten in the next round
     }
@@ -900,142 +735,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const v2f pyB = {V.py[min(Y + 8, P.h - 1)], V.py[min(Y + 12, P.h - 1)]};
     float4 *stage = s_stage[wv];
     const float4 *__restrict__ rec = V.rec;
-    const uint4 *__restrict__ bbox = V.bbox;
-    const unsigned *__restrict__ cs = V.cell_start;
-    const int wtx = sx0 >> SUBX_SHIFT, wty = (sy0 - P.row0) >> SUBY_SHIFT;   // in the units of k_bin's spans (8 columns, 16 rows)
-
-    // segment table of the 32x32 tile (every wave builds the same one; cf. fwd_block)
-    const int rx = (int)V.hdr[8], ry = (int)V.hdr[9];
-    int nseg = 0;
-    unsigned sbeg = 0, send = 0;
-    if (rx > 0) {
-        const int cx0 = max(bx0 - rx, 0) >> CELL_SHIFT, cx1 = min((bx1 + rx) >> CELL_SHIFT, P.ncx - 1);
-        const int cy0 = max(by0 - ry, 0) >> CELL_SHIFT, cy1 = min((by1 + ry) >> CELL_SHIFT, P.ncy - 1);
-        nseg = cy1 - cy0 + 1;
-        if (lane < nseg) {
-            sbeg = cs[(cy0 + lane) * P.ncx + cx0];
-            send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
-        }
-    }
-    if (lane == nseg) {
-        sbeg = cs[P.ncells];
-        send = cs[P.ncells + 1];
-    }
-    ++nseg;
-    const unsigned len = send - sbeg;
-    unsigned pin = len;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)pin, o);
-        if (lane >= o) pin += v;
-    }
-    const unsigned pex = pin - len;
-    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)pin, nseg - 1);
-    const unsigned nchunks = (total + 63u) >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    // table and coarse pass on the 32x32 tile, fine test on the wave's 16x16 sub-tile: two 8-column units of the spans
+    const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (sy0 - P.row0) >> SUBY_SHIFT};
+    const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
+    const unsigned nchunks = T.chunks();
     int rseg = 0;
     v2f acc[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) acc[k] = (v2f){0.f, 0.f};
 
     for (unsigned base = 0, round = 0; base < nchunks; base += 4u * COARSE_CHUNKS, ++round) {
-        unsigned *cnt = s_cnt + (round & 1u);
-        // ---- phase A: this wave's share of the round's chunks against the whole tile -------------------
-        unsigned cj[COARSE_CHUNKS];
-        uint2 cw[COARSE_CHUNKS];
-#pragma unroll
-        for (int k = 0; k < COARSE_CHUNKS; ++k) {
-            const unsigned c = base + (unsigned)wv + 4u * (unsigned)k;
-            cj[k] = c < nchunks ? fwd_candidate(c, lane, nseg, rseg, sbeg, pex, pin) : 0xffffffffu;
-            cw[k] = make_uint2(0x7fffu, 0x7fffu);
-            if (cj[k] != 0xffffffffu) cw[k] = V.win[cj[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < COARSE_CHUNKS; ++k) {
-            const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
-            const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
-            const bool hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
-            const unsigned long long m = __ballot(hit);
-            if (m) {
-                unsigned at = 0;
-                if (lane == 0) at = atomicAdd(cnt, (unsigned)__builtin_popcountll(m));
-                at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
-                if (hit) s_list[at + (unsigned)__builtin_popcountll(m & below)] = cj[k];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0u;
-        const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)*cnt);
-        // ---- phase B: the full test of the tile's survivors against this wave's sub-tile ------------------
+        const unsigned n = coarse_pass<4, COARSE_CHUNKS>(V, T, rseg, bx0, bx1, by0, by1, base, round, wv, lane, s_list, s_cnt);
         if (live) {
-            unsigned j = (unsigned)lane < n ? s_list[lane] : 0xffffffffu;
-            const uint4 dead = make_uint4(0x7fffu, 0x7fffu, 0u, 0u);
-            uint4 bb = dead;
-            uint2 bs = make_uint2(0u, 0u);
-            if (j != 0xffffffffu) {
-                bb = bbox[2 * (size_t)j];
-                bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
-            }
-            for (unsigned q = 0; q < n; q += 64u) {
-                const unsigned nq = q + 64u + (unsigned)lane;
-                const unsigned nj = nq < n ? s_list[nq] : 0xffffffffu;
-                uint4 nbb = dead;
-                uint2 nbs = make_uint2(0u, 0u);
-                if (nj != 0xffffffffu) {
-                    nbb = bbox[2 * (size_t)nj];
-                    nbs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)nj + 1);
-                }
-                const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
-                const int r0 = (int)(bb.y & 0x7fffu), r1 = (int)(bb.y >> 16);
-                bool hit = (c0 <= sx1) & (c1 >= sx0) & (r0 <= sy1) & (r1 >= sy0);
-                if (bb.y & 0x8000u) {  // per-tile-row column spans (k_bin), in 8-column units: the sub-tile covers two
-                    const unsigned t = (unsigned)(wty - ((r0 - P.row0) >> SUBY_SHIFT)) & 7u, sh = (t & 3u) * 8u;
-                    const unsigned lo = t < 4u ? bb.z : bs.x, hi = t < 4u ? bb.w : bs.y;
-                    const int txr = wtx - (c0 >> SUBX_SHIFT);
-                    hit &= (txr + 1 >= (int)((lo >> sh) & 0xffu)) & (txr <= (int)((hi >> sh) & 0xffu));
-                }
-                const bool needs = BOUNDED && (bb.x & 0x8000u) != 0u;
-                // Sort the hits by the row pairs their window reaches: both, only the upper eight rows of the sub-tile (pair A),
-                // only the lower eight (pair B); windows cut by the dmax box (exact in-kernel test) stay one list on both.
-                const int cls = !hit ? 4 : needs ? 3 : r1 < sy0 + 8 ? 1 : r0 >= sy0 + 8 ? 2 : 0;
-                const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2);
-                const unsigned long long m3 = BOUNDED ? __ballot(cls == 3) : 0ull;
-                const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1), n2 = __builtin_popcountll(m2);
-                const int n3 = __builtin_popcountll(m3);
-                if (n0 + n1 + n2 + n3) {
-                    __builtin_amdgcn_wave_barrier();
-                    if (hit) {
-                        const unsigned long long mine = cls == 0 ? m0 : cls == 1 ? m1 : cls == 2 ? m2 : m3;
-                        const int base = cls == 0 ? 0 : cls == 1 ? n0 : cls == 2 ? n0 + n1 : n0 + n1 + n2;
-                        const int slot = base + __builtin_popcountll(mine & below);
-                        const float4 *src = rec + 2 * (size_t)j;
-                        stage[2 * slot] = src[0];
-                        stage[2 * slot + 1] = src[1];
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    fwd_eval_lds16<false, 3>(stage, 0, n0, px, pyA, pyB, P.dmax, acc);
-                    fwd_eval_lds16<false, 1>(stage, n0, n0 + n1, px, pyA, pyB, P.dmax, acc);
-                    fwd_eval_lds16<false, 2>(stage, n0 + n1, n0 + n1 + n2, px, pyA, pyB, P.dmax, acc);
-                    if (BOUNDED) fwd_eval_lds16<true, 3>(stage, n0 + n1 + n2, n0 + n1 + n2 + n3, px, pyA, pyB, P.dmax, acc);
-                }
-                j = nj; bb = nbb; bs = nbs;
-            }
+            survivor_walk<BOUNDED, 2>(V.bbox, s_list, n, 0u, 64u, lane, S, P.row0, [&](unsigned j, const FineHit h) {
+                float4 ra, rb;
+                fwd_record(rec, j, h.hit, ra, rb);
+                wide_stage_eval<BOUNDED>(stage, wide_class(h, sy0), ra, rb, px, pyA, pyB, P.dmax, acc, lane);
+            });
         }
         __syncthreads();   // the list is rewritten in the next round
     }
-    if (P.loss_target && live) {   // wave-uniform: the loss form of the store (single images only)
-        const Geo g = Geo{P.h, P.w, 0, 0};
-        const float c = fwd_loss_coef(P, g);
-        const float phi = (fwd_loss_px(P, g, 0, c, X, Y, acc[0].x, acc[1].x, acc[2].x) + fwd_loss_px(P, g, 0, c, X, Y + 4, acc[0].y, acc[1].y, acc[2].y)) +
-                          (fwd_loss_px(P, g, 0, c, X, Y + 8, acc[3].x, acc[4].x, acc[5].x) + fwd_loss_px(P, g, 0, c, X, Y + 12, acc[3].y, acc[4].y, acc[5].y));
-        fwd_loss_flush(P, wty, wtx >> 1, phi, lane);      // (in the units the walk already keeps: 16 rows, 8 columns)
-        if (!img) return;
-    }
-    if (live && X < P.w) {
-        fwd_store_px(P, img, X, Y, acc[0].x, acc[1].x, acc[2].x);
-        fwd_store_px(P, img, X, Y + 4, acc[0].y, acc[1].y, acc[2].y);
-        fwd_store_px(P, img, X, Y + 8, acc[3].x, acc[4].x, acc[5].x);
-        fwd_store_px(P, img, X, Y + 12, acc[3].y, acc[4].y, acc[5].y);
-    }
+    if (live) wide_finish(P, img, X, Y, (sy0 - P.row0) >> 4, sx0 >> 4, acc, lane);
 }
 
 // ---- forward from the plan's tile lists (round 5) -------------------------------------------------------------
@@ -1152,90 +872,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const v2f pyA = {V.py[min(Y, P.h - 1)], V.py[min(Y + 4, P.h - 1)]};
     const v2f pyB = {V.py[min(Y + 8, P.h - 1)], V.py[min(Y + 12, P.h - 1)]};
     const float4 *__restrict__ rec = V.rec;
-    const unsigned long long below = (1ull << lane) - 1ull;
     v2f acc[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) acc[k] = (v2f){0.f, 0.f};
 
-    // stage the hits of one chunk sorted by row-pair class (cls 0 both, 1 upper rows only, 2 lower rows only, 3 dmax-tested,
-    // 4 none) and evaluate them
-    auto stage_eval = [&](int cls, const float4 ra, const float4 rb) {
-        const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2);
-        const unsigned long long m3 = BOUNDED ? __ballot(cls == 3) : 0ull;
-        const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1), n2 = __builtin_popcountll(m2);
-        const int n3 = __builtin_popcountll(m3);
-        if (n0 + n1 + n2 + n3 == 0) return;
-        __builtin_amdgcn_wave_barrier();
-        if (cls < 4) {
-            const unsigned long long mine = cls == 0 ? m0 : cls == 1 ? m1 : cls == 2 ? m2 : m3;
-            const int base = cls == 0 ? 0 : cls == 1 ? n0 : cls == 2 ? n0 + n1 : n0 + n1 + n2;
-            const int slot = base + __builtin_popcountll(mine & below);
-            stage[2 * slot] = ra;
-            stage[2 * slot + 1] = rb;
-        }
-        __builtin_amdgcn_wave_barrier();
-        fwd_eval_lds16<false, 3>(stage, 0, n0, px, pyA, pyB, P.dmax, acc);
-        fwd_eval_lds16<false, 1>(stage, n0, n0 + n1, px, pyA, pyB, P.dmax, acc);
-        fwd_eval_lds16<false, 2>(stage, n0 + n1, n0 + n1 + n2, px, pyA, pyB, P.dmax, acc);
-        if (BOUNDED) fwd_eval_lds16<true, 3>(stage, n0 + n1 + n2, n0 + n1 + n2 + n3, px, pyA, pyB, P.dmax, acc);
-    };
-    // one-level search of this sub-tile over candidate segments (the large class; every class when the tile's list overflowed)
+    // one-level search of this SUB-TILE over candidate segments (the large class; every class when the tile's list overflowed)
     auto search = [&](bool large_only) {
-        const uint4 *__restrict__ bbox = V.bbox;
-        const unsigned *__restrict__ cs = V.cell_start;
-        const int wtx = sx0 >> SUBX_SHIFT, wty = (sy0 - P.row0) >> SUBY_SHIFT;
-        const int rx = large_only ? 0 : (int)V.hdr[8], ry = large_only ? 0 : (int)V.hdr[9];
-        int nseg = 0;
-        unsigned sbeg = 0, send = 0;
-        if (rx > 0) {
-            const int cx0 = max(sx0 - rx, 0) >> CELL_SHIFT, cx1 = min((sx1 + rx) >> CELL_SHIFT, P.ncx - 1);
-            const int cy0 = max(sy0 - ry, 0) >> CELL_SHIFT, cy1 = min((sy1 + ry) >> CELL_SHIFT, P.ncy - 1);
-            nseg = cy1 - cy0 + 1;
-            if (lane < nseg) {
-                sbeg = cs[(cy0 + lane) * P.ncx + cx0];
-                send = cs[(cy0 + lane) * P.ncx + cx1 + 1];
-            }
-        }
-        if (lane == nseg) {
-            sbeg = cs[P.ncells];
-            send = cs[P.ncells + 1];
-        }
-        ++nseg;
-        const unsigned len = send - sbeg;
-        unsigned pin = len;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned v = (unsigned)__shfl_up((int)pin, o);
-            if (lane >= o) pin += v;
-        }
-        const unsigned pex = pin - len;
-        const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)pin, nseg - 1);
-        const unsigned nchunks = (total + 63u) >> 6;
+        const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (sy0 - P.row0) >> SUBY_SHIFT};
+        const SegTable T = seg_table(P, V, sx0, sx1, sy0, sy1, large_only ? 0 : (int)V.hdr[8], large_only ? 0 : (int)V.hdr[9], lane);
         int rseg = 0;
-        for (unsigned c = 0; c < nchunks; ++c) {
-            const unsigned j = fwd_candidate(c, lane, nseg, rseg, sbeg, pex, pin);
-            uint4 bb = make_uint4(0x7fffu, 0x7fffu, 0u, 0u);
-            uint2 bs = make_uint2(0u, 0u);
-            if (j != 0xffffffffu) {
-                bb = bbox[2 * (size_t)j];
-                bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
-            }
-            const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
-            const int r0 = (int)(bb.y & 0x7fffu), r1 = (int)(bb.y >> 16);
-            bool hit = (c0 <= sx1) & (c1 >= sx0) & (r0 <= sy1) & (r1 >= sy0);
-            if (bb.y & 0x8000u) {
-                const unsigned t = (unsigned)(wty - ((r0 - P.row0) >> SUBY_SHIFT)) & 7u, sh = (t & 3u) * 8u;
-                const unsigned lo = t < 4u ? bb.z : bs.x, hi = t < 4u ? bb.w : bs.y;
-                const int txr = wtx - (c0 >> SUBX_SHIFT);
-                hit &= (txr + 1 >= (int)((lo >> sh) & 0xffu)) & (txr <= (int)((hi >> sh) & 0xffu));
-            }
-            const bool needs = BOUNDED && (bb.x & 0x8000u) != 0u;
-            const int cls = !hit ? 4 : needs ? 3 : r1 < sy0 + 8 ? 1 : r0 >= sy0 + 8 ? 2 : 0;
-            float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-            if (hit) {
-                ra = rec[2 * (size_t)j];
-                rb = rec[2 * (size_t)j + 1];
-            }
-            stage_eval(cls, ra, rb);
+        for (unsigned c = 0; c < T.chunks(); ++c) {
+            const unsigned j = fwd_candidate(c, lane, T, rseg);
+            const FineHit h = fine_test<BOUNDED, 2>(fine_load(V.bbox, j), S, P.row0);
+            float4 ra, rb;
+            fwd_record(rec, j, h.hit, ra, rb);
+            wide_stage_eval<BOUNDED>(stage, wide_class(h, sy0), ra, rb, px, pyA, pyB, P.dmax, acc, lane);
         }
     };
 
@@ -1272,26 +923,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             }
             q += 64u;
             const uint2 nne = q + 64u + (unsigned)lane < cnt ? ent[q + 64u + lane] : none;
-            stage_eval(cls, ra, rb);
+            wide_stage_eval<BOUNDED>(stage, cls, ra, rb, px, pyA, pyB, P.dmax, acc, lane);
             cls = ncls; ra = na; rb = nb; ne = nne;
         }
         const unsigned nlarge = V.cell_start[P.ncells + 1] - V.cell_start[P.ncells];
         if (__builtin_amdgcn_readfirstlane((int)nlarge) != 0) search(true);
     }
-    if (P.loss_target) {   // wave-uniform: the loss form of the store (single images only)
-        const Geo g = Geo{P.h, P.w, 0, 0};
-        const float c = fwd_loss_coef(P, g);
-        const float phi = (fwd_loss_px(P, g, 0, c, X, Y, acc[0].x, acc[1].x, acc[2].x) + fwd_loss_px(P, g, 0, c, X, Y + 4, acc[0].y, acc[1].y, acc[2].y)) +
-                          (fwd_loss_px(P, g, 0, c, X, Y + 8, acc[3].x, acc[4].x, acc[5].x) + fwd_loss_px(P, g, 0, c, X, Y + 12, acc[3].y, acc[4].y, acc[5].y));
-        fwd_loss_flush(P, (sy0 - P.row0) >> 4, sx0 >> 4, phi, lane);
-        if (!img) return;
-    }
-    if (X < P.w) {
-        fwd_store_px(P, img, X, Y, acc[0].x, acc[1].x, acc[2].x);
-        fwd_store_px(P, img, X, Y + 4, acc[0].y, acc[1].y, acc[2].y);
-        fwd_store_px(P, img, X, Y + 8, acc[3].x, acc[4].x, acc[5].x);
-        fwd_store_px(P, img, X, Y + 12, acc[3].y, acc[4].y, acc[5].y);
-    }
+    wide_finish(P, img, X, Y, (sy0 - P.row0) >> 4, sx0 >> 4, acc, lane);
 }
 
 // Small images (fewer sub-tiles than the chip has wave slots, e.g. the 192x192 training crops of
