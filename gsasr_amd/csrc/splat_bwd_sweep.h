@@ -335,7 +335,7 @@ __device__ __forceinline__ void bwd_write(float v, int lane, const Params &P, un
     float *pc = g_coords + (size_t)i * stride2(P), *ps = g_sigmas + (size_t)i * stride3(P) - 2,
           *pk = g_colors + (size_t)i * stride3(P) - 5;
     float *dst = (k < 2 ? pc : (k < 5 ? ps : pk)) + k;
-    if (P.flags & GSASR_FLAG_OVERWRITE_GRADS) *dst = v;
+    if (P.flags & GSASR_FLAG_OVERWRITE_GRADS) store_out<ST_GRAD>(dst, v);
     else atomicAdd(dst, v);   // fire-and-forget: the wave must not end on a load-add-store round trip
 }
 

@@ -1025,6 +1025,102 @@ struct StepSrc {
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------
+// Cache policy of the step's bulk OUTPUT stores (the image, the gradients, the plan arrays).  What a kernel leaves dirty in its
+// XCD's L2 is written back behind its last wave, in front of the next kernel of the stream; a site names in one word how its
+// bytes leave:
+//   ST_PLAIN  the compiler's store: write-back, the line stays (dirty) in L2
+//   ST_WT     write-through (sc1): the bytes go to memory with the store and the line is dropped from L2
+//   ST_NT     non-temporal (nt): a streaming hint, the line is the first to be evicted
+// Only the store instruction differs: values, addresses and their order are the same under every policy, and nobody reads
+// these bytes back inside the kernel that stores them.  Measured per site at config 2 (profiles/heads_tails_ab.txt, DESIGN.md
+// 3.2): the interleaved image gains from write-through (k_render_fwd2 23.8 -> 22.9 us: its 12.6 MB no longer wait for the
+// write-back behind the last wave); the plan arrays gain in k_bin what the forward then loses reading them; the gradients'
+// scattered dwords lose under both (write-through +2 us on k_render_bwd).  The planar and the 8-bit image (one dword / one byte
+// per store: the narrow write-through forms) are not measured and stay plain.  The sites' policies are the constants below (a
+// what-if build overrides one with -DGSASR_ST_PLAN=ST_WT etc.).
+// ---------------------------------------------------------------------------------------------------
+enum StorePolicy { ST_PLAIN = 0, ST_WT = 1, ST_NT = 2 };
+#ifndef GSASR_ST_IMAGE
+#define GSASR_ST_IMAGE ST_WT
+#endif
+#ifndef GSASR_ST_IMAGE_CHW
+#define GSASR_ST_IMAGE_CHW ST_PLAIN
+#endif
+#ifndef GSASR_ST_IMAGE_U8
+#define GSASR_ST_IMAGE_U8 ST_PLAIN
+#endif
+#ifndef GSASR_ST_GRAD
+#define GSASR_ST_GRAD ST_PLAIN
+#endif
+#ifndef GSASR_ST_PLAN
+#define GSASR_ST_PLAN ST_PLAIN
+#endif
+constexpr StorePolicy ST_IMAGE = GSASR_ST_IMAGE;   // fwd_store / fwd_store_px: interleaved [rows, w, 3], 12 bytes per pixel
+constexpr StorePolicy ST_IMAGE_CHW = GSASR_ST_IMAGE_CHW;   // ... planar [3, rows, w]
+constexpr StorePolicy ST_IMAGE_U8 = GSASR_ST_IMAGE_U8;     // fwd_store_u8_px
+constexpr StorePolicy ST_GRAD = GSASR_ST_GRAD;     // bwd_write (the store branch; the atomic one is what it is)
+constexpr StorePolicy ST_PLAN = GSASR_ST_PLAN;     // k_bin: rec / fin / bbox / win
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+// one dword / two / four dwords of an output array (p aligned to the size of what is stored)
+template <StorePolicy POL>
+__device__ __forceinline__ void store_out(float *p, float v)
+{
+    if constexpr (POL == ST_WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (= global_store_dword .. sc1)
+    else if constexpr (POL == ST_NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+template <StorePolicy POL>
+__device__ __forceinline__ void store_out(unsigned char *p, unsigned char v)   // (a byte of the 8-bit image)
+{
+    if constexpr (POL == ST_WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (POL == ST_NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+template <StorePolicy POL>
+__device__ __forceinline__ void store_out(uint2 *p, uint2 v)
+{
+    if constexpr (POL == ST_WT)
+        __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v.x | ((unsigned long long)v.y << 32), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (POL == ST_NT) __builtin_nontemporal_store((v2u){v.x, v.y}, reinterpret_cast<v2u *>(p));
+    else *p = v;
+}
+// (16 bytes have no atomic form: the write-through store is written out; nothing after it in the kernel reads the line, so that
+// the compiler does not count it is harmless, and the wait state lets the store read its data registers before they are reused)
+__device__ __forceinline__ void store_wt16(void *p, v4f v)
+{
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+}
+template <StorePolicy POL>
+__device__ __forceinline__ void store_out(float4 *p, float4 v)
+{
+    if constexpr (POL == ST_WT) store_wt16(p, (v4f){v.x, v.y, v.z, v.w});
+    else if constexpr (POL == ST_NT) __builtin_nontemporal_store((v4f){v.x, v.y, v.z, v.w}, reinterpret_cast<v4f *>(p));
+    else *p = v;
+}
+template <StorePolicy POL>
+__device__ __forceinline__ void store_out(uint4 *p, uint4 v)
+{
+    store_out<POL>(reinterpret_cast<float4 *>(p), make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)));
+}
+// the three floats of one interleaved pixel (12 bytes, aligned to 4): one store instruction under the two policies that name one
+template <StorePolicy POL>
+__device__ __forceinline__ void store_out3(float *p, float r, float g, float b)
+{
+    if constexpr (POL == ST_WT) {
+        typedef float v3f __attribute__((ext_vector_type(3)));
+        asm volatile("global_store_dwordx3 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"((v3f){r, g, b}) : "memory");
+    } else if constexpr (POL == ST_NT) {
+        __builtin_nontemporal_store(r, p); __builtin_nontemporal_store(g, p + 1); __builtin_nontemporal_store(b, p + 2);
+    } else {
+        p[0] = r; p[1] = g; p[2] = b;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // How the render kernels FIND their Gaussians (the forward kernels and the tile backward): a segment table over the plan's
 // cells, walked in chunks of 64 candidates, each tested against a tile (coarse_pass) and a sub-tile (fine_test).  Written
 // once here; what differs from kernel to kernel is a parameter.

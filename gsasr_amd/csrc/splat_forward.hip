@@ -340,9 +340,9 @@ __device__ __forceinline__ void fwd_store_u8_px(const Params &P, size_t row, int
 {
     unsigned char *o = P.u8 + row * P.u8_pitch + 3 * (size_t)X;
     const unsigned char qr = fwd_quant(r), qg = fwd_quant(g), qb = fwd_quant(b);
-    o[0] = P.u8_swap ? qb : qr;
-    o[1] = qg;
-    o[2] = P.u8_swap ? qr : qb;
+    store_out<ST_IMAGE_U8>(o, P.u8_swap ? qb : qr);
+    store_out<ST_IMAGE_U8>(o + 1, qg);
+    store_out<ST_IMAGE_U8>(o + 2, P.u8_swap ? qr : qb);
 }
 
 // Fused pixel loss (gsasr_splat_forward_loss): the loss form of the image store.  With v the finished pixel and t the target,
@@ -448,25 +448,25 @@ __device__ __forceinline__ void fwd_store(const Params &P, const PlanView &V, fl
     if (P.flags & GSASR_FLAG_CHW_IMAGE) {
         if (ok0) {
             float *o = img + chw0;
-            if (store) { o[0] = ar.x; o[plane] = ag.x; o[2 * plane] = ab.x; }
-            else { o[0] += ar.x; o[plane] += ag.x; o[2 * plane] += ab.x; }
+            if (!store) { ar.x += o[0]; ag.x += o[plane]; ab.x += o[2 * plane]; }
+            store_out<ST_IMAGE_CHW>(o, ar.x); store_out<ST_IMAGE_CHW>(o + plane, ag.x); store_out<ST_IMAGE_CHW>(o + 2 * plane, ab.x);
         }
         if (ok1) {
             float *o = img + chw1;
-            if (store) { o[0] = ar.y; o[plane] = ag.y; o[2 * plane] = ab.y; }
-            else { o[0] += ar.y; o[plane] += ag.y; o[2 * plane] += ab.y; }
+            if (!store) { ar.y += o[0]; ag.y += o[plane]; ab.y += o[2 * plane]; }
+            store_out<ST_IMAGE_CHW>(o, ar.y); store_out<ST_IMAGE_CHW>(o + plane, ag.y); store_out<ST_IMAGE_CHW>(o + 2 * plane, ab.y);
         }
         return;
     }
     if (ok0) {
         float *o = img + ((size_t)(Y0 - P.row0) * P.w + X) * 3;
-        if (store) { o[0] = ar.x; o[1] = ag.x; o[2] = ab.x; }
-        else { o[0] += ar.x; o[1] += ag.x; o[2] += ab.x; }
+        if (!store) { ar.x += o[0]; ag.x += o[1]; ab.x += o[2]; }
+        store_out3<ST_IMAGE>(o, ar.x, ag.x, ab.x);
     }
     if (ok1) {
         float *o = img + ((size_t)(Y1 - P.row0) * P.w + X) * 3;
-        if (store) { o[0] = ar.y; o[1] = ag.y; o[2] = ab.y; }
-        else { o[0] += ar.y; o[1] += ag.y; o[2] += ab.y; }
+        if (!store) { ar.y += o[0]; ag.y += o[1]; ab.y += o[2]; }
+        store_out3<ST_IMAGE>(o, ar.y, ag.y, ab.y);
     }
 }
 
@@ -525,13 +525,13 @@ __device__ __forceinline__ void fwd_store_px(const Params &P, float *__restrict_
     if (P.flags & GSASR_FLAG_CHW_IMAGE) {
         const size_t plane = (size_t)(P.row1 - P.row0) * P.w;
         float *o = img + (size_t)(Y - P.row0) * P.w + X;
-        if (store) { o[0] = r; o[plane] = g; o[2 * plane] = b; }
-        else { o[0] += r; o[plane] += g; o[2 * plane] += b; }
+        if (!store) { r += o[0]; g += o[plane]; b += o[2 * plane]; }
+        store_out<ST_IMAGE_CHW>(o, r); store_out<ST_IMAGE_CHW>(o + plane, g); store_out<ST_IMAGE_CHW>(o + 2 * plane, b);
         return;
     }
     float *o = img + ((size_t)(Y - P.row0) * P.w + X) * 3;
-    if (store) { o[0] = r; o[1] = g; o[2] = b; }
-    else { o[0] += r; o[1] += g; o[2] += b; }
+    if (!store) { r += o[0]; g += o[1]; b += o[2]; }
+    store_out3<ST_IMAGE>(o, r, g, b);
 }
 
 // ---- what the two wide kernels (k_render_fwd16, k_render_fwd16_list) do with a chunk's hits, and with the finished pixels ----

@@ -779,17 +779,17 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
     const bool live = key <= (unsigned)P.ncells;
     const bool backward_records = !(P.flags & GSASR_FLAG_FORWARD_ONLY);
     if (live) {
-        V.rec[2 * j + 0] = recA;
-        V.rec[2 * j + 1] = recB;
-        V.bbox[2 * j + 1] = bc;
+        store_out<ST_PLAN>(V.rec + 2 * j + 0, recA);
+        store_out<ST_PLAN>(V.rec + 2 * j + 1, recB);
+        store_out<ST_PLAN>(V.bbox + 2 * j + 1, bc);
         if (V.qspan) V.qspan[j] = qs;
     }
     if (backward_records) {
-        if (live) V.fin[2 * j + 0] = finA;
-        V.fin[2 * j + 1] = finB;
+        if (live) store_out<ST_PLAN>(V.fin + 2 * j + 0, finA);
+        store_out<ST_PLAN>(V.fin + 2 * j + 1, finB);
     }
-    V.bbox[2 * j] = bb;
-    V.win[j] = make_uint2(bb.x, bb.y);
+    store_out<ST_PLAN>(V.bbox + 2 * j, bb);
+    store_out<ST_PLAN>(V.win + j, make_uint2(bb.x, bb.y));
     // the atomic accumulators (row chunks of a large Gaussian; windows wider than their slots in the tile backward) start from zero
     // (needed by: the large class; a plan with slots, whose too-wide windows fall back to them; the atomic variant)
     if (backward_records && live && (large || V.qspan || (P.flags & GSASR_FLAG_BWD_ATOMIC))) {
