@@ -105,6 +105,16 @@ class WindowAttn(ctypes.Structure):
                 ("scratch", ctypes.c_void_p)]
 
 
+class WindowAttnRope(ctypes.Structure):
+    """struct gsasr_window_attn_rope: the decoder's window attention with a 2-D rotary embedding (gsasr_window_attn_rope_forward / _backward)"""
+    _fields_ = [("windows", ctypes.c_int), ("heads", ctypes.c_int), ("nq", ctypes.c_int), ("nk", ctypes.c_int),
+                ("head_dim", ctypes.c_int), ("angle_rows", ctypes.c_int), ("scale", ctypes.c_float), ("flags", ctypes.c_uint),
+                ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("angles", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("grad_out", ctypes.c_void_p),
+                ("g_q", ctypes.c_void_p), ("g_k", ctypes.c_void_p), ("g_v", ctypes.c_void_p), ("g_angles", ctypes.c_void_p),
+                ("cossin", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
+
+
 RESIZE_NO_ANTIALIAS, RESIZE_ACCUMULATE, RESIZE_SHARED_SCALE = 1, 2, 4     # GSASR_RESIZE_*
 BATCH_HFLIP, BATCH_VFLIP, BATCH_TRANSPOSE = 1, 2, 4     # GSASR_BATCH_* (aug bits)
 BATCH_BGR, BATCH_NO_ANTIALIAS = 1, 2                    # GSASR_BATCH_* (flags)
@@ -116,6 +126,7 @@ LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
 _vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
 _rzp, _btp, _wap = ctypes.POINTER(Resize), ctypes.POINTER(Batch), ctypes.POINTER(WindowAttn)
+_wrp = ctypes.POINTER(WindowAttnRope)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -195,6 +206,10 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_window_attn_scratch_bytes": (_sz, [_wap]),
     "gsasr_window_attn_forward": (_i, [_wap, _vp]),
     "gsasr_window_attn_backward": (_i, [_wap, _vp]),
+    # ... with a rotary embedding instead of the bias (gsasr_window_attn_rope)
+    "gsasr_window_attn_rope_scratch_bytes": (_sz, [_wrp]),
+    "gsasr_window_attn_rope_forward": (_i, [_wrp, _vp]),
+    "gsasr_window_attn_rope_backward": (_i, [_wrp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1263,6 +1278,61 @@ def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_o
         d.scratch = scratch.data_ptr()
         check(lib().gsasr_window_attn_backward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_backward")
     return tuple(grads)
+
+
+# ---- the decoder's window attention with a rotary embedding (include/gsasr_splat.h: gsasr_window_attn_rope) -----
+def make_window_attn_rope(windows: int, heads: int, nq: int, nk: int, head_dim: int, angle_rows: int, scale: float) -> WindowAttnRope:
+    """a gsasr_window_attn_rope descriptor without pointers"""
+    d = WindowAttnRope(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(angle_rows))
+    d.scale, d.flags = float(scale), 0
+    return d
+
+
+def _window_attn_rope(q, k, v, angles, scale: float) -> WindowAttnRope:
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (angles, "angles")):
+        _chk(t, name)
+    heads = int(angles.shape[0])
+    d = make_window_attn_rope(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, angles.shape[1], scale)
+    d.q, d.k, d.v, d.angles = q.data_ptr(), k.data_ptr(), v.data_ptr(), angles.data_ptr()
+    return d
+
+
+def window_attn_rope_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, angles: torch.Tensor, scale: float, want_stats: bool = True):
+    """gsasr_window_attn_rope_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `angles` `[H,N,d/2]` fp32 contiguous ->
+    (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None, the (cos, sin) table `[H,N,d/2,2]` the backward reads)"""
+    d = _window_attn_rope(q, k, v, angles, scale)
+    dev = q.device
+    with _on(dev):
+        out = torch.empty_like(q)
+        stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
+        cossin = torch.empty(*angles.shape, 2, dtype=torch.float32, device=dev)
+        d.out, d.stats, d.cossin = out.data_ptr(), None if stats is None else stats.data_ptr(), cossin.data_ptr()
+        check(lib().gsasr_window_attn_rope_forward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_rope_forward")
+    return out, stats, cossin
+
+
+def window_attn_rope_backward(q, k, v, angles, scale: float, out, stats, cossin, grad_out, need=(True, True, True, True)):
+    """gsasr_window_attn_rope_backward -> (g_q, g_k, g_v, g_angles), None where `need` is False (the angle gradient is formed
+    from g_q and g_k: both are computed for it, and dropped here when not needed themselves)"""
+    d = _window_attn_rope(q, k, v, angles, scale)
+    for t, name in ((out, "out"), (stats, "stats"), (cossin, "cossin"), (grad_out, "grad_out")):
+        _chk(t, name)
+    if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq) or \
+            tuple(cossin.shape) != (*angles.shape, 2):
+        raise RuntimeError("out / grad_out must have q's shape, stats [W,H,nq] and cossin angles' shape + [2]")
+    dev = q.device
+    with _on(dev):
+        make = (need[0] or need[3], need[1] or need[3], need[2], need[3])
+        grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, angles), make)]
+        d.out, d.stats, d.cossin, d.grad_out = out.data_ptr(), stats.data_ptr(), cossin.data_ptr(), grad_out.data_ptr()
+        d.g_q, d.g_k, d.g_v, d.g_angles = [None if g is None else g.data_ptr() for g in grads]
+        n = int(lib().gsasr_window_attn_rope_scratch_bytes(ctypes.byref(d)))
+        if n == 0:
+            check(-1, "gsasr_window_attn_rope_scratch_bytes")
+        scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        d.scratch = scratch.data_ptr()
+        check(lib().gsasr_window_attn_rope_backward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_rope_backward")
+    return tuple(g if n else None for g, n in zip(grads, need))
 
 
 # ---- validation metrics of an 8-bit picture (include/gsasr_splat.h: gsasr_metrics) -----------------------------

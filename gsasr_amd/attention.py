@@ -2,12 +2,16 @@
 layers in every shipped configuration), fused:
 
     window_attention(q, k, v, bias_table, bias_index, scale=None)      # == window_attention_torch, one HIP call
-    use_hip_attention(model)                                            # switch a model's attention modules to it
+    window_attention_rope(q, k, v, angles, scale=None)                 # == window_attention_rope_torch: the RoPE decoder's
+    use_hip_attention(model)                                            # switch a model's attention modules to them
     constant_key_attention(mha, row)                                    # the layers' attention to the scale embedding, closed form
 
-CUDA tensors: gsasr_window_attn_forward / _backward (hand-written HIP, csrc/splat_attn.hip) as one autograd node on the current
-stream, or an error -- no torch fallback.  CPU tensors: the torch expression `window_attention_torch` below, which is also the
-contract.  include/gsasr_splat.h has the formulas.  fp32 only: under autocast the inputs are cast to fp32 at the node's boundary
+`window_attention_rope` is the attention of `Fea2GS_ROPE_AMP` (utils/fea2gsropeamp.py, the AMP and UltraPerformance models): q and
+k rotated by a 2-D rotary embedding with learned angles (`rope_angles`), then bias-free softmax(scale q k^T) v.
+
+CUDA tensors: gsasr_window_attn_forward / _backward and gsasr_window_attn_rope_forward / _backward (hand-written HIP,
+csrc/splat_attn.hip) as one autograd node on the current stream, or an error -- no torch fallback.  CPU tensors: the torch
+expressions `window_attention_torch` / `window_attention_rope_torch` below, which are also the contracts.  include/gsasr_splat.h has the formulas.  fp32 only: under autocast the inputs are cast to fp32 at the node's boundary
 (bf16 compute is not implemented).
 """
 import types
@@ -117,7 +121,105 @@ def window_attention(q, k, v, bias_table, bias_index, scale=None):
     return _WindowAttention.apply(q, k, v, bias_table, index, scale, keep)
 
 
+def _rotate(x, cos, sin):
+    """`x` `[W,n,H,d/2,2]` (re, im) times cos + i sin, `cos` / `sin` `[n,H,d/2]` -> `[W,n,H,d]`"""
+    re, im = x[..., 0], x[..., 1]
+    return torch.stack((re * cos - im * sin, re * sin + im * cos), dim=-1).flatten(-2)
+
+
+def window_attention_rope_torch(q, k, v, angles, scale=None):
+    """`q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]` (channel h*d + j = head h, component j), `angles` real `[H,N,d/2]` with
+    N >= max(nq, nk) -> `[W,nq,H*d]`: head h's column pair (2j, 2j+1) of the token at row n of q and of k is the complex number
+    re + i im, multiplied by cos + i sin of angles[h, n, j] (query i uses row i, key j row j); then softmax(scale q_rot k_rot^T) v
+    per window and head, in the inputs' dtype"""
+    W, nq, C = q.shape
+    nk, H = k.shape[1], angles.shape[0]
+    d = C // H
+    scale = d ** -0.5 if scale is None else scale
+    a = angles.permute(1, 0, 2)                                                # [N, H, d/2]
+    cos, sin = torch.cos(a).to(q.dtype), torch.sin(a).to(q.dtype)
+    qh = _rotate(q.view(W, nq, H, d // 2, 2), cos[:nq], sin[:nq]).permute(0, 2, 1, 3) * scale
+    kh = _rotate(k.view(W, nk, H, d // 2, 2), cos[:nk], sin[:nk]).permute(0, 2, 1, 3)
+    vh = v.view(W, nk, H, d).permute(0, 2, 1, 3)
+    attn = qh @ kh.transpose(-2, -1)
+    return (torch.softmax(attn, dim=-1) @ vh).transpose(1, 2).reshape(W, nq, C)
+
+
+class _WindowAttentionRope(torch.autograd.Function):
+    """(q, k, v, angles, scale, keep) -> out; `keep`: save the row statistic and the (cos, sin) table for a backward"""
+
+    @staticmethod
+    @fp32_boundary_fwd
+    def forward(ctx, q, k, v, angles, scale, keep):
+        from . import _cabi
+        q, k, v, angles = q.contiguous(), k.contiguous(), v.contiguous(), angles.contiguous()
+        out, stats, cossin = _cabi.window_attn_rope_forward(q, k, v, angles, scale, want_stats=keep)
+        if keep:
+            ctx.save_for_backward(q, k, v, angles, out, stats, cossin)
+            ctx.scale = scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @fp32_boundary_bwd
+    def backward(ctx, grad_out):
+        from . import _cabi
+        q, k, v, angles, out, stats, cossin = ctx.saved_tensors
+        g = _cabi.window_attn_rope_backward(q, k, v, angles, ctx.scale, out, stats, cossin, grad_out.to(torch.float32).contiguous(),
+                                            need=tuple(ctx.needs_input_grad[:4]))
+        return (*g, None, None)
+
+
+def window_attention_rope(q, k, v, angles, scale=None):
+    """softmax(scale rot(q) rot(k)^T) v per window and head, q and k rotated by `angles` (`window_attention_rope_torch` has the
+    shapes and the rotation), as ONE differentiable call: gradients to `q`, `k`, `v` and `angles`.  Limits: 1 <= nq, nk <= 256,
+    d even with 2 <= d <= 32, angles [H, N >= max(nq, nk), d/2] floating point on the inputs' device; anything else: ValueError
+    before any launch.  `scale`: default d ** -0.5."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (angles, "angles")):
+        if not (torch.is_tensor(t) and t.dtype.is_floating_point):
+            raise ValueError(f"{name} must be a floating-point tensor")
+    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: expected [W,nq,C], [W,nk,C], [W,nk,C]")
+    W, nq, C = (int(s) for s in q.shape)
+    nk = int(k.shape[1])
+    if angles.dim() != 3 or angles.shape[0] < 1 or angles.shape[2] < 1:
+        raise ValueError(f"angles has shape {tuple(angles.shape)}, expected [H,N,d/2]")
+    H, N, half = (int(s) for s in angles.shape)
+    if C != H * 2 * half:
+        raise ValueError(f"{C} channels are not {H} heads (angles' first extent) times a head dimension of {2 * half} (twice its last)")
+    d = 2 * half
+    if W < 1 or not 1 <= nq <= MAX_TOKENS or not 1 <= nk <= MAX_TOKENS:
+        raise ValueError(f"need W >= 1 and 1 <= nq, nk <= {MAX_TOKENS} (got W {W}, nq {nq}, nk {nk})")
+    if d > MAX_HEAD_DIM:
+        raise ValueError(f"head dimension {d} exceeds {MAX_HEAD_DIM}")
+    if N < max(nq, nk):
+        raise ValueError(f"angles has {N} rows, fewer than max(nq, nk) = {max(nq, nk)}")
+    scale = float(d ** -0.5 if scale is None else scale)
+    if not (q.device == k.device == v.device == angles.device):
+        raise ValueError("q, k, v and angles must be on one device")
+    if not q.is_cuda:
+        return window_attention_rope_torch(q, k, v, angles, scale)
+    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, angles))
+    q, k, v, angles = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, angles))
+    return _WindowAttentionRope.apply(q, k, v, angles, scale, keep)
+
+
 _ATTRS = ("qhead", "khead", "vhead", "proj", "relative_position_bias_table", "relative_position_index", "num_heads")
+_ROPE_ATTRS = ("qhead", "khead", "vhead", "proj", "num_heads", "rope_freqs", "rope_t_x", "rope_t_y")
+
+
+def rope_angles(freqs, t_x, t_y):
+    """the angles `[H,N,d/2]` of the RoPE modules: t_x freqs[0] + t_y freqs[1] (`compute_cis` of utils/fea2gsropeamp.py without
+    the `polar`), in fp32 with autocast disabled; differentiable in `freqs` `[2,H,d/2]`"""
+    with torch.autocast(device_type=freqs.device.type, enabled=False):
+        return t_x[None, :, None] * freqs[0][:, None, :] + t_y[None, :, None] * freqs[1][:, None, :]
+
+
+def _rope_module_forward(self, gs, feat=None):
+    """the RoPE module's own Linears around window_attention_rope: `forward(gs)` or `forward(gs, feat)`"""
+    src = gs if feat is None else feat
+    angles = rope_angles(self.rope_freqs, self.rope_t_x, self.rope_t_y)
+    return self.proj(window_attention_rope(self.qhead(gs), self.khead(src), self.vhead(src), angles))
 
 
 def _module_forward(self, gs, feat=None):
@@ -134,12 +236,17 @@ def _module_forward(self, gs, feat=None):
 def use_hip_attention(model) -> int:
     """give every module of `model` that carries the decoder's attention attributes (qhead, khead, vhead, proj,
     relative_position_bias_table, relative_position_index, num_heads: WindowCrossAttn and GSSelfAttn) a `forward` that runs
-    its three Linears, `window_attention` and `proj` with the module's own parameters -> the number of modules switched.
-    Parameters, buffers and state dicts are untouched."""
+    its three Linears, `window_attention` and `proj` with the module's own parameters; likewise every module of the RoPE
+    decoder (qhead, khead, vhead, proj, num_heads, rope_freqs, rope_t_x, rope_t_y and no relative_position_bias_table:
+    WindowCrossAttn and GSSelfAttn of utils/fea2gsropeamp.py, rope_mixed or not) one that runs `rope_angles` and
+    `window_attention_rope` -> the number of modules switched, both kinds.  Parameters, buffers and state dicts are untouched."""
     n = 0
     for m in model.modules():
         if all(hasattr(m, a) for a in _ATTRS):
             m.forward = types.MethodType(_module_forward, m)
+            n += 1
+        elif all(hasattr(m, a) for a in _ROPE_ATTRS) and not hasattr(m, "relative_position_bias_table"):
+            m.forward = types.MethodType(_rope_module_forward, m)
             n += 1
     return n
 

@@ -30,6 +30,14 @@
 // Every workgroup owns its window-head whole: dq, dk, dv are written once, without atomics, and two runs give the same bits.
 // Both backward kernels form S exactly as the forward did (same chain, then the bias): the statistic is of those bits.
 // The table gradient depends on the order of the LDS float adds.
+//
+// The rotary variant (gsasr_window_attn_rope_forward / _backward: the RoPE decoder of utils/fea2gsropeamp.py) is the same three
+// kernels with ROPE = true: no table, no index, no bias; q and k rotated by the angles' (cos, sin), which k_attn_cossin writes
+// once per call.  K (or scale Q in k_attn_bwd_kv) is rotated as it is staged, the row kept in registers as it is loaded, every
+// value through att_rot and "rotate, then scale", so that S has the forward's bits in all three; dq and dk are multiplied by the
+// conjugate at the store (the pair's other column is on lane ^ 1 of the D layout).  The angle gradient is a sum over windows of
+// Im(conj(x) g_x) of the un-rotated q, k and their gradients: k_attn_angle_grad (a slice of windows per thread, in window
+// order) and k_attn_angle_sum (the slices in order) -- fixed order, no atomics, the same bits in every run.
 #include "splat_common.h"
 
 using namespace gsasr_detail;
@@ -51,6 +59,10 @@ struct AttnArgs {
     int windows, heads, nq, nk, d, rows, wslots;
     bool vec;       // index rows can be read 16 bytes at a time
     float scale;
+    // the rotary variant (ROPE kernels; no table, no index)
+    const float *angles;
+    float *cossin, *g_angles;
+    int arows, achunk, aslices;     // angle rows; windows per slice and slices of the angle gradient's first stage
 };
 
 __device__ __forceinline__ att_f4 att_mfma(float a, float b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -117,6 +129,58 @@ __device__ __forceinline__ void att_load_row(float (&r)[8], const float *__restr
     }
 }
 
+// Rotary variant: column pair (2 j, 2 j + 1) of a token at angle row n is the complex number re + i im times cos + i sin of
+// angles[h, n, j].  One component: x its own column, xp the pair's other column, odd = the imaginary one.  EVERY kernel forms
+// a rotated value through this function and then multiplies by `mul`, so that forward and backward see the same bits; with
+// (cs, -sn) it is the conjugate (the gradient of the un-rotated input from that of the rotated one: a rotation is unitary)
+__device__ __forceinline__ float att_rot(float x, float xp, float cs, float sn, bool odd) { return fmaf(x, cs, xp * (odd ? sn : -sn)); }
+
+// att_stage with the rows rotated: `cs` = the head's (cos, sin) rows [angle_rows][d / 2].  The pair's other column is on the
+// neighbouring lane (element e = 32 row + column, consecutive over the lanes)
+__device__ __forceinline__ void att_stage_rot(float *s, const float *__restrict__ src, const float2 *__restrict__ cs, int n, int rows_pad, int d, int C, float mul)
+{
+    const int nthr = blockDim.x, hd = d >> 1;
+    for (int e0 = threadIdx.x; e0 < rows_pad * 32; e0 += 8 * nthr) {
+        float x[8];
+        float2 t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + nthr * u, j = e >> 5, c = e & 31;
+            const bool ok = j < n && c < d;
+            x[u] = ok ? src[(size_t)j * C + c] : 0.f;
+            t[u] = ok ? cs[j * hd + (c >> 1)] : make_float2(0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + nthr * u;
+            const float xp = __shfl_xor(x[u], 1);       // (whole waves get here: rows_pad * 32 and nthr are multiples of 64)
+            if (e < rows_pad * 32) s[(e >> 5) * ATT_LD + (e & 31)] = att_rot(x[u], xp, t[u].x, t[u].y, e & 1) * mul;
+        }
+    }
+}
+
+// att_load_row with the row rotated by its (cos, sin) row `cs` [d / 2]: both columns of a pair in one 8-byte load
+__device__ __forceinline__ void att_load_row_rot(float (&r)[8], const float *__restrict__ row, const float2 *__restrict__ cs, int g, int d, bool valid, float mul)
+{
+    const bool odd = g & 1;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int c = 4 * s + g, pj = c >> 1;
+        const bool ok = valid && c < d;
+        const float2 xy = ok ? *reinterpret_cast<const float2 *>(row + 2 * pj) : make_float2(0.f, 0.f);
+        const float2 t = ok ? cs[pj] : make_float2(0.f, 0.f);
+        r[s] = att_rot(odd ? xy.y : xy.x, odd ? xy.x : xy.y, t.x, t.y, odd) * mul;
+    }
+}
+
+// the D tile's value `a` (row of angle row `n`, column c16 + 16 * half) times the conjugate: its pair's other column is on lane ^ 1
+__device__ __forceinline__ float att_unrot(float a, const float2 *__restrict__ cs, int n, int hd, int col, int d)
+{
+    const float xp = __shfl_xor(a, 1);
+    const float2 t = col < d ? cs[n * hd + (col >> 1)] : make_float2(0.f, 0.f);
+    return att_rot(a, xp, t.x, -t.y, col & 1);
+}
+
 // D = sum_s A_lds[row0 + (l & 15)][4 s + g] * b[s]: a 16 x 16 tile over the 32 padded columns
 __device__ __forceinline__ att_f4 att_tile(const float *s_a, int row0, int c16, int g, const float (&b)[8])
 {
@@ -130,7 +194,8 @@ __device__ __forceinline__ att_f4 att_tile(const float *s_a, int row0, int c16, 
     return acc;
 }
 
-template <int MAXT, bool STATS, bool TLDS>
+// ROPE: q and k rotated (K as it is staged, the query row in registers; rotate, then scale), no table / index / bias
+template <int MAXT, bool STATS, bool TLDS, bool ROPE = false>
 __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -138,7 +203,9 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
     const int nt = (nk + 15) >> 4, nkp = nt << 4;
     float *s_k = s_mem, *s_v = s_mem + nkp * ATT_LD, *s_tb = s_v + nkp * ATT_LD;
-    att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+    const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
+    if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * C + h * d, cs, nk, nkp, d, C, 1.f);
+    else att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
     att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
@@ -147,16 +214,17 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
     for (int qt = wave; qt < nqt; qt += nwaves) {
         const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
         float qr[8];
-        att_load_row(qr, A.q + ((size_t)w * nq + ic) * C + h * d, g, d, true, A.scale);
+        if (ROPE) att_load_row_rot(qr, A.q + ((size_t)w * nq + ic) * C + h * d, cs + ic * (d >> 1), g, d, true, A.scale);
+        else att_load_row(qr, A.q + ((size_t)w * nq + ic) * C + h * d, g, d, true, A.scale);
         att_f4 sc[MAXT];
-        const int *irow = A.index + (size_t)ic * nk;
+        const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
         float m = -INFINITY;
         // the biases of the whole row first, for every tile the instantiation has (indices past nk are clamped, so nothing here
         // depends on nt and all the loads are in flight together).  They are ADDED to the finished products, as the torch
         // expression does: as the chains' initial accumulators a bias of 50 costs the eight products their low bits
-        att_f4 bs[MAXT];
+        att_f4 bs[ROPE ? 1 : MAXT];
 #pragma unroll
-        for (int t = 0; t < MAXT; ++t) {
+        for (int t = 0; t < (ROPE ? 0 : MAXT); ++t) {
             int ix[4];
             att_load_index(ix, irow, 16 * t + 4 * g, nk, A.vec);
 #pragma unroll
@@ -168,7 +236,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
                 sc[t] = att_tile(s_k, 16 * t, c16, g, qr);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    sc[t][r] = 16 * t + 4 * g + r < nk ? sc[t][r] + bs[t][r] : -INFINITY;
+                    sc[t][r] = 16 * t + 4 * g + r < nk ? (ROPE ? sc[t][r] : sc[t][r] + bs[ROPE ? 0 : t][r]) : -INFINITY;
                     m = fmaxf(m, sc[t][r]);
                 }
             }
@@ -212,7 +280,8 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
 }
 
 // TAB: 0 no table gradient, 1 binned in LDS -> a partial column, 2 global atomics on g_table
-template <int TAB, bool TLDS>
+// ROPE (TAB 0, no table): K staged rotated, the query row rotated in registers, dq times the conjugate at the store
+template <int TAB, bool TLDS, bool ROPE = false>
 __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -221,11 +290,13 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
     const int nt = (nk + 15) >> 4, nkp = nt << 4, nqt = (nq + 15) >> 4;
     float *s_k = s_mem, *s_v = s_mem + nkp * ATT_LD, *s_tb = s_v + nkp * ATT_LD, *s_tab = s_tb + (TLDS ? A.rows : 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
     if (TAB == 1) for (int t = threadIdx.x; t < A.rows; t += blockDim.x) s_tab[t] = 0.f;
     if (TLDS) att_stage_table(s_tb, A, h);
     for (int w = slot; w < A.windows; w += A.wslots) {
         __syncthreads();        // (the previous window's reads of s_k / s_v are done; s_tab is zeroed)
-        att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+        if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * C + h * d, cs, nk, nkp, d, C, 1.f);
+        else att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
         att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
         __syncthreads();
         for (int qt = wave; qt < nqt; qt += nwaves) {
@@ -233,7 +304,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
             const bool iv = i < nq;
             const size_t qoff = ((size_t)w * nq + ic) * C + h * d;
             float qr[8], gr[8], orow[8];
-            att_load_row(qr, A.q + qoff, g, d, true, A.scale);
+            if (ROPE) att_load_row_rot(qr, A.q + qoff, cs + ic * (d >> 1), g, d, true, A.scale);
+            else att_load_row(qr, A.q + qoff, g, d, true, A.scale);
             att_load_row(gr, A.grad_out + qoff, g, d, iv, 1.f);
             att_load_row(orow, A.out + qoff, g, d, iv, 1.f);
             float delta = 0.f;
@@ -241,19 +313,23 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
             for (int s = 0; s < 8; ++s) delta = fmaf(gr[s], orow[s], delta);
             delta = att_row_sum(delta);
             const float lse = A.stats[((size_t)w * A.heads + h) * nq + ic];
-            const int *irow = A.index + (size_t)ic * nk;
+            const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
             att_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};
             // the tile's indices are loaded one tile ahead and its biases before its products: the dependent round trips run
             // under the MFMAs
             int ix[4], ix1[4];
-            att_load_index(ix, irow, 4 * g, nk, A.vec);
-            att_load_index(ix1, irow, 16 + 4 * g, nk, A.vec);
+            if (!ROPE) {
+                att_load_index(ix, irow, 4 * g, nk, A.vec);
+                att_load_index(ix1, irow, 16 + 4 * g, nk, A.vec);
+            }
             for (int t = 0; t < nt; ++t) {
                 float b[4];
                 int ixn[4];     // (two tiles ahead: one tile's products are shorter than a round trip to L2)
+                if (!ROPE) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
-                att_load_index(ixn, irow, 16 * t + 32 + 4 * g, nk, A.vec);
+                    for (int r = 0; r < 4; ++r) b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+                    att_load_index(ixn, irow, 16 * t + 32 + 4 * g, nk, A.vec);
+                }
                 const float *kr = s_k + (16 * t + 4 * g) * ATT_LD + c16;
                 float k0[4], k1[4], ds[4];
 #pragma unroll
@@ -269,7 +345,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
                 for (int r = 0; r < 4; ++r) {
                     const int j = 16 * t + 4 * g + r;
                     const bool valid = iv && j < nk;
-                    const float p = valid ? att_exp((sc[r] + b[r]) - lse) : 0.f;
+                    const float p = valid ? att_exp((ROPE ? sc[r] : sc[r] + b[r]) - lse) : 0.f;
                     ds[r] = p * (dp[r] - delta);
                     if (TAB == 1 && valid) atomicAdd(&s_tab[ix[r]], ds[r]);
                     if (TAB == 2 && valid) atomicAdd(&A.g_table[(size_t)ix[r] * A.heads + h], ds[r]);
@@ -286,10 +362,15 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int io = qt * 16 + 4 * g + r;
+                    float u0 = 0.f, u1 = 0.f;
+                    if (ROPE) {         // (before the row's test: the shuffle wants the whole wave)
+                        u0 = att_unrot(dq0[r] * A.scale, cs, min(io, nq - 1), d >> 1, c16, d);
+                        u1 = att_unrot(dq1[r] * A.scale, cs, min(io, nq - 1), d >> 1, c16 + 16, d);
+                    }
                     if (io < nq) {
                         float *po = A.g_q + ((size_t)w * nq + io) * C + h * d;
-                        if (c16 < d) po[c16] = dq0[r] * A.scale;
-                        if (c16 + 16 < d) po[c16 + 16] = dq1[r] * A.scale;
+                        if (c16 < d) po[c16] = ROPE ? u0 : dq0[r] * A.scale;
+                        if (c16 + 16 < d) po[c16 + 16] = ROPE ? u1 : dq1[r] * A.scale;
                     }
                 }
             }
@@ -320,7 +401,8 @@ __global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgs A)
     }
 }
 
-template <bool TLDS>
+// ROPE: scale Q staged rotated, the key row rotated in registers, dk times the conjugate at the store
+template <bool TLDS, bool ROPE = false>
 __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -329,7 +411,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
     const int nqt = (nq + 15) >> 4, nqp = nqt << 4, nkt = (nk + 15) >> 4;
     float *s_q = s_mem, *s_g = s_mem + nqp * ATT_LD, *s_lse = s_g + nqp * ATT_LD, *s_delta = s_lse + nqp, *s_tb = s_delta + nqp;
     const size_t qbase = (size_t)w * nq * C + h * d;
-    att_stage(s_q, A.q + qbase, nq, nqp, d, C, A.scale);
+    const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
+    if (ROPE) att_stage_rot(s_q, A.q + qbase, cs, nq, nqp, d, C, A.scale);
+    else att_stage(s_q, A.q + qbase, nq, nqp, d, C, A.scale);
     att_stage(s_g, A.grad_out + qbase, nq, nqp, d, C, 1.f);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
@@ -349,22 +433,27 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
         const bool jv = j < nk;
         const size_t koff = ((size_t)w * nk + jc) * C + h * d;
         float kr[8], vr[8];
-        att_load_row(kr, A.k + koff, g, d, jv, 1.f);
+        if (ROPE) att_load_row_rot(kr, A.k + koff, cs + jc * (d >> 1), g, d, jv, 1.f);
+        else att_load_row(kr, A.k + koff, g, d, jv, 1.f);
         att_load_row(vr, A.v + koff, g, d, jv, 1.f);
         att_f4 dk0 = {0.f, 0.f, 0.f, 0.f}, dk1 = dk0, dv0 = dk0, dv1 = dk0;
         int ix[4], ix1[4];      // (loaded two tiles ahead, unconditionally: as in k_attn_bwd_q)
+        if (!ROPE) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            ix[r] = A.index[(size_t)min(4 * g + r, nq - 1) * nk + jc];
-            ix1[r] = A.index[(size_t)min(16 + 4 * g + r, nq - 1) * nk + jc];
+            for (int r = 0; r < 4; ++r) {
+                ix[r] = A.index[(size_t)min(4 * g + r, nq - 1) * nk + jc];
+                ix1[r] = A.index[(size_t)min(16 + 4 * g + r, nq - 1) * nk + jc];
+            }
         }
         for (int t = 0; t < nqt; ++t) {
             float b[4];
             int ixn[4];
+            if (!ROPE) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
-                ixn[r] = A.index[(size_t)min(16 * t + 32 + 4 * g + r, nq - 1) * nk + jc];
+                for (int r = 0; r < 4; ++r) {
+                    b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+                    ixn[r] = A.index[(size_t)min(16 * t + 32 + 4 * g + r, nq - 1) * nk + jc];
+                }
             }
             const float *gq = s_g + (16 * t + 4 * g) * ATT_LD + c16, *qq = s_q + (16 * t + 4 * g) * ATT_LD + c16;
             float g0[4], g1[4], q0[4], q1[4], lse[4], dl[4];
@@ -380,7 +469,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int i = 16 * t + 4 * g + r;
-                p[r] = (jv && i < nq) ? att_exp((sc[r] + b[r]) - lse[r]) : 0.f;
+                p[r] = (jv && i < nq) ? att_exp((ROPE ? sc[r] : sc[r] + b[r]) - lse[r]) : 0.f;
                 ds[r] = p[r] * (dp[r] - dl[r]);
                 ix[r] = ix1[r];
                 ix1[r] = ixn[r];
@@ -396,11 +485,16 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int jo = kt * 16 + 4 * g + r;
+            float u0 = 0.f, u1 = 0.f;
+            if (ROPE) {         // (before the row's test: the shuffle wants the whole wave)
+                u0 = att_unrot(dk0[r], cs, min(jo, nk - 1), d >> 1, c16, d);
+                u1 = att_unrot(dk1[r], cs, min(jo, nk - 1), d >> 1, c16 + 16, d);
+            }
             if (jo < nk) {
                 const size_t off = ((size_t)w * nk + jo) * C + h * d;
                 if (A.g_k) {
-                    if (c16 < d) A.g_k[off + c16] = dk0[r];
-                    if (c16 + 16 < d) A.g_k[off + c16 + 16] = dk1[r];
+                    if (c16 < d) A.g_k[off + c16] = ROPE ? u0 : dk0[r];
+                    if (c16 + 16 < d) A.g_k[off + c16 + 16] = ROPE ? u1 : dk1[r];
                 }
                 if (A.g_v) {
                     if (c16 < d) A.g_v[off + c16] = dv0[r];
@@ -409,6 +503,57 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
             }
         }
     }
+}
+
+// cossin[h, n, j] = (cos, sin) of angles[h, n, j], once per call: the accurate sincosf (angles reach tens of radians, where the
+// hardware's v_sin_f32 / v_cos_f32 lose the bits the scores need), read by every workgroup of the three attention kernels
+__global__ __launch_bounds__(256) void k_attn_cossin(AttnArgs A)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= A.heads * A.arows * (A.d >> 1)) return;
+    float sn, cs;
+    sincosf(A.angles[e], &sn, &cs);
+    reinterpret_cast<float2 *>(A.cossin)[e] = make_float2(cs, sn);
+}
+
+// d L / d angles[h, n, j] = sum over windows of Im(conj(x) g_x), x = q (n < nq) and x = k (n < nk): the column pair (2 j, 2 j + 1)
+// of head h and token n of the UN-rotated input and of its gradient.  One thread per angle; blockIdx.y = a slice of `achunk`
+// consecutive windows, added in window order (q's term, then k's) into the slice's partial (or g_angles itself when there is one
+// slice).  Rows past both nq and nk get exactly 0.
+__global__ __launch_bounds__(256) void k_attn_angle_grad(AttnArgs A)
+{
+    const int hd = A.d >> 1, per = A.heads * A.arows * hd;
+    const int e = blockIdx.x * 256 + threadIdx.x, slice = blockIdx.y;
+    if (e >= per) return;
+    const int j = e % hd, n = (e / hd) % A.arows, h = e / (hd * A.arows);
+    const int C = A.heads * A.d, col = h * A.d + 2 * j;
+    const int w0 = slice * A.achunk, w1 = min(A.windows, w0 + A.achunk);
+    float a = 0.f;
+    for (int w = w0; w < w1; ++w) {
+        if (n < A.nq) {
+            const size_t off = ((size_t)w * A.nq + n) * C + col;
+            const float2 x = *reinterpret_cast<const float2 *>(A.q + off), gx = *reinterpret_cast<const float2 *>(A.g_q + off);
+            a = fmaf(x.x, gx.y, a);
+            a = fmaf(-x.y, gx.x, a);
+        }
+        if (n < A.nk) {
+            const size_t off = ((size_t)w * A.nk + n) * C + col;
+            const float2 x = *reinterpret_cast<const float2 *>(A.k + off), gx = *reinterpret_cast<const float2 *>(A.g_k + off);
+            a = fmaf(x.x, gx.y, a);
+            a = fmaf(-x.y, gx.x, a);
+        }
+    }
+    (A.aslices == 1 ? A.g_angles : A.part + (size_t)slice * per)[e] = a;
+}
+
+// g_angles = the slices' partials added in slice order
+__global__ __launch_bounds__(256) void k_attn_angle_sum(AttnArgs A)
+{
+    const int per = A.heads * A.arows * (A.d >> 1), e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= per) return;
+    float a = A.part[e];
+    for (int s = 1; s < A.aslices; ++s) a += A.part[(size_t)s * per + e];
+    A.g_angles[e] = a;
 }
 
 int attn_geometry_check(const gsasr_window_attn *a)
@@ -436,6 +581,47 @@ AttnArgs attn_args(const gsasr_window_attn *a)
     A.wslots = attn_wslots(a);
     A.vec = a->nk % 4 == 0 && ((uintptr_t)a->index & 15) == 0;
     A.scale = a->scale;
+    A.angles = nullptr; A.cossin = nullptr; A.g_angles = nullptr; A.arows = 0; A.achunk = 0; A.aslices = 0;
+    return A;
+}
+
+constexpr int ATT_ANGLE_CHUNK = 8;      // windows a thread of k_attn_angle_grad adds, at least
+constexpr int ATT_ANGLE_SLICES = 64;    // slices (partials per angle), at most
+
+int attn_rope_geometry_check(const gsasr_window_attn_rope *a)
+{
+    if (!a) return fail(GSASR_ERR_ARG, "null rotary window-attention descriptor");
+    if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
+    if (a->nq < 1 || a->nq > ATT_MAX_N || a->nk < 1 || a->nk > ATT_MAX_N) return fail(GSASR_ERR_ARG, "need 1 <= nq, nk <= 256");
+    if (a->head_dim < 2 || a->head_dim > ATT_MAX_D || a->head_dim % 2) return fail(GSASR_ERR_ARG, "need an even head_dim, 2 <= head_dim <= 32");
+    if (a->angle_rows < (a->nq > a->nk ? a->nq : a->nk)) return fail(GSASR_ERR_ARG, "angle_rows must be at least max(nq, nk)");
+    if (a->flags) return fail(GSASR_ERR_ARG, "unknown flags (none are defined)");
+    if (!(a->scale == a->scale)) return fail(GSASR_ERR_ARG, "scale is NaN");
+    if ((long long)a->windows * a->heads > 0x7fffffffLL || (long long)a->angle_rows * a->heads * (a->head_dim / 2) > 0x7fffffffLL)
+        return fail(GSASR_ERR_ARG, "windows * heads or heads * angle_rows * head_dim / 2 exceeds 2^31 - 1");
+    return GSASR_OK;
+}
+
+inline int attn_angle_chunk(int windows)
+{
+    const int even = (windows + ATT_ANGLE_SLICES - 1) / ATT_ANGLE_SLICES;
+    return even > ATT_ANGLE_CHUNK ? even : ATT_ANGLE_CHUNK;
+}
+inline int attn_angle_slices(int windows) { return (windows + attn_angle_chunk(windows) - 1) / attn_angle_chunk(windows); }
+
+inline bool attn_misaligned(const void *p) { return ((uintptr_t)p & 7) != 0; }
+
+AttnArgs attn_rope_args(const gsasr_window_attn_rope *a)
+{
+    AttnArgs A;
+    A.q = a->q; A.k = a->k; A.v = a->v; A.table = nullptr; A.index = nullptr; A.out = a->out; A.o = a->out; A.stats = a->stats;
+    A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.g_table = nullptr; A.part = (float *)a->scratch;
+    A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.rows = 0;
+    A.wslots = a->windows;      // (no table to bin: one workgroup of k_attn_bwd_q per window and head)
+    A.vec = false;
+    A.scale = a->scale;
+    A.angles = a->angles; A.cossin = a->cossin; A.g_angles = a->g_angles; A.arows = a->angle_rows;
+    A.achunk = attn_angle_chunk(a->windows); A.aslices = attn_angle_slices(a->windows);
     return A;
 }
 
@@ -520,6 +706,69 @@ int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream)
         const unsigned grid = (unsigned)(a->windows * a->heads);
         const int waves = attn_waves(a->nk);
         if (int rc = tlds ? attn_launch(k_attn_bwd_kv<true>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_kv<false>, grid, waves, lds, st, A)) return rc;
+    }
+    return GSASR_OK;
+}
+
+size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_rope *a)
+{
+    if (attn_rope_geometry_check(a)) return 0;
+    // the slices' partial angle gradients of the backward; never 0 for a valid descriptor
+    const int slices = attn_angle_slices(a->windows);
+    const bool part = a->g_angles && slices > 1;
+    return 256 + (part ? align_up((size_t)slices * a->heads * a->angle_rows * (a->head_dim / 2) * sizeof(float), 256) : 0);
+}
+
+int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *a, void *stream)
+{
+    if (int rc = attn_rope_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->angles || !a->out || !a->cossin) return fail(GSASR_ERR_ARG, "null q, k, v, angles, out or cossin pointer");
+    if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin)) return fail(GSASR_ERR_ARG, "q, k and cossin must be 8-byte aligned");
+    const AttnArgs A = attn_rope_args(a);
+    const int nt = (a->nk + 15) / 16;
+    const bool stats = a->stats != nullptr;
+    const size_t lds = (size_t)2 * nt * 16 * ATT_LD * sizeof(float);
+    const unsigned grid = (unsigned)(a->windows * a->heads);
+    const int waves = attn_waves(a->nq);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_attn_cossin, dim3((unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+#define ATT_FWD(T) (stats ? attn_launch(k_attn_fwd<T, true, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, false, false, true>, grid, waves, lds, st, A))
+    if (nt <= 3) return ATT_FWD(3);
+    if (nt <= 9) return ATT_FWD(9);
+    return ATT_FWD(16);
+#undef ATT_FWD
+}
+
+int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *a, void *stream)
+{
+    if (int rc = attn_rope_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->out || !a->stats || !a->grad_out || !a->cossin)
+        return fail(GSASR_ERR_ARG, "null q, k, v, out, stats, grad_out or cossin pointer");
+    if (a->g_angles && (!a->g_q || !a->g_k)) return fail(GSASR_ERR_ARG, "g_angles needs g_q and g_k (it is formed from them)");
+    if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin) || attn_misaligned(a->g_q) || attn_misaligned(a->g_k))
+        return fail(GSASR_ERR_ARG, "q, k, cossin, g_q and g_k must be 8-byte aligned");
+    const AttnArgs A = attn_rope_args(a);
+    if (a->g_angles && A.aslices > 1 && !a->scratch)
+        return fail(GSASR_ERR_ARG, "null scratch pointer (the angle gradient needs gsasr_window_attn_rope_scratch_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    if (a->g_q) {
+        const size_t lds = (size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD * sizeof(float);
+        if (int rc = attn_launch(k_attn_bwd_q<0, false, true>, (unsigned)(a->windows * a->heads), attn_waves(a->nq), lds, st, A)) return rc;
+    }
+    if (a->g_k || a->g_v) {
+        const int nqp = (a->nq + 15) / 16 * 16;
+        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp) * sizeof(float);
+        if (int rc = attn_launch(k_attn_bwd_kv<false, true>, (unsigned)(a->windows * a->heads), attn_waves(a->nk), lds, st, A)) return rc;
+    }
+    if (a->g_angles) {
+        const unsigned blocks = (unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256);
+        hipLaunchKernelGGL(k_attn_angle_grad, dim3(blocks, (unsigned)A.aslices), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (A.aslices > 1) {
+            hipLaunchKernelGGL(k_attn_angle_sum, dim3(blocks), dim3(256), 0, st, A);
+            HIP_TRY(hipGetLastError());
+        }
     }
     return GSASR_OK;
 }

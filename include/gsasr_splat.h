@@ -679,6 +679,49 @@ GSASR_API size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *attn);
 GSASR_API int gsasr_window_attn_forward(const gsasr_window_attn *attn, void *stream);
 GSASR_API int gsasr_window_attn_backward(const gsasr_window_attn *attn, void *stream);
 
+/* Window attention with a 2-D rotary embedding: the core of every layer of the Fea2GS_ROPE_AMP decoder (WindowCrossAttn and
+ * GSSelfAttn of utils/fea2gsropeamp.py: rotation of q and k by learned angles, then bias-free scaled-dot-product attention),
+ * fused like the biased one above -- same layouts, same kernels' geometry, no table and no index.  For window w, head h, with
+ * x[w, n, h] the head's columns of token n read as head_dim / 2 complex numbers (column 2 j + i column 2 j + 1):
+ *
+ *   R(x)[w, n, h, j] = x[w, n, h, j] (cos t + i sin t),  t = angles[h, n, j]       (query i uses row i, key j row j of angles)
+ *   S = scale R(q)[w, :, h] R(k)[w, :, h]^T (rotate, then scale),  P = softmax over the keys of S,  out[w, :, h] = P v[w, :, h]
+ *   stats[w, h, i] = log sum_j exp(S[i, j]);   cossin[h, n, j] = (cos t, sin t), the accurate sincosf, written by the forward
+ *   backward, given grad_out: delta, dP, dS as above;  g_v = P^T grad_out,  g_q = conj-rotation of scale dS R(k),
+ *   g_k = conj-rotation of scale dS^T R(q)   (a rotation is unitary: the gradient of the un-rotated input is the gradient of the
+ *   rotated one times cos t - i sin t),
+ *   g_angles[h, n, j] = sum_w Im(conj(q) g_q)[w, n, h, j] [n < nq] + sum_w Im(conj(k) g_k)[w, n, h, j] [n < nk],
+ *   Im(conj(x) g) = x_re g_im - x_im g_re, of the UN-rotated inputs and their gradients.
+ *
+ * fp32 throughout.  out, g_q, g_k, g_v and g_angles are each written once and two calls give the same bits: g_angles is added
+ * in a fixed order (window by window inside a slice of windows, then slice by slice), without atomics; its rows past
+ * max(nq, nk) are exactly 0.  Nothing is read on the host and everything is enqueued on `stream`.
+ *
+ *   q, k, v, out, stats, grad_out, g_q, g_k, g_v   as in gsasr_window_attn; q, k, g_q, g_k and cossin 8-byte aligned
+ *   angles, g_angles   [heads, angle_rows, head_dim / 2], angle_rows >= max(nq, nk)
+ *   cossin             float [heads, angle_rows, head_dim / 2, 2]: written by the forward, read by the backward (like stats)
+ *   g_q, g_k, g_v, g_angles   each NULL = not wanted, but g_angles needs g_q AND g_k: it is formed from them
+ *   scratch            gsasr_window_attn_rope_scratch_bytes(descriptor) bytes, 256-byte aligned, for the backward when g_angles
+ *                      is set (set it before asking): the slices' partial sums, every word written before it is read
+ * GSASR_ERR_ARG before anything is enqueued: windows or heads below 1, nq or nk outside 1..256, head_dim odd or outside 2..32,
+ * angle_rows < max(nq, nk), flags other than 0, a NaN scale, a null or misaligned pointer among those the call needs, g_angles
+ * without g_q or g_k. */
+typedef struct gsasr_window_attn_rope {
+    int windows, heads, nq, nk, head_dim, angle_rows;
+    float scale;
+    unsigned flags;       /* 0 (none defined) */
+    const float *q, *k, *v, *angles;
+    float *out;           /* written by the forward, read by the backward */
+    float *stats;
+    const float *grad_out;
+    float *g_q, *g_k, *g_v, *g_angles;
+    float *cossin;
+    void *scratch;
+} gsasr_window_attn_rope;
+GSASR_API size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_rope *attn);   /* 0 on bad arguments (only g_angles among the pointers is looked at) */
+GSASR_API int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *attn, void *stream);
+GSASR_API int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *attn, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate

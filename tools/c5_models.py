@@ -131,17 +131,56 @@ class _BiasedWindowAttention(nn.Module):
         return self.o(out.transpose(1, 2).reshape(b, nq, c))
 
 
+class _RotaryWindowAttention(nn.Module):
+    """multi-head attention of the window's n x n query tokens over its n x n key tokens, q and k rotated by a 2-D rotary
+    embedding with learned frequencies (the RoPE decoder's modules, and their attribute names: qhead, khead, vhead, proj,
+    num_heads, rope_freqs [2, heads, d/2], rope_t_x / rope_t_y on the token grid), then bias-free attention"""
+
+    def __init__(self, c, heads, n, attention="torch", theta=10.0):
+        super().__init__()
+        self.num_heads, self.attention = heads, attention
+        self.qhead, self.khead, self.vhead, self.proj = nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c)
+        d = c // heads
+        assert d % 4 == 0, "the rotary embedding splits a head into quarters (x / y, re / im)"
+        t = torch.arange(n * n, dtype=torch.float32)
+        self.register_buffer("rope_t_x", t % n)
+        self.register_buffer("rope_t_y", torch.div(t, n, rounding_mode="floor"))
+        mag = 1.0 / theta ** (torch.arange(0, d, 4).float() / d)               # [d/4]
+        turn = torch.rand(heads, 1) * 2 * torch.pi                             # each head's axes turned by a random angle
+        fx = torch.cat([mag * torch.cos(turn), mag * torch.cos(torch.pi / 2 + turn)], -1)
+        fy = torch.cat([mag * torch.sin(turn), mag * torch.sin(torch.pi / 2 + turn)], -1)
+        self.rope_freqs = nn.Parameter(torch.stack([fx, fy]))                  # [2, heads, d/2]
+
+    def forward(self, xq, xk):
+        from gsasr_amd.attention import rope_angles
+        b, nq, c = xq.shape
+        h = self.num_heads
+        angles = rope_angles(self.rope_freqs, self.rope_t_x, self.rope_t_y)    # [heads, n*n, d/2], fp32
+        if self.attention == "hip":
+            from gsasr_amd.attention import window_attention_rope
+            return self.proj(window_attention_rope(self.qhead(xq), self.khead(xk), self.vhead(xk), angles))
+        q = self.qhead(xq).view(b, nq, h, c // h).transpose(1, 2)
+        k = self.khead(xk).view(b, -1, h, c // h).transpose(1, 2)
+        v = self.vhead(xk).view(b, -1, h, c // h).transpose(1, 2)
+        cis = torch.polar(torch.ones_like(angles), angles)                     # the reference's rotation: complex pairs times cis
+        wide = lambda x: x if x.dtype == torch.float64 else x.float()        # noqa: E731 (fp32 temporaries under AMP, as the reference)
+        q, k = (torch.view_as_real(torch.view_as_complex(wide(x).reshape(*x.shape[:-1], -1, 2)) * cis[:, :x.shape[2]]).flatten(3).type_as(x)
+                for x in (q, k))
+        out = F.scaled_dot_product_attention(q, k, v)
+        return self.proj(out.transpose(1, 2).reshape(b, nq, c))
+
+
 class _SeedLayer(nn.Module):
     """one decoder layer: seeds attend to the scale embedding, FFN, window attention (to image features, or among the seeds),
     FFN -- pre-norm residuals.  `cross`: keys are the window's image features; else the seeds themselves."""
 
-    def __init__(self, c, heads, win, shift, cross, attention="torch", scale_attention="mha"):
+    def __init__(self, c, heads, win, shift, cross, attention="torch", scale_attention="mha", position="bias"):
         super().__init__()
         self.win, self.shift, self.cross, self.scale_attention = win, shift, cross, scale_attention
         self.n1, self.n2, self.n3, self.n4 = (nn.LayerNorm(c) for _ in range(4))
         self.to_scale = nn.MultiheadAttention(c, heads, batch_first=True)
         self.f1, self.f2 = _FFN(c), _FFN(c)
-        self.attn = _BiasedWindowAttention(c, heads, win, win, attention)
+        self.attn = _BiasedWindowAttention(c, heads, win, win, attention) if position == "bias" else _RotaryWindowAttention(c, heads, win, attention)
 
     def forward(self, x, pos, feat, scale_emb, grid):
         b, m, n = grid                                               # images, windows per column / row
@@ -175,10 +214,10 @@ class _SeedLayer(nn.Module):
 
 
 class _SeedBlock(nn.Module):
-    def __init__(self, c, heads, win, layers, cross, attention="torch", scale_attention="mha"):
+    def __init__(self, c, heads, win, layers, cross, attention="torch", scale_attention="mha", position="bias"):
         super().__init__()
         self.norm = nn.LayerNorm(c)
-        self.layers = nn.ModuleList([_SeedLayer(c, heads, win, 0 if i % 2 == 0 else win // 2, cross, attention, scale_attention)
+        self.layers = nn.ModuleList([_SeedLayer(c, heads, win, 0 if i % 2 == 0 else win // 2, cross, attention, scale_attention, position)
                                      for i in range(layers)])
         self.mlp = _FFN(c)
 
@@ -194,15 +233,18 @@ class Fea2GSDecoder(nn.Module):
     docstring), one seed per LR pixel, 16 Gaussians per seed after the two pixel shuffles, raster order of the 4h x 4w grid.
     `attention`: "torch" (F.scaled_dot_product_attention with the bias as mask, the default) | "hip" (gsasr_amd.window_attention);
     `scale_attention`: "mha" (nn.MultiheadAttention over the repeated scale embedding, the default) | "constant"
-    (gsasr_amd.attention.constant_key_attention).  Same parameters and state dict in every mode."""
+    (gsasr_amd.attention.constant_key_attention).  Same parameters and state dict in every mode.
+    `position`: "bias" (the learned relative-position bias of utils/fea2gs.py, the default) | "rope" (the RoPE decoder of
+    utils/fea2gsropeamp.py: every layer's window attention rotates q and k by a 2-D rotary embedding with learned frequencies
+    and has no bias; `attention` "torch" = that rotation + F.scaled_dot_product_attention, "hip" = gsasr_amd.window_attention_rope)."""
     UP = 4
 
     def __init__(self, inchannel=64, channel=180, heads=6, window=12, cross_layers=2, self_blocks=6, self_layers=6,
-                 attention="torch", scale_attention="mha"):
+                 attention="torch", scale_attention="mha", position="bias"):
         super().__init__()
-        if attention not in ("torch", "hip") or scale_attention not in ("mha", "constant"):
-            raise ValueError('attention must be "torch" or "hip", scale_attention "mha" or "constant"')
-        mode = (attention, scale_attention)
+        if attention not in ("torch", "hip") or scale_attention not in ("mha", "constant") or position not in ("bias", "rope"):
+            raise ValueError('attention must be "torch" or "hip", scale_attention "mha" or "constant", position "bias" or "rope"')
+        mode = (attention, scale_attention, position)
         self.c, self.win = channel, window
         self.seed = nn.Parameter(torch.randn(window * window, channel))
         self.pos = nn.Parameter(torch.randn(window * window, channel))

@@ -1,7 +1,10 @@
 """Times gsasr_amd.window_attention against the two forms a user can write in torch, and the Fea2GS-shaped decoder of
-tools/c5_models.py in its three modes (profiles/window_attention.txt).
+tools/c5_models.py in its three modes (profiles/window_attention.txt); likewise gsasr_amd.window_attention_rope
+against the RoPE decoder's own expression (the rotation of apply_rotary_emb, then F.scaled_dot_product_attention) and against
+the explicit torch expression, in fp32 and under bf16 autocast, and the decoder with position="rope"
+(profiles/window_attention_rope.txt).
 
-    python tools/window_attention_bench.py [--reps 9] [--iters 20] [--skip-decoder] [--only-hip]
+    python tools/window_attention_bench.py [--reps 9] [--iters 20] [--skip-decoder] [--skip-op] [--only-hip] [--skip-bias] [--skip-rope]
 
 Protocol: one process; every variant warmed up first; then `reps` rounds in which the variants take turns (interleaved, so a
 drift of the clock hits all of them), each turn `iters` back-to-back calls between two events on the current stream; the
@@ -18,9 +21,10 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
-from gsasr_amd.attention import window_attention, window_attention_torch      # noqa: E402
+from gsasr_amd.attention import window_attention, window_attention_rope, window_attention_rope_torch, window_attention_torch      # noqa: E402
 
 OP_SHAPES = [(256, 144, 6, 30), (64, 256, 6, 32)]      # (W, n, H, d): config 5's batch (16 samples x 16 windows); the 16 x 16 configs
+ROPE_SHAPES = [(256, 144, 6, 32), (64, 256, 6, 32)]    # the RoPE decoder's: 192 channels; EDSR / RDN / SwinIR 144 tokens, HATL 256
 
 
 def sdpa_form(q, k, v, table, index, scale=None):
@@ -82,10 +86,66 @@ def op_level(args, dev):
                 print(json.dumps(dict(level="op", shape=dict(W=W, n=n, H=H, d=d), what=what, form=name, **{k: round(x, 4) for k, x in r.items()})), flush=True)
 
 
-def decoder_level(args, dev):
+def rope_reference_form(q, k, v, angles, scale=None):
+    """the RoPE modules' own expression (utils/fea2gsropeamp.py): head split, complex pairs times cis through fp32 temporaries,
+    `type_as`, bias-free F.scaled_dot_product_attention, head merge"""
+    W, nq, C = q.shape
+    H = angles.shape[0]
+    d = C // H
+    qh, kh, vh = (t.view(W, -1, H, d).permute(0, 2, 1, 3) for t in (q, k, v))
+    cis = torch.polar(torch.ones_like(angles), angles)
+    qh, kh = (torch.view_as_real(torch.view_as_complex(x.float().reshape(*x.shape[:-1], -1, 2)) * cis[:, :x.shape[2]]).flatten(3).type_as(x)
+              for x in (qh, kh))
+    return F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(W, nq, C)
+
+
+def rope_op_level(args, dev):
+    for (W, n, H, d) in ROPE_SHAPES:
+        g = torch.Generator().manual_seed(0)
+        q, k, v, wgt = (torch.randn(W, n, H * d, generator=g).to(dev) for _ in range(4))
+        side = int(round(n ** 0.5))
+        t = torch.arange(n, dtype=torch.float32)
+        freqs = torch.rand(2, H, d // 2, generator=g)                  # (magnitudes up to 1: angles up to 2 (side - 1) rad)
+        angles = ((t % side)[None, :, None] * freqs[0][:, None, :] + torch.div(t, side, rounding_mode="floor")[None, :, None] * freqs[1][:, None, :]).to(dev)
+        forms = {"hip": window_attention_rope}
+        if not args.only_hip:
+            forms.update(torch_explicit=window_attention_rope_torch, torch_reference=rope_reference_form)
+            # the biased op on the same q, k, v (a table of the window's relative offsets; its 4th leaf is the table): what the rotation costs
+            table = (0.5 * torch.randn((2 * side - 1) ** 2, H, generator=g)).to(dev)
+            cy, cx = torch.div(t, side, rounding_mode="floor").long(), (t % side).long()
+            index = ((cy[:, None] - cy[None, :] + side - 1) * (2 * side - 1) + cx[:, None] - cx[None, :] + side - 1).to(dev)
+            forms["hip_biased_op"] = lambda a, b, c, ang: window_attention(a, b, c, table if ang is angles else ang, index)
+        for amp in (False, True):
+            cast = (lambda x: x.bfloat16()) if amp else (lambda x: x)
+            qa, ka, va, wa = (cast(x) for x in (q, k, v, wgt))
+            leaves = [x.clone().requires_grad_(True) for x in (qa, ka, va)] + [angles.clone().requires_grad_(True)]
+            if not args.only_hip:
+                bias_leaves = leaves[:3] + [table.clone().requires_grad_(True)]
+
+            def fwd(fn):
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    return fn(qa, ka, va, angles)
+
+            def fwd_bwd(fn):
+                ls = bias_leaves if fn is forms.get("hip_biased_op") else leaves
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    out = fn(*ls)
+                torch.autograd.grad(out, ls, wa.to(out.dtype))
+
+            for what, run in (("forward", fwd), ("forward+backward", fwd_bwd)):
+                res = interleaved({name: (lambda f=fn: run(f)) for name, fn in forms.items()}, args.reps, args.iters)
+                for name, r in res.items():
+                    print(json.dumps(dict(level="op", position="rope", precision="bf16 autocast" if amp else "fp32", shape=dict(W=W, n=n, H=H, d=d), what=what,
+                                          form=name, **{k: round(x, 4) for k, x in r.items()})), flush=True)
+
+
+def decoder_level(args, dev, position="bias"):
     import c5_models
     torch.manual_seed(0)
     modes = {"default": dict(), "attention=hip": dict(attention="hip"), "attention=hip,scale_attention=constant": dict(attention="hip", scale_attention="constant")}
+    if position == "rope":     # 192 channels, full depth; the constant-key form with the torch attention as well
+        modes = {"default": dict(), "scale_attention=constant": dict(scale_attention="constant"), **{k: v for k, v in modes.items() if k != "default"}}
+        modes = {name: dict(kw, position="rope", channel=192) for name, kw in modes.items()}
     nets = {}
     for name, kw in modes.items():
         nets[name] = c5_models.Fea2GSDecoder(**kw).to(dev)
@@ -100,7 +160,7 @@ def decoder_level(args, dev):
 
     res = interleaved({name: (lambda m=net: step(m)) for name, net in nets.items()}, max(3, args.reps // 2), 2, warmup=2)
     for name, r in res.items():
-        print(json.dumps(dict(level="decoder", feat=[16, 64, 48, 48], what="forward+backward", mode=name, **{k: round(x, 3) for k, x in r.items()})), flush=True)
+        print(json.dumps(dict(level="decoder", position=position, feat=[16, 64, 48, 48], what="forward+backward", mode=name, **{k: round(x, 3) for k, x in r.items()})), flush=True)
 
 
 def main():
@@ -108,12 +168,21 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--skip-decoder", action="store_true")
+    ap.add_argument("--skip-op", action="store_true", help="the decoder level alone")
     ap.add_argument("--only-hip", action="store_true")
+    ap.add_argument("--skip-bias", action="store_true", help="leave out the biased op and its decoder")
+    ap.add_argument("--skip-rope", action="store_true", help="leave out the rotary op and its decoder")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    op_level(args, dev)
+    if not args.skip_bias and not args.skip_op:
+        op_level(args, dev)
+    if not args.skip_rope and not args.skip_op:
+        rope_op_level(args, dev)
     if not args.skip_decoder and not args.only_hip:
-        decoder_level(args, dev)
+        if not args.skip_bias:
+            decoder_level(args, dev)
+        if not args.skip_rope:
+            decoder_level(args, dev, "rope")
 
 
 if __name__ == "__main__":
