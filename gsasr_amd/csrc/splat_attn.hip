@@ -23,7 +23,9 @@
 //                  delta = rowsum(dO o O), dq = scale dS K with dS as the A operand in place.  d table: dS is binned with LDS
 //                  float adds into the workgroup's copy of the head's table column; a workgroup walks the windows
 //                  b, b + stride, ... of its head and writes ONE partial column at the end (k_attn_table_sum adds the
-//                  partials in a fixed order).  Tables above ATT_TAB_LDS rows: global float atomics on a zeroed g_table.
+//                  partials in a fixed order).  Tables above ATT_TAB_LDS rows: global atomics in DOUBLE on a zeroed column
+//                  in the scratch, rounded to g_table once by k_attn_table_round (a row's sum has windows x pairs terms
+//                  in no fixed order: in fp32 its error grew with the root of that count, past the fp32 torch sum's).
 //   k_attn_bwd_kv  one workgroup per (window, head) with scale Q, dO, the statistic and delta in LDS; a wave takes 16 KEYS at a
 //                  time and computes S = (scale Q) K^T and dP = dO V^T with the key on the lane: P^T and dS^T are then the A
 //                  operands of dv = P^T dO and dk = dS^T (scale Q) in place.
@@ -279,7 +281,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
     }
 }
 
-// TAB: 0 no table gradient, 1 binned in LDS -> a partial column, 2 global atomics on g_table
+// TAB: 0 no table gradient, 1 binned in LDS -> a partial column, 2 global double atomics on the scratch's [rows, heads]
 // ROPE (TAB 0, no table): K staged rotated, the query row rotated in registers, dq times the conjugate at the store
 template <int TAB, bool TLDS, bool ROPE = false>
 __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
@@ -348,7 +350,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
                     const float p = valid ? att_exp((ROPE ? sc[r] : sc[r] + b[r]) - lse) : 0.f;
                     ds[r] = p * (dp[r] - delta);
                     if (TAB == 1 && valid) atomicAdd(&s_tab[ix[r]], ds[r]);
-                    if (TAB == 2 && valid) atomicAdd(&A.g_table[(size_t)ix[r] * A.heads + h], ds[r]);
+                    if (TAB == 2 && valid) atomicAdd(reinterpret_cast<double *>(A.part) + (size_t)ix[r] * A.heads + h, (double)ds[r]);
                     ix[r] = ix1[r];
                     ix1[r] = ixn[r];
                 }
@@ -399,6 +401,13 @@ __global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgs A)
         for (int u = 1; u < 8; ++u) a += s_sum[u][threadIdx.x];
         A.g_table[(size_t)t * A.heads + h] = a;
     }
+}
+
+// g_table = the double sums of the TAB == 2 walk, rounded once
+__global__ __launch_bounds__(256) void k_attn_table_round(AttnArgs A)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < A.rows * A.heads) A.g_table[e] = (float)reinterpret_cast<const double *>(A.part)[e];
 }
 
 // ROPE: scale Q staged rotated, the key row rotated in registers, dk times the conjugate at the store
@@ -650,9 +659,11 @@ extern "C" {
 size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *a)
 {
     if (attn_geometry_check(a)) return 0;
-    // the partial table columns of the backward (one per window slot and head); never 0 for a valid descriptor
-    const bool part = a->g_table && a->table_rows <= ATT_TAB_LDS;
-    return 256 + (part ? align_up((size_t)attn_wslots(a) * a->heads * a->table_rows * sizeof(float), 256) : 0);
+    // the partial table columns of the backward (one per window slot and head), or above ATT_TAB_LDS rows the table's sums
+    // in double; never 0 for a valid descriptor
+    if (!a->g_table) return 256;
+    if (a->table_rows > ATT_TAB_LDS) return 256 + align_up((size_t)a->table_rows * a->heads * sizeof(double), 256);
+    return 256 + align_up((size_t)attn_wslots(a) * a->heads * a->table_rows * sizeof(float), 256);
 }
 
 int gsasr_window_attn_forward(const gsasr_window_attn *a, void *stream)
@@ -683,20 +694,25 @@ int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream)
     hipStream_t st = (hipStream_t)stream;
     const bool tlds = attn_tlds(a);
     const int tab = !a->g_table ? 0 : tlds ? 1 : 2;
-    if (tab == 1 && !a->scratch) return fail(GSASR_ERR_ARG, "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)");
+    if (tab && !a->scratch) return fail(GSASR_ERR_ARG, "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)");
+    if (tab == 2 && ((uintptr_t)a->scratch & 7)) return fail(GSASR_ERR_ARG, "scratch must be 8-byte aligned");
     if (a->g_q || tab) {
         const size_t lds = ((size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD + (tlds ? a->table_rows : 0) + (tab == 1 ? a->table_rows : 0)) * sizeof(float);
         const unsigned grid = (unsigned)(A.wslots * a->heads);
         const int waves = attn_waves(a->nq);
         int rc;
         if (tab == 2) {
-            HIP_TRY(hipMemsetAsync(a->g_table, 0, (size_t)a->table_rows * a->heads * sizeof(float), st));
+            HIP_TRY(hipMemsetAsync(a->scratch, 0, (size_t)a->table_rows * a->heads * sizeof(double), st));
             rc = attn_launch(k_attn_bwd_q<2, false>, grid, waves, lds, st, A);
         } else if (tab == 1) rc = attn_launch(k_attn_bwd_q<1, true>, grid, waves, lds, st, A);
         else rc = tlds ? attn_launch(k_attn_bwd_q<0, true>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_q<0, false>, grid, waves, lds, st, A);
         if (rc) return rc;
         if (tab == 1) {
             hipLaunchKernelGGL(k_attn_table_sum, dim3((unsigned)((a->table_rows * a->heads + 31) / 32)), dim3(256), 0, st, A);
+            HIP_TRY(hipGetLastError());
+        }
+        if (tab == 2) {
+            hipLaunchKernelGGL(k_attn_table_round, dim3((unsigned)((a->table_rows * a->heads + 255) / 256)), dim3(256), 0, st, A);
             HIP_TRY(hipGetLastError());
         }
     }

@@ -651,7 +651,8 @@ GSASR_API int gsasr_batch_pick(const gsasr_batch *batch, const int *points, int 
  * fp32 throughout: the products run on the exact-fp32 matrix instruction (a k-ordered chain of fmaf), the softmax sees the
  * whole row at once (one maximum, one sum; no online rescaling).  out, g_q, g_k and g_v are written once by the workgroup that
  * owns the (window, head) -- no atomics, two calls give the same bits.  g_table is binned with float adds in LDS whose order is
- * not fixed: its last bits may differ between two calls; a row that no (i, j) uses is exactly 0.  Nothing is read on the host and
+ * not fixed (above 4096 table rows: with global adds in double, rounded once): its last bits may differ between two calls; a
+ * row that no (i, j) uses is exactly 0.  Nothing is read on the host and
  * everything is enqueued on `stream`: the calls can be captured into a graph.
  *
  *   q, out, grad_out, g_q   [windows, nq, heads * head_dim], contiguous;  k, v, g_k, g_v   [windows, nk, heads * head_dim]
@@ -661,6 +662,7 @@ GSASR_API int gsasr_batch_pick(const gsasr_batch *batch, const int *points, int 
  *   g_q, g_k, g_v, g_table  each NULL = not wanted (its work is skipped where that saves a kernel)
  *   scratch                 gsasr_window_attn_scratch_bytes(descriptor) bytes, 256-byte aligned, for the backward when g_table is set
  *                           (set g_table before asking): per-workgroup partial tables, every word written before it is read
+ *                           (above 4096 table rows: the table's sums in double, zeroed by the call)
  * GSASR_ERR_ARG before anything is enqueued: windows, heads or table_rows below 1, nq or nk outside 1..256, head_dim outside
  * 1..32, flags other than 0, a NaN scale, a null pointer among those the call needs. */
 typedef struct gsasr_window_attn {
