@@ -13,6 +13,7 @@ ChrisDud0257/GSASR, behind the reference's own autograd/operator surface).
     from gsasr_amd import make_batch, draw_batch                                   # the dataset's crop / LR / augment / pad, one call on uint8 images
     from gsasr_amd import window_attention, use_hip_attention                      # the Fea2GS decoder's window attention, fused
     from gsasr_amd import window_attention_rope                                    # ... of the RoPE decoder (Fea2GS_ROPE_AMP)
+    from gsasr_amd import window_attention_bf16_torch, window_attention_rope_bf16_torch   # the contracts of their compute="bf16" mode
 
 The compute lives in gsasr_amd/csrc/splat_{plan,forward,backward,backward_home,step,sampled,shard,ssim,metrics,resize,data,attn,api}.hip (hand-written HIP
 for gfx950; csrc/gsasr_splat.hip is the same code as one translation unit for the micro-benchmark) behind the C ABI of
@@ -34,7 +35,8 @@ def __getattr__(name):      # (lazily: importing the package alone does not impo
     if name in ("make_batch", "draw_batch"):
         from . import data
         return getattr(data, name)
-    if name in ("window_attention", "window_attention_rope", "use_hip_attention"):
+    if name in ("window_attention", "window_attention_rope", "use_hip_attention", "window_attention_bf16_torch",
+                "window_attention_rope_bf16_torch"):
         from . import attention
         return getattr(attention, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

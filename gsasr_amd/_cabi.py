@@ -115,6 +115,16 @@ class WindowAttnRope(ctypes.Structure):
                 ("cossin", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
 
 
+class WindowAttnBf16(ctypes.Structure):
+    """struct gsasr_window_attn_bf16: gsasr_window_attn with bf16 activations (same fields, same layout)"""
+    _fields_ = list(WindowAttn._fields_)
+
+
+class WindowAttnRopeBf16(ctypes.Structure):
+    """struct gsasr_window_attn_rope_bf16: gsasr_window_attn_rope with bf16 activations (same fields, same layout)"""
+    _fields_ = list(WindowAttnRope._fields_)
+
+
 RESIZE_NO_ANTIALIAS, RESIZE_ACCUMULATE, RESIZE_SHARED_SCALE = 1, 2, 4     # GSASR_RESIZE_*
 BATCH_HFLIP, BATCH_VFLIP, BATCH_TRANSPOSE = 1, 2, 4     # GSASR_BATCH_* (aug bits)
 BATCH_BGR, BATCH_NO_ANTIALIAS = 1, 2                    # GSASR_BATCH_* (flags)
@@ -126,7 +136,7 @@ LOSS_NORMS = {"mean": 0, "sum": 1}                      # GSASR_LOSS_MEAN / _SUM
 _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(Dims)
 _vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
 _rzp, _btp, _wap = ctypes.POINTER(Resize), ctypes.POINTER(Batch), ctypes.POINTER(WindowAttn)
-_wrp = ctypes.POINTER(WindowAttnRope)
+_wrp, _wabp, _wrbp = ctypes.POINTER(WindowAttnRope), ctypes.POINTER(WindowAttnBf16), ctypes.POINTER(WindowAttnRopeBf16)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -210,6 +220,13 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_window_attn_rope_scratch_bytes": (_sz, [_wrp]),
     "gsasr_window_attn_rope_forward": (_i, [_wrp, _vp]),
     "gsasr_window_attn_rope_backward": (_i, [_wrp, _vp]),
+    # ... both with bf16 activations (gsasr_window_attn_bf16, gsasr_window_attn_rope_bf16)
+    "gsasr_window_attn_bf16_scratch_bytes": (_sz, [_wabp]),
+    "gsasr_window_attn_bf16_forward": (_i, [_wabp, _vp]),
+    "gsasr_window_attn_bf16_backward": (_i, [_wabp, _vp]),
+    "gsasr_window_attn_rope_bf16_scratch_bytes": (_sz, [_wrbp]),
+    "gsasr_window_attn_rope_bf16_forward": (_i, [_wrbp, _vp]),
+    "gsasr_window_attn_rope_bf16_backward": (_i, [_wrbp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1227,20 +1244,36 @@ def ssim_loss(img: torch.Tensor, target: torch.Tensor, sizes=None, weight: float
 
 
 # ---- the decoder's window attention (include/gsasr_splat.h: gsasr_window_attn) ----------------------------------
-def make_window_attn(windows: int, heads: int, nq: int, nk: int, head_dim: int, table_rows: int, scale: float) -> WindowAttn:
-    """a gsasr_window_attn descriptor without pointers"""
-    d = WindowAttn(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(table_rows))
+def make_window_attn(windows: int, heads: int, nq: int, nk: int, head_dim: int, table_rows: int, scale: float, bf16: bool = False):
+    """a gsasr_window_attn (`bf16`: gsasr_window_attn_bf16) descriptor without pointers"""
+    d = (WindowAttnBf16 if bf16 else WindowAttn)(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(table_rows))
     d.scale, d.flags = float(scale), 0
     return d
 
 
-def _window_attn(q, k, v, table, index, scale: float) -> WindowAttn:
-    for t, name in ((q, "q"), (k, "k"), (v, "v"), (table, "bias_table")):
-        _chk(t, name)
+def _chk_act(t: torch.Tensor, name: str, bf16: bool) -> int:
+    """`_chk` of an activation: fp32, or bf16 for the bf16 entry points"""
+    if not bf16:
+        return _chk(t, name)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.bfloat16):
+        raise RuntimeError(f"{name} must be a contiguous bfloat16 CUDA tensor")
+    return t.data_ptr()
+
+
+def _attn_fn(stem: str, bf16: bool, what: str) -> str:
+    return f"{stem}_bf16_{what}" if bf16 else f"{stem}_{what}"
+
+
+def _window_attn(q, k, v, table, index, scale: float):
+    """the descriptor of the call; bf16 activations (`q`'s dtype) select gsasr_window_attn_bf16"""
+    bf16 = q.dtype == torch.bfloat16
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _chk_act(t, name, bf16)
+    _chk(table, "bias_table")
     if index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous():
         raise RuntimeError("bias_index must be a contiguous int32 CUDA tensor")
     heads = int(table.shape[1])
-    d = make_window_attn(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, table.shape[0], scale)
+    d = make_window_attn(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, table.shape[0], scale, bf16)
     d.q, d.k, d.v, d.table, d.index = q.data_ptr(), k.data_ptr(), v.data_ptr(), table.data_ptr(), index.data_ptr()
     return d
 
@@ -1248,22 +1281,26 @@ def _window_attn(q, k, v, table, index, scale: float) -> WindowAttn:
 def window_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table: torch.Tensor, index: torch.Tensor, scale: float,
                         want_stats: bool = True):
     """gsasr_window_attn_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `table` `[T,H]` fp32 contiguous, `index` int32
-    `[nq,nk]` (validated by the caller) -> (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None)"""
+    `[nq,nk]` (validated by the caller) -> (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None).  bf16 `q`, `k`, `v`:
+    gsasr_window_attn_bf16_forward, `out` bf16"""
     d = _window_attn(q, k, v, table, index, scale)
+    fn = _attn_fn("gsasr_window_attn", q.dtype == torch.bfloat16, "forward")
     dev = q.device
     with _on(dev):
         out = torch.empty_like(q)
         stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
         d.out, d.stats = out.data_ptr(), None if stats is None else stats.data_ptr()
-        check(lib().gsasr_window_attn_forward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_forward")
+        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
     return out, stats
 
 
 def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_out, need=(True, True, True, True)):
-    """gsasr_window_attn_backward -> (g_q, g_k, g_v, g_table), None where `need` is False"""
+    """gsasr_window_attn_backward (bf16 activations: gsasr_window_attn_bf16_backward) -> (g_q, g_k, g_v, g_table), None where
+    `need` is False"""
     d = _window_attn(q, k, v, table, index, scale)
-    for t, name in ((out, "out"), (stats, "stats"), (grad_out, "grad_out")):
-        _chk(t, name)
+    bf16 = q.dtype == torch.bfloat16
+    fn_bytes, fn = _attn_fn("gsasr_window_attn", bf16, "scratch_bytes"), _attn_fn("gsasr_window_attn", bf16, "backward")
+    _chk_act(out, "out", bf16), _chk(stats, "stats"), _chk_act(grad_out, "grad_out", bf16)
     if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq):
         raise RuntimeError("out / grad_out must have q's shape and stats [W,H,nq]")
     dev = q.device
@@ -1271,43 +1308,48 @@ def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_o
         grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, table), need)]
         d.out, d.stats, d.grad_out = out.data_ptr(), stats.data_ptr(), grad_out.data_ptr()
         d.g_q, d.g_k, d.g_v, d.g_table = [None if g is None else g.data_ptr() for g in grads]
-        n = int(lib().gsasr_window_attn_scratch_bytes(ctypes.byref(d)))
+        n = int(getattr(lib(), fn_bytes)(ctypes.byref(d)))
         if n == 0:
-            check(-1, "gsasr_window_attn_scratch_bytes")
+            check(-1, fn_bytes)
         scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
         d.scratch = scratch.data_ptr()
-        check(lib().gsasr_window_attn_backward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_backward")
+        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
     return tuple(grads)
 
 
 # ---- the decoder's window attention with a rotary embedding (include/gsasr_splat.h: gsasr_window_attn_rope) -----
-def make_window_attn_rope(windows: int, heads: int, nq: int, nk: int, head_dim: int, angle_rows: int, scale: float) -> WindowAttnRope:
-    """a gsasr_window_attn_rope descriptor without pointers"""
-    d = WindowAttnRope(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(angle_rows))
+def make_window_attn_rope(windows: int, heads: int, nq: int, nk: int, head_dim: int, angle_rows: int, scale: float, bf16: bool = False):
+    """a gsasr_window_attn_rope (`bf16`: gsasr_window_attn_rope_bf16) descriptor without pointers"""
+    d = (WindowAttnRopeBf16 if bf16 else WindowAttnRope)(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(angle_rows))
     d.scale, d.flags = float(scale), 0
     return d
 
 
-def _window_attn_rope(q, k, v, angles, scale: float) -> WindowAttnRope:
-    for t, name in ((q, "q"), (k, "k"), (v, "v"), (angles, "angles")):
-        _chk(t, name)
+def _window_attn_rope(q, k, v, angles, scale: float):
+    """the descriptor of the call; bf16 activations (`q`'s dtype) select gsasr_window_attn_rope_bf16"""
+    bf16 = q.dtype == torch.bfloat16
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _chk_act(t, name, bf16)
+    _chk(angles, "angles")
     heads = int(angles.shape[0])
-    d = make_window_attn_rope(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, angles.shape[1], scale)
+    d = make_window_attn_rope(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, angles.shape[1], scale, bf16)
     d.q, d.k, d.v, d.angles = q.data_ptr(), k.data_ptr(), v.data_ptr(), angles.data_ptr()
     return d
 
 
 def window_attn_rope_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, angles: torch.Tensor, scale: float, want_stats: bool = True):
     """gsasr_window_attn_rope_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `angles` `[H,N,d/2]` fp32 contiguous ->
-    (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None, the (cos, sin) table `[H,N,d/2,2]` the backward reads)"""
+    (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None, the (cos, sin) table `[H,N,d/2,2]` the backward reads).  bf16
+    `q`, `k`, `v`: gsasr_window_attn_rope_bf16_forward, `out` bf16"""
     d = _window_attn_rope(q, k, v, angles, scale)
+    fn = _attn_fn("gsasr_window_attn_rope", q.dtype == torch.bfloat16, "forward")
     dev = q.device
     with _on(dev):
         out = torch.empty_like(q)
         stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
         cossin = torch.empty(*angles.shape, 2, dtype=torch.float32, device=dev)
         d.out, d.stats, d.cossin = out.data_ptr(), None if stats is None else stats.data_ptr(), cossin.data_ptr()
-        check(lib().gsasr_window_attn_rope_forward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_rope_forward")
+        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
     return out, stats, cossin
 
 
@@ -1315,8 +1357,9 @@ def window_attn_rope_backward(q, k, v, angles, scale: float, out, stats, cossin,
     """gsasr_window_attn_rope_backward -> (g_q, g_k, g_v, g_angles), None where `need` is False (the angle gradient is formed
     from g_q and g_k: both are computed for it, and dropped here when not needed themselves)"""
     d = _window_attn_rope(q, k, v, angles, scale)
-    for t, name in ((out, "out"), (stats, "stats"), (cossin, "cossin"), (grad_out, "grad_out")):
-        _chk(t, name)
+    bf16 = q.dtype == torch.bfloat16
+    fn_bytes, fn = _attn_fn("gsasr_window_attn_rope", bf16, "scratch_bytes"), _attn_fn("gsasr_window_attn_rope", bf16, "backward")
+    _chk_act(out, "out", bf16), _chk(stats, "stats"), _chk(cossin, "cossin"), _chk_act(grad_out, "grad_out", bf16)
     if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq) or \
             tuple(cossin.shape) != (*angles.shape, 2):
         raise RuntimeError("out / grad_out must have q's shape, stats [W,H,nq] and cossin angles' shape + [2]")
@@ -1326,12 +1369,12 @@ def window_attn_rope_backward(q, k, v, angles, scale: float, out, stats, cossin,
         grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, angles), make)]
         d.out, d.stats, d.cossin, d.grad_out = out.data_ptr(), stats.data_ptr(), cossin.data_ptr(), grad_out.data_ptr()
         d.g_q, d.g_k, d.g_v, d.g_angles = [None if g is None else g.data_ptr() for g in grads]
-        n = int(lib().gsasr_window_attn_rope_scratch_bytes(ctypes.byref(d)))
+        n = int(getattr(lib(), fn_bytes)(ctypes.byref(d)))
         if n == 0:
-            check(-1, "gsasr_window_attn_rope_scratch_bytes")
+            check(-1, fn_bytes)
         scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
         d.scratch = scratch.data_ptr()
-        check(lib().gsasr_window_attn_rope_backward(ctypes.byref(d), _stream(dev)), "gsasr_window_attn_rope_backward")
+        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
     return tuple(g if n else None for g, n in zip(grads, need))
 
 

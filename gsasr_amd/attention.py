@@ -3,7 +3,8 @@ layers in every shipped configuration), fused:
 
     window_attention(q, k, v, bias_table, bias_index, scale=None)      # == window_attention_torch, one HIP call
     window_attention_rope(q, k, v, angles, scale=None)                 # == window_attention_rope_torch: the RoPE decoder's
-    use_hip_attention(model)                                            # switch a model's attention modules to them
+    window_attention(..., compute="bf16") / window_attention_rope(..., compute="bf16")      # bf16 in, bf16 out (below)
+    use_hip_attention(model, compute="fp32")                            # switch a model's attention modules to them
     constant_key_attention(mha, row)                                    # the layers' attention to the scale embedding, closed form
 
 `window_attention_rope` is the attention of `Fea2GS_ROPE_AMP` (utils/fea2gsropeamp.py, the AMP and UltraPerformance models): q and
@@ -11,8 +12,13 @@ k rotated by a 2-D rotary embedding with learned angles (`rope_angles`), then bi
 
 CUDA tensors: gsasr_window_attn_forward / _backward and gsasr_window_attn_rope_forward / _backward (hand-written HIP,
 csrc/splat_attn.hip) as one autograd node on the current stream, or an error -- no torch fallback.  CPU tensors: the torch
-expressions `window_attention_torch` / `window_attention_rope_torch` below, which are also the contracts.  include/gsasr_splat.h has the formulas.  fp32 only: under autocast the inputs are cast to fp32 at the node's boundary
-(bf16 compute is not implemented).
+expressions `window_attention_torch` / `window_attention_rope_torch` below, which are also the contracts.  include/gsasr_splat.h has the formulas.
+
+`compute="fp32"` (the default): under autocast the inputs are cast to fp32 at the node's boundary and the result is fp32.
+`compute="bf16"`: what the decoder's Linears produce under `torch.autocast(dtype=bfloat16)` goes in as it is -- q, k, v are bf16 in
+memory (cast if they are not), the table / angles fp32, the result bf16: gsasr_window_attn_bf16_* / gsasr_window_attn_rope_bf16_*,
+whose forward runs on the bf16 matrix instruction with fp32 scores and an fp32 softmax (include/gsasr_splat.h has the contract;
+`window_attention_bf16_torch` / `window_attention_rope_bf16_torch` are its torch form and the CPU path).
 """
 import types
 import weakref
@@ -20,6 +26,8 @@ import weakref
 import torch
 
 from ._amp import fp32_boundary_bwd, fp32_boundary_fwd
+
+COMPUTE_MODES = ("fp32", "bf16")
 
 MAX_TOKENS = 256        # queries or keys per window
 MAX_HEAD_DIM = 32
@@ -37,6 +45,21 @@ def window_attention_torch(q, k, v, bias_table, bias_index, scale=None):
     vh = v.view(W, nk, H, d).permute(0, 2, 1, 3)
     attn = qh @ kh.transpose(-2, -1) + bias_table[bias_index.long()].permute(2, 0, 1)
     return (torch.softmax(attn, dim=-1) @ vh).transpose(1, 2).reshape(W, nq, C)
+
+
+def _bf16_rounded(*ts):
+    return tuple(t.to(torch.bfloat16).float() for t in ts)
+
+
+def window_attention_bf16_torch(q, k, v, bias_table, bias_index, scale=None):
+    """the contract of `window_attention(..., compute="bf16")`: `window_attention_torch` in fp32 on q, k, v rounded to bf16 (and
+    the table as fp32), the result rounded to bf16"""
+    return window_attention_torch(*_bf16_rounded(q, k, v), bias_table.float(), bias_index, scale).to(torch.bfloat16)
+
+
+def _check_compute(compute):
+    if compute not in COMPUTE_MODES:
+        raise ValueError(f"compute must be one of {COMPUTE_MODES} (got {compute!r})")
 
 
 _INDEX_CACHE = {}       # id(index tensor) -> (weak reference, its version, table rows, device, the int32 copy)
@@ -85,10 +108,36 @@ class _WindowAttention(torch.autograd.Function):
         return (*g, None, None, None)
 
 
-def window_attention(q, k, v, bias_table, bias_index, scale=None):
+class _WindowAttentionBf16(torch.autograd.Function):
+    """_WindowAttention on bf16 q, k, v and an fp32 table (the caller casts, and disables autocast around `apply`) -> bf16 out"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, table, index, scale, keep):
+        from . import _cabi
+        q, k, v, table = q.contiguous(), k.contiguous(), v.contiguous(), table.contiguous()
+        out, stats = _cabi.window_attn_forward(q, k, v, table, index, scale, want_stats=keep)
+        if keep:
+            ctx.save_for_backward(q, k, v, table, index, out, stats)
+            ctx.scale = scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import _cabi
+        q, k, v, table, index, out, stats = ctx.saved_tensors
+        g = _cabi.window_attn_backward(q, k, v, table, index, ctx.scale, out, stats, grad_out.to(torch.bfloat16).contiguous(),
+                                       need=tuple(ctx.needs_input_grad[:4]))
+        return (*g, None, None, None)
+
+
+def window_attention(q, k, v, bias_table, bias_index, scale=None, compute="fp32"):
     """softmax(scale q k^T + bias_table[bias_index]) v per window and head (`window_attention_torch` has the shapes), as ONE
     differentiable call: gradients to `q`, `k`, `v` and `bias_table`.  Limits: 1 <= nq, nk <= 256, 1 <= d <= 32; anything else,
-    a non-integer or out-of-range index, or mismatched shapes: ValueError before any launch.  `scale`: default d ** -0.5."""
+    a non-integer or out-of-range index, or mismatched shapes: ValueError before any launch.  `scale`: default d ** -0.5.
+    `compute`: "fp32" (fp32 result; other dtypes are cast to fp32) or "bf16" (q, k, v cast to bf16 if they are not, the table to
+    fp32, a bf16 result: `window_attention_bf16_torch`); gradients arrive in each input's own dtype."""
+    _check_compute(compute)
     for t, name in ((q, "q"), (k, "k"), (v, "v"), (bias_table, "bias_table")):
         if not (torch.is_tensor(t) and t.dtype.is_floating_point):
             raise ValueError(f"{name} must be a floating-point tensor")
@@ -114,9 +163,16 @@ def window_attention(q, k, v, bias_table, bias_index, scale=None):
     if not (q.device == k.device == v.device == bias_table.device):
         raise ValueError("q, k, v and bias_table must be on one device")
     index = _checked_index(bias_index, T, q.device)
+    if compute == "bf16" and not q.is_cuda:
+        return window_attention_bf16_torch(q, k, v, bias_table, index, scale)
     if not q.is_cuda:
         return window_attention_torch(q, k, v, bias_table, index, scale)
     keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, bias_table))
+    if compute == "bf16":
+        q, k, v = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
+        bias_table = bias_table if bias_table.dtype == torch.float32 else bias_table.float()
+        with torch.autocast("cuda", enabled=False):
+            return _WindowAttentionBf16.apply(q, k, v, bias_table, index, scale, keep)
     q, k, v, bias_table = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, bias_table))
     return _WindowAttention.apply(q, k, v, bias_table, index, scale, keep)
 
@@ -145,6 +201,13 @@ def window_attention_rope_torch(q, k, v, angles, scale=None):
     return (torch.softmax(attn, dim=-1) @ vh).transpose(1, 2).reshape(W, nq, C)
 
 
+def window_attention_rope_bf16_torch(q, k, v, angles, scale=None):
+    """the contract of `window_attention_rope(..., compute="bf16")`: `window_attention_rope_torch` in fp32 on q, k, v rounded to
+    bf16 (and the angles as fp32), the result rounded to bf16.  The kernels additionally round the ROTATED q and k to bf16, as the
+    reference's apply_rotary_emb_single does; include/gsasr_splat.h has that contract."""
+    return window_attention_rope_torch(*_bf16_rounded(q, k, v), angles.float(), scale).to(torch.bfloat16)
+
+
 class _WindowAttentionRope(torch.autograd.Function):
     """(q, k, v, angles, scale, keep) -> out; `keep`: save the row statistic and the (cos, sin) table for a backward"""
 
@@ -170,11 +233,36 @@ class _WindowAttentionRope(torch.autograd.Function):
         return (*g, None, None)
 
 
-def window_attention_rope(q, k, v, angles, scale=None):
+class _WindowAttentionRopeBf16(torch.autograd.Function):
+    """_WindowAttentionRope on bf16 q, k, v and fp32 angles (the caller casts, and disables autocast around `apply`) -> bf16 out"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, angles, scale, keep):
+        from . import _cabi
+        q, k, v, angles = q.contiguous(), k.contiguous(), v.contiguous(), angles.contiguous()
+        out, stats, cossin = _cabi.window_attn_rope_forward(q, k, v, angles, scale, want_stats=keep)
+        if keep:
+            ctx.save_for_backward(q, k, v, angles, out, stats, cossin)
+            ctx.scale = scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import _cabi
+        q, k, v, angles, out, stats, cossin = ctx.saved_tensors
+        g = _cabi.window_attn_rope_backward(q, k, v, angles, ctx.scale, out, stats, cossin, grad_out.to(torch.bfloat16).contiguous(),
+                                            need=tuple(ctx.needs_input_grad[:4]))
+        return (*g, None, None)
+
+
+def window_attention_rope(q, k, v, angles, scale=None, compute="fp32"):
     """softmax(scale rot(q) rot(k)^T) v per window and head, q and k rotated by `angles` (`window_attention_rope_torch` has the
     shapes and the rotation), as ONE differentiable call: gradients to `q`, `k`, `v` and `angles`.  Limits: 1 <= nq, nk <= 256,
     d even with 2 <= d <= 32, angles [H, N >= max(nq, nk), d/2] floating point on the inputs' device; anything else: ValueError
-    before any launch.  `scale`: default d ** -0.5."""
+    before any launch.  `scale`: default d ** -0.5.  `compute`: "fp32" or "bf16", as in `window_attention` (bf16: the angles are
+    cast to fp32, the rotation is evaluated in fp32 and the rotated q, k rounded to bf16)."""
+    _check_compute(compute)
     for t, name in ((q, "q"), (k, "k"), (v, "v"), (angles, "angles")):
         if not (torch.is_tensor(t) and t.dtype.is_floating_point):
             raise ValueError(f"{name} must be a floating-point tensor")
@@ -197,9 +285,16 @@ def window_attention_rope(q, k, v, angles, scale=None):
     scale = float(d ** -0.5 if scale is None else scale)
     if not (q.device == k.device == v.device == angles.device):
         raise ValueError("q, k, v and angles must be on one device")
+    if compute == "bf16" and not q.is_cuda:
+        return window_attention_rope_bf16_torch(q, k, v, angles, scale)
     if not q.is_cuda:
         return window_attention_rope_torch(q, k, v, angles, scale)
     keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, angles))
+    if compute == "bf16":
+        q, k, v = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
+        angles = angles if angles.dtype == torch.float32 else angles.float()
+        with torch.autocast("cuda", enabled=False):
+            return _WindowAttentionRopeBf16.apply(q, k, v, angles, scale, keep)
     q, k, v, angles = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, angles))
     return _WindowAttentionRope.apply(q, k, v, angles, scale, keep)
 
@@ -215,38 +310,51 @@ def rope_angles(freqs, t_x, t_y):
         return t_x[None, :, None] * freqs[0][:, None, :] + t_y[None, :, None] * freqs[1][:, None, :]
 
 
-def _rope_module_forward(self, gs, feat=None):
+def _rope_module_forward(self, gs, feat=None, compute="fp32"):
     """the RoPE module's own Linears around window_attention_rope: `forward(gs)` or `forward(gs, feat)`"""
     src = gs if feat is None else feat
     angles = rope_angles(self.rope_freqs, self.rope_t_x, self.rope_t_y)
-    return self.proj(window_attention_rope(self.qhead(gs), self.khead(src), self.vhead(src), angles))
+    x = window_attention_rope(self.qhead(gs), self.khead(src), self.vhead(src), angles, compute=compute)
+    return self.proj(x if compute == "fp32" else x.to(gs.dtype))      # (bf16: a no-op under autocast; an fp32 model outside it keeps working)
 
 
-def _module_forward(self, gs, feat=None):
+def _module_forward(self, gs, feat=None, compute="fp32"):
     """the module's own Linears around window_attention: `forward(gs)` (self attention) or `forward(gs, feat)` (keys and values
     from `feat`)"""
     src = gs if feat is None else feat
     c = gs.shape[-1]
     scale = getattr(self, "scale", None)
     x = window_attention(self.qhead(gs), self.khead(src), self.vhead(src), self.relative_position_bias_table,
-                         self.relative_position_index, (c // self.num_heads) ** -0.5 if scale is None else scale)
-    return self.proj(x)
+                         self.relative_position_index, (c // self.num_heads) ** -0.5 if scale is None else scale, compute=compute)
+    return self.proj(x if compute == "fp32" else x.to(gs.dtype))
 
 
-def use_hip_attention(model) -> int:
+def _rope_module_forward_bf16(self, gs, feat=None):
+    return _rope_module_forward(self, gs, feat, "bf16")
+
+
+def _module_forward_bf16(self, gs, feat=None):
+    return _module_forward(self, gs, feat, "bf16")
+
+
+def use_hip_attention(model, compute="fp32") -> int:
     """give every module of `model` that carries the decoder's attention attributes (qhead, khead, vhead, proj,
     relative_position_bias_table, relative_position_index, num_heads: WindowCrossAttn and GSSelfAttn) a `forward` that runs
     its three Linears, `window_attention` and `proj` with the module's own parameters; likewise every module of the RoPE
     decoder (qhead, khead, vhead, proj, num_heads, rope_freqs, rope_t_x, rope_t_y and no relative_position_bias_table:
     WindowCrossAttn and GSSelfAttn of utils/fea2gsropeamp.py, rope_mixed or not) one that runs `rope_angles` and
-    `window_attention_rope` -> the number of modules switched, both kinds.  Parameters, buffers and state dicts are untouched."""
+    `window_attention_rope` -> the number of modules switched, both kinds.  Parameters, buffers and state dicts are untouched.
+    `compute="bf16"`: the switched modules call the ops in that mode (for a model run under bf16 autocast) and cast the result to
+    their input's dtype before `proj`."""
+    _check_compute(compute)
+    biased, rope = (_module_forward, _rope_module_forward) if compute == "fp32" else (_module_forward_bf16, _rope_module_forward_bf16)
     n = 0
     for m in model.modules():
         if all(hasattr(m, a) for a in _ATTRS):
-            m.forward = types.MethodType(_module_forward, m)
+            m.forward = types.MethodType(biased, m)
             n += 1
         elif all(hasattr(m, a) for a in _ROPE_ATTRS) and not hasattr(m, "relative_position_bias_table"):
-            m.forward = types.MethodType(_rope_module_forward, m)
+            m.forward = types.MethodType(rope, m)
             n += 1
     return n
 

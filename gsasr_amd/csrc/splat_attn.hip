@@ -40,6 +40,12 @@
 // conjugate at the store (the pair's other column is on lane ^ 1 of the D layout).  The angle gradient is a sum over windows of
 // Im(conj(x) g_x) of the un-rotated q, k and their gradients: k_attn_angle_grad (a slice of windows per thread, in window
 // order) and k_attn_angle_sum (the slices in order) -- fixed order, no atomics, the same bits in every run.
+//
+// The bf16 entry points (gsasr_window_attn_bf16_* / gsasr_window_attn_rope_bf16_*: q, k, v, out and their gradients bf16 in
+// memory, everything else fp32; include/gsasr_splat.h has the numerical contract).  Forward: k_attn_fwd_bf, the geometry of
+// k_attn_fwd on v_mfma_f32_16x16x32_bf16 -- one instruction per score tile, V staged transposed for the permuted k order of P.
+// Backward: the kernels above instantiated on the element type T = att_bf (loads widen, stores round to nearest even, the
+// rotated operands are rounded to bf16 where they are formed); the products stay on the exact-fp32 instruction.
 #include "splat_common.h"
 
 using namespace gsasr_detail;
@@ -54,10 +60,20 @@ constexpr int ATT_MAX_D = 32;         // head dimension
 constexpr int ATT_TAB_LDS = 4096;     // table rows up to which d table is binned in LDS
 constexpr int ATT_TAB_WG = 256;       // window slots (workgroups per head) of k_attn_bwd_q = partial columns per head, at most
 
-struct AttnArgs {
-    const float *q, *k, *v, *table, *out, *grad_out;
+typedef unsigned short att_bf;        // a bf16 in memory (gsasr_bf16)
+
+// T = the activations' element type: float, or att_bf for the bf16 entry points (the table, the angles, the statistic, the
+// (cos, sin) table and their gradients are fp32 in both)
+template <typename T>
+struct AttnArgsT {
+    const T *q, *k, *v;
+    const float *table;
+    const T *out, *grad_out;
     const int *index;
-    float *o, *stats, *g_q, *g_k, *g_v, *g_table, *part;
+    T *o;
+    float *stats;
+    T *g_q, *g_k, *g_v;
+    float *g_table, *part;
     int windows, heads, nq, nk, d, rows, wslots;
     bool vec;       // index rows can be read 16 bytes at a time
     float scale;
@@ -65,12 +81,31 @@ struct AttnArgs {
     const float *angles;
     float *cossin, *g_angles;
     int arows, achunk, aslices;     // angle rows; windows per slice and slices of the angle gradient's first stage
+    int ldvec;      // bf16 forward: elements per global load of q, k, v (8, 2 or 1: the head's slice is 16-, 4- or 2-byte aligned)
 };
+typedef AttnArgsT<float> AttnArgs;
+
+// one activation as fp32, a column pair as fp32, and the store: bf16 widens exactly and is rounded to nearest even at the store
+__device__ __forceinline__ float att_ld(const float *p) { return *p; }
+__device__ __forceinline__ float att_ld(const att_bf *p) { return __uint_as_float((unsigned)*p << 16); }
+__device__ __forceinline__ float2 att_ld2(const float *p) { return *reinterpret_cast<const float2 *>(p); }
+__device__ __forceinline__ float2 att_ld2(const att_bf *p)
+{
+    const unsigned u = *reinterpret_cast<const unsigned *>(p);
+    return make_float2(__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u));
+}
+__device__ __forceinline__ att_bf att_bits(float x) { return __builtin_bit_cast(att_bf, (__bf16)x); }
+__device__ __forceinline__ void att_st(float *p, float x) { *p = x; }
+__device__ __forceinline__ void att_st(att_bf *p, float x) { *p = att_bits(x); }
+// a rotated operand as the products see it: the bf16 ops round it to bf16 (the reference rotates x.float() and returns type_as(x))
+template <typename T> __device__ __forceinline__ float att_rnd(float x) { return x; }
+template <> __device__ __forceinline__ float att_rnd<att_bf>(float x) { return (float)(__bf16)x; }
 
 __device__ __forceinline__ att_f4 att_mfma(float a, float b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // rows [0, n) x columns [0, d) of the head's slice of `src` (row pitch C floats) times `mul` into s[rows_pad][ATT_LD], zero elsewhere
-__device__ __forceinline__ void att_stage(float *s, const float *__restrict__ src, int n, int rows_pad, int d, int C, float mul)
+template <typename T>
+__device__ __forceinline__ void att_stage(float *s, const T *__restrict__ src, int n, int rows_pad, int d, int C, float mul)
 {
     // eight loads in flight per thread before the first LDS store (one load per round trip made the staging the kernels' largest cost)
     const int nthr = blockDim.x;      // (a multiple of 64)
@@ -79,7 +114,7 @@ __device__ __forceinline__ void att_stage(float *s, const float *__restrict__ sr
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int e = e0 + nthr * u, j = e >> 5, c = e & 31;
-            x[u] = (j < n && c < d) ? src[(size_t)j * C + c] : 0.f;
+            x[u] = (j < n && c < d) ? att_ld(src + (size_t)j * C + c) : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -90,15 +125,16 @@ __device__ __forceinline__ void att_stage(float *s, const float *__restrict__ sr
 }
 
 // head h's column of the table into LDS (TLDS kernels: table_rows <= ATT_TAB_LDS), so that a bias is an LDS read
-__device__ __forceinline__ void att_stage_table(float *s_tb, const AttnArgs &A, int h)
+template <typename T>
+__device__ __forceinline__ void att_stage_table(float *s_tb, const AttnArgsT<T> &A, int h)
 {
     for (int t = threadIdx.x; t < A.rows; t += blockDim.x) s_tb[t] = A.table[(size_t)t * A.heads + h];
 }
 
 template <bool TLDS>
-__device__ __forceinline__ float att_bias(const float *s_tb, const AttnArgs &A, int h, int ix)
+__device__ __forceinline__ float att_bias(const float *s_tb, const float *__restrict__ table, int heads, int h, int ix)
 {
-    return TLDS ? s_tb[ix] : A.table[(size_t)ix * A.heads + h];
+    return TLDS ? s_tb[ix] : table[(size_t)ix * heads + h];
 }
 
 // index[row][j0 .. j0 + 3] with j0 a multiple of 4; entries past nk repeat a valid one (their scores are masked).  `vec`: nk is a
@@ -122,12 +158,13 @@ __device__ __forceinline__ float att_row_sum(float v) { v += __shfl_xor(v, 16); 
 __device__ __forceinline__ float att_row_max(float v) { v = fmaxf(v, __shfl_xor(v, 16)); return fmaxf(v, __shfl_xor(v, 32)); }
 
 // the eight A / B values of a row-operand kept in registers: x[row][4 s + g], s = 0..7 (0 past d columns or when !valid)
-__device__ __forceinline__ void att_load_row(float (&r)[8], const float *__restrict__ row, int g, int d, bool valid, float mul)
+template <typename T>
+__device__ __forceinline__ void att_load_row(float (&r)[8], const T *__restrict__ row, int g, int d, bool valid, float mul)
 {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int c = 4 * s + g;
-        r[s] = (valid && c < d) ? row[c] * mul : 0.f;
+        r[s] = (valid && c < d) ? att_ld(row + c) * mul : 0.f;
     }
 }
 
@@ -139,7 +176,8 @@ __device__ __forceinline__ float att_rot(float x, float xp, float cs, float sn, 
 
 // att_stage with the rows rotated: `cs` = the head's (cos, sin) rows [angle_rows][d / 2].  The pair's other column is on the
 // neighbouring lane (element e = 32 row + column, consecutive over the lanes)
-__device__ __forceinline__ void att_stage_rot(float *s, const float *__restrict__ src, const float2 *__restrict__ cs, int n, int rows_pad, int d, int C, float mul)
+template <typename T>
+__device__ __forceinline__ void att_stage_rot(float *s, const T *__restrict__ src, const float2 *__restrict__ cs, int n, int rows_pad, int d, int C, float mul)
 {
     const int nthr = blockDim.x, hd = d >> 1;
     for (int e0 = threadIdx.x; e0 < rows_pad * 32; e0 += 8 * nthr) {
@@ -149,29 +187,30 @@ __device__ __forceinline__ void att_stage_rot(float *s, const float *__restrict_
         for (int u = 0; u < 8; ++u) {
             const int e = e0 + nthr * u, j = e >> 5, c = e & 31;
             const bool ok = j < n && c < d;
-            x[u] = ok ? src[(size_t)j * C + c] : 0.f;
+            x[u] = ok ? att_ld(src + (size_t)j * C + c) : 0.f;
             t[u] = ok ? cs[j * hd + (c >> 1)] : make_float2(0.f, 0.f);
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int e = e0 + nthr * u;
             const float xp = __shfl_xor(x[u], 1);       // (whole waves get here: rows_pad * 32 and nthr are multiples of 64)
-            if (e < rows_pad * 32) s[(e >> 5) * ATT_LD + (e & 31)] = att_rot(x[u], xp, t[u].x, t[u].y, e & 1) * mul;
+            if (e < rows_pad * 32) s[(e >> 5) * ATT_LD + (e & 31)] = att_rnd<T>(att_rot(x[u], xp, t[u].x, t[u].y, e & 1)) * mul;
         }
     }
 }
 
 // att_load_row with the row rotated by its (cos, sin) row `cs` [d / 2]: both columns of a pair in one 8-byte load
-__device__ __forceinline__ void att_load_row_rot(float (&r)[8], const float *__restrict__ row, const float2 *__restrict__ cs, int g, int d, bool valid, float mul)
+template <typename T>
+__device__ __forceinline__ void att_load_row_rot(float (&r)[8], const T *__restrict__ row, const float2 *__restrict__ cs, int g, int d, bool valid, float mul)
 {
     const bool odd = g & 1;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int c = 4 * s + g, pj = c >> 1;
         const bool ok = valid && c < d;
-        const float2 xy = ok ? *reinterpret_cast<const float2 *>(row + 2 * pj) : make_float2(0.f, 0.f);
+        const float2 xy = ok ? att_ld2(row + 2 * pj) : make_float2(0.f, 0.f);
         const float2 t = ok ? cs[pj] : make_float2(0.f, 0.f);
-        r[s] = att_rot(odd ? xy.y : xy.x, odd ? xy.x : xy.y, t.x, t.y, odd) * mul;
+        r[s] = att_rnd<T>(att_rot(odd ? xy.y : xy.x, odd ? xy.x : xy.y, t.x, t.y, odd)) * mul;
     }
 }
 
@@ -230,7 +269,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
             int ix[4];
             att_load_index(ix, irow, 16 * t + 4 * g, nk, A.vec);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) bs[t][r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+            for (int r = 0; r < 4; ++r) bs[t][r] = att_bias<TLDS>(s_tb, A.table, A.heads, h, ix[r]);
         }
 #pragma unroll
         for (int t = 0; t < MAXT; ++t) {
@@ -281,10 +320,198 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
     }
 }
 
+// ---- the forward of the bf16 ops, on v_mfma_f32_16x16x32_bf16 ----------------------------------------------------
+// Lane l supplies A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7 (eight bf16 = 16 bytes), and
+// receives D[row 4 (l >> 4) + reg][col l & 15] as above (tools/mfma_f32_layout_check.hip checks the maps).  The padded head
+// dimension 32 is ONE k step: S^T = K Q^T is one instruction per key tile, its A operand one 16-byte LDS read of a K row, its
+// B operand the query's eight consecutive columns, kept in registers.  P is the A operand of O = P V in place: a step takes the
+// key tiles 2 u and 2 u + 1, element j of lane group g is key 32 u + 16 (j >> 2) + 4 g + (j & 3), so V is staged TRANSPOSED
+// ([column][key], keys zero-filled to whole steps: an odd tile count leaves a half-empty step whose p are 0) and its B operand
+// is two 8-byte reads of four consecutive keys.  LDS pitches: K rows of 40 bf16 = 20 words (the rows l & 15 of a 16-byte read
+// start 20 r mod 64 banks apart, all different multiples of 4); V^T rows of keys + 8 bf16 = 16 m + 4 words (4 (4 m + 1) r mod 64:
+// the sixteen columns of an 8-byte read land on different groups of four banks).
+typedef __bf16 att_bf8 __attribute__((ext_vector_type(8)));
+constexpr int ATT_KLD = 40;       // bf16 per LDS row of K
+constexpr int ATT_VPAD = 8;       // bf16 past the padded keys per LDS row of V^T
+
+__device__ __forceinline__ att_f4 att_mfma_bf(att_bf8 a, att_bf8 b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ att_bf8 att_frag(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(att_bf8, make_uint4(a, b, c, d)); }
+
+// VEC consecutive bf16 at p as packed pairs (0 when !ok): one 16-, 4- or 2-byte load
+template <int VEC>
+__device__ __forceinline__ void att_ld_raw(unsigned (&w)[(VEC + 1) / 2], const att_bf *__restrict__ p, bool ok)
+{
+    if constexpr (VEC == 8) {
+        const uint4 u = ok ? *reinterpret_cast<const uint4 *>(p) : make_uint4(0u, 0u, 0u, 0u);
+        w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w;
+    } else if constexpr (VEC == 2) w[0] = ok ? *reinterpret_cast<const unsigned *>(p) : 0u;
+    else w[0] = ok ? (unsigned)*p : 0u;
+}
+
+// the packed pair (re, im) rotated by (cos, sin) in fp32, each component rounded to bf16
+__device__ __forceinline__ unsigned att_rot_pair(unsigned w, float2 t)
+{
+    const float re = __uint_as_float(w << 16), im = __uint_as_float(w & 0xffff0000u);
+    return (unsigned)att_bits(att_rot(re, im, t.x, t.y, false)) | ((unsigned)att_bits(att_rot(im, re, t.x, t.y, true)) << 16);
+}
+
+// the head's slices of K (rotated when ROPE) and V, rows [0, nk) x columns [0, d), into s_k[nkp32][ATT_KLD] and s_vt[32][vld],
+// zero elsewhere.  U loads of K and of V in flight per thread before the first LDS store
+template <int VEC, bool ROPE>
+__device__ __forceinline__ void att_stage_kv_bf(att_bf *s_k, att_bf *s_vt, const att_bf *__restrict__ ksrc, const att_bf *__restrict__ vsrc,
+                                                const float2 *__restrict__ cs, int nk, int nkp32, int vld, int d, int C)
+{
+    constexpr int CPR = 32 / VEC, NW = (VEC + 1) / 2, U = VEC == 8 ? 2 : 4;
+    const int nthr = blockDim.x, total = nkp32 * CPR, hd = d >> 1;
+    for (int e0 = threadIdx.x; e0 < total; e0 += U * nthr) {
+        unsigned kw[U][NW], vw[U][NW];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + nthr * u, j = e / CPR, cc = (e % CPR) * VEC;
+            const bool ok = e < total && j < nk && cc < d;
+            att_ld_raw<VEC>(kw[u], ksrc + (size_t)j * C + cc, ok);
+            att_ld_raw<VEC>(vw[u], vsrc + (size_t)j * C + cc, ok);
+            if constexpr (ROPE && VEC > 1) {
+#pragma unroll
+                for (int i = 0; i < NW; ++i) kw[u][i] = att_rot_pair(kw[u][i], ok ? cs[j * hd + (cc >> 1) + i] : make_float2(0.f, 0.f));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + nthr * u, j = e / CPR, cc = (e % CPR) * VEC;
+            if (e < total) {
+                att_bf *dk = s_k + j * ATT_KLD + cc;
+                if constexpr (VEC == 8) *reinterpret_cast<uint4 *>(dk) = make_uint4(kw[u][0], kw[u][1], kw[u][2], kw[u][3]);
+                else if constexpr (VEC == 2) *reinterpret_cast<unsigned *>(dk) = kw[u][0];
+                else *dk = (att_bf)kw[u][0];
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) s_vt[(cc + i) * vld + j] = (att_bf)(vw[u][i >> 1] >> (16 * (i & 1)));
+            }
+        }
+    }
+}
+
+// the query's B fragment: columns 8 g .. 8 g + 7 of its row (0 past d), rotated by the row's (cos, sin) `cs` [d / 2] when ROPE
+template <int VEC, bool ROPE>
+__device__ __forceinline__ att_bf8 att_load_q_bf(const att_bf *__restrict__ row, const float2 *__restrict__ cs, int g, int d)
+{
+    unsigned w[4];
+    if constexpr (VEC == 8) {
+        const uint4 u = 8 * g < d ? *reinterpret_cast<const uint4 *>(row + 8 * g) : make_uint4(0u, 0u, 0u, 0u);
+        w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = 8 * g + 2 * i;
+            if (VEC == 2) w[i] = c < d ? *reinterpret_cast<const unsigned *>(row + c) : 0u;
+            else w[i] = (c < d ? (unsigned)row[c] : 0u) | (c + 1 < d ? (unsigned)row[c + 1] << 16 : 0u);
+        }
+    }
+    if (ROPE) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = att_rot_pair(w[i], 8 * g + 2 * i < d ? cs[4 * g + i] : make_float2(0.f, 0.f));
+    }
+    return att_frag(w[0], w[1], w[2], w[3]);
+}
+
+// The geometry of k_attn_fwd (one workgroup per (window, head), a wave takes 16 queries, the lane holds its query's whole score
+// row in fp32: one maximum, one sum of the unrounded p).  scale multiplies the fp32 score sum; p is rounded to bf16 only as the
+// operand of P V; out is rounded once at the store.  include/gsasr_splat.h has the contract.
+template <int MAXT, bool STATS, bool TLDS, bool ROPE>
+__global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
+    const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    const int nt = (nk + 15) >> 4, nkp32 = ((nk + 31) >> 5) << 5, vld = nkp32 + ATT_VPAD;
+    att_bf *s_k = reinterpret_cast<att_bf *>(s_mem), *s_vt = s_k + nkp32 * ATT_KLD;
+    float *s_tb = reinterpret_cast<float *>(s_vt + 32 * vld);
+    const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
+    const att_bf *ksrc = A.k + (size_t)w * nk * C + h * d, *vsrc = A.v + (size_t)w * nk * C + h * d;
+    if (A.ldvec == 8) att_stage_kv_bf<8, ROPE>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
+    else if (A.ldvec == 2) att_stage_kv_bf<2, ROPE>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
+    else if (!ROPE) att_stage_kv_bf<1, false>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
+    if (TLDS) att_stage_table(s_tb, A, h);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const int nqt = (nq + 15) >> 4;
+    for (int qt = wave; qt < nqt; qt += nwaves) {
+        const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
+        const att_bf *qrow = A.q + ((size_t)w * nq + ic) * C + h * d;
+        const float2 *qcs = ROPE ? cs + ic * (d >> 1) : nullptr;
+        att_bf8 qf;
+        if (A.ldvec == 8) qf = att_load_q_bf<8, ROPE>(qrow, qcs, g, d);
+        else if (A.ldvec == 2) qf = att_load_q_bf<2, ROPE>(qrow, qcs, g, d);
+        else qf = att_load_q_bf<1, false>(qrow, qcs, g, d);
+        att_f4 sc[MAXT];
+        const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
+        float m = -INFINITY;
+        att_f4 bs[ROPE ? 1 : MAXT];         // (the whole row's biases first, as in k_attn_fwd)
+#pragma unroll
+        for (int t = 0; t < (ROPE ? 0 : MAXT); ++t) {
+            int ix[4];
+            att_load_index(ix, irow, 16 * t + 4 * g, nk, A.vec);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bs[t][r] = att_bias<TLDS>(s_tb, A.table, A.heads, h, ix[r]);
+        }
+#pragma unroll
+        for (int t = 0; t < MAXT; ++t) {
+            if (t < nt) {
+                const att_bf8 kf = __builtin_bit_cast(att_bf8, *reinterpret_cast<const uint4 *>(s_k + (16 * t + c16) * ATT_KLD + 8 * g));
+                const att_f4 zero = {0.f, 0.f, 0.f, 0.f};
+                sc[t] = att_mfma_bf(kf, qf, zero);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float s = sc[t][r] * A.scale;         // (the fp32 sum times scale, then the fp32 bias)
+                    sc[t][r] = 16 * t + 4 * g + r < nk ? (ROPE ? s : s + bs[ROPE ? 0 : t][r]) : -INFINITY;
+                    m = fmaxf(m, sc[t][r]);
+                }
+            }
+        }
+        m = att_row_max(m);
+        float l = 0.f;
+        att_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < (MAXT + 1) / 2; ++u) {
+            if (2 * u < nt) {
+                const att_bf *vr = s_vt + c16 * vld + 32 * u + 4 * g;
+                const uint2 a0 = *reinterpret_cast<const uint2 *>(vr), a1 = *reinterpret_cast<const uint2 *>(vr + 16);
+                const uint2 b0 = *reinterpret_cast<const uint2 *>(vr + 16 * vld), b1 = *reinterpret_cast<const uint2 *>(vr + 16 * vld + 16);
+                float p[8];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    p[r] = att_exp(sc[2 * u][r] - m);
+                    p[4 + r] = (2 * u + 1 < MAXT && 2 * u + 1 < nt) ? att_exp(sc[2 * u + 1 < MAXT ? 2 * u + 1 : 0][r] - m) : 0.f;
+                    l += p[r] + p[4 + r];
+                }
+                att_bf8 pf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pf[j] = (__bf16)p[j];
+                o0 = att_mfma_bf(pf, att_frag(a0.x, a0.y, a1.x, a1.y), o0);
+                o1 = att_mfma_bf(pf, att_frag(b0.x, b0.y, b1.x, b1.y), o1);     // (always: the padded columns are zero)
+            }
+        }
+        l = att_row_sum(l);
+        if (STATS && g == 0 && i < nq) A.stats[((size_t)w * A.heads + h) * nq + i] = m + logf(l);
+        const float linv = 1.f / l;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {       // the tile's row 4 g + r belongs to the query on lane 4 g + r
+            const float f = __shfl(linv, 4 * g + r);
+            const int io = qt * 16 + 4 * g + r;
+            if (io < nq) {
+                att_bf *po = A.o + ((size_t)w * nq + io) * C + h * d;
+                if (c16 < d) po[c16] = att_bits(o0[r] * f);
+                if (c16 + 16 < d) po[c16 + 16] = att_bits(o1[r] * f);
+            }
+        }
+    }
+}
+
 // TAB: 0 no table gradient, 1 binned in LDS -> a partial column, 2 global double atomics on the scratch's [rows, heads]
 // ROPE (TAB 0, no table): K staged rotated, the query row rotated in registers, dq times the conjugate at the store
-template <int TAB, bool TLDS, bool ROPE = false>
-__global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
+// T: the activations' element type (bf16: loads widen as they stage, delta is of the bf16 out that was stored, dq is rounded at the store)
+template <int TAB, bool TLDS, bool ROPE = false, typename T = float>
+__global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int slot = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
@@ -329,7 +556,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
                 int ixn[4];     // (two tiles ahead: one tile's products are shorter than a round trip to L2)
                 if (!ROPE) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+                    for (int r = 0; r < 4; ++r) b[r] = att_bias<TLDS>(s_tb, A.table, A.heads, h, ix[r]);
                     att_load_index(ixn, irow, 16 * t + 32 + 4 * g, nk, A.vec);
                 }
                 const float *kr = s_k + (16 * t + 4 * g) * ATT_LD + c16;
@@ -370,9 +597,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
                         u1 = att_unrot(dq1[r] * A.scale, cs, min(io, nq - 1), d >> 1, c16 + 16, d);
                     }
                     if (io < nq) {
-                        float *po = A.g_q + ((size_t)w * nq + io) * C + h * d;
-                        if (c16 < d) po[c16] = ROPE ? u0 : dq0[r] * A.scale;
-                        if (c16 + 16 < d) po[c16 + 16] = ROPE ? u1 : dq1[r] * A.scale;
+                        T *po = A.g_q + ((size_t)w * nq + io) * C + h * d;
+                        if (c16 < d) att_st(po + c16, ROPE ? u0 : dq0[r] * A.scale);
+                        if (c16 + 16 < d) att_st(po + c16 + 16, ROPE ? u1 : dq1[r] * A.scale);
                     }
                 }
             }
@@ -387,7 +614,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgs A)
 
 // g_table[t, h] = the partial columns of head h added in a fixed order: 32 entries per workgroup, eight threads per entry
 // each adding the slots s = slice, slice + 8, ... (short chains of independent loads), then the eight sums in slice order
-__global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgs A)
+template <typename T = float>
+__global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgsT<T> A)
 {
     __shared__ float s_sum[8][32];
     const int e = blockIdx.x * 32 + (threadIdx.x & 31), slice = threadIdx.x >> 5;
@@ -404,15 +632,16 @@ __global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgs A)
 }
 
 // g_table = the double sums of the TAB == 2 walk, rounded once
-__global__ __launch_bounds__(256) void k_attn_table_round(AttnArgs A)
+template <typename T = float>
+__global__ __launch_bounds__(256) void k_attn_table_round(AttnArgsT<T> A)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < A.rows * A.heads) A.g_table[e] = (float)reinterpret_cast<const double *>(A.part)[e];
 }
 
 // ROPE: scale Q staged rotated, the key row rotated in registers, dk times the conjugate at the store
-template <bool TLDS, bool ROPE = false>
-__global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
+template <bool TLDS, bool ROPE = false, typename T = float>
+__global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
@@ -429,8 +658,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
     for (int i = threadIdx.x; i < nqp; i += blockDim.x) {
         float a = 0.f;
         if (i < nq) {
-            const float *po = A.out + qbase + (size_t)i * C;
-            for (int c = 0; c < d; ++c) a = fmaf(s_g[i * ATT_LD + c], po[c], a);
+            const T *po = A.out + qbase + (size_t)i * C;
+            for (int c = 0; c < d; ++c) a = fmaf(s_g[i * ATT_LD + c], att_ld(po + c), a);
         }
         s_delta[i] = a;
         s_lse[i] = i < nq ? A.stats[((size_t)w * A.heads + h) * nq + i] : 0.f;
@@ -460,7 +689,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
             if (!ROPE) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    b[r] = att_bias<TLDS>(s_tb, A, h, ix[r]);
+                    b[r] = att_bias<TLDS>(s_tb, A.table, A.heads, h, ix[r]);
                     ixn[r] = A.index[(size_t)min(16 * t + 32 + 4 * g + r, nq - 1) * nk + jc];
                 }
             }
@@ -502,12 +731,12 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
             if (jo < nk) {
                 const size_t off = ((size_t)w * nk + jo) * C + h * d;
                 if (A.g_k) {
-                    if (c16 < d) A.g_k[off + c16] = ROPE ? u0 : dk0[r];
-                    if (c16 + 16 < d) A.g_k[off + c16 + 16] = ROPE ? u1 : dk1[r];
+                    if (c16 < d) att_st(A.g_k + off + c16, ROPE ? u0 : dk0[r]);
+                    if (c16 + 16 < d) att_st(A.g_k + off + c16 + 16, ROPE ? u1 : dk1[r]);
                 }
                 if (A.g_v) {
-                    if (c16 < d) A.g_v[off + c16] = dv0[r];
-                    if (c16 + 16 < d) A.g_v[off + c16 + 16] = dv1[r];
+                    if (c16 < d) att_st(A.g_v + off + c16, dv0[r]);
+                    if (c16 + 16 < d) att_st(A.g_v + off + c16 + 16, dv1[r]);
                 }
             }
         }
@@ -516,7 +745,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgs A)
 
 // cossin[h, n, j] = (cos, sin) of angles[h, n, j], once per call: the accurate sincosf (angles reach tens of radians, where the
 // hardware's v_sin_f32 / v_cos_f32 lose the bits the scores need), read by every workgroup of the three attention kernels
-__global__ __launch_bounds__(256) void k_attn_cossin(AttnArgs A)
+template <typename T = float>
+__global__ __launch_bounds__(256) void k_attn_cossin(AttnArgsT<T> A)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= A.heads * A.arows * (A.d >> 1)) return;
@@ -529,7 +759,8 @@ __global__ __launch_bounds__(256) void k_attn_cossin(AttnArgs A)
 // of head h and token n of the UN-rotated input and of its gradient.  One thread per angle; blockIdx.y = a slice of `achunk`
 // consecutive windows, added in window order (q's term, then k's) into the slice's partial (or g_angles itself when there is one
 // slice).  Rows past both nq and nk get exactly 0.
-__global__ __launch_bounds__(256) void k_attn_angle_grad(AttnArgs A)
+template <typename T = float>
+__global__ __launch_bounds__(256) void k_attn_angle_grad(AttnArgsT<T> A)
 {
     const int hd = A.d >> 1, per = A.heads * A.arows * hd;
     const int e = blockIdx.x * 256 + threadIdx.x, slice = blockIdx.y;
@@ -541,13 +772,13 @@ __global__ __launch_bounds__(256) void k_attn_angle_grad(AttnArgs A)
     for (int w = w0; w < w1; ++w) {
         if (n < A.nq) {
             const size_t off = ((size_t)w * A.nq + n) * C + col;
-            const float2 x = *reinterpret_cast<const float2 *>(A.q + off), gx = *reinterpret_cast<const float2 *>(A.g_q + off);
+            const float2 x = att_ld2(A.q + off), gx = att_ld2(A.g_q + off);
             a = fmaf(x.x, gx.y, a);
             a = fmaf(-x.y, gx.x, a);
         }
         if (n < A.nk) {
             const size_t off = ((size_t)w * A.nk + n) * C + col;
-            const float2 x = *reinterpret_cast<const float2 *>(A.k + off), gx = *reinterpret_cast<const float2 *>(A.g_k + off);
+            const float2 x = att_ld2(A.k + off), gx = att_ld2(A.g_k + off);
             a = fmaf(x.x, gx.y, a);
             a = fmaf(-x.y, gx.x, a);
         }
@@ -556,7 +787,8 @@ __global__ __launch_bounds__(256) void k_attn_angle_grad(AttnArgs A)
 }
 
 // g_angles = the slices' partials added in slice order
-__global__ __launch_bounds__(256) void k_attn_angle_sum(AttnArgs A)
+template <typename T = float>
+__global__ __launch_bounds__(256) void k_attn_angle_sum(AttnArgsT<T> A)
 {
     const int per = A.heads * A.arows * (A.d >> 1), e = blockIdx.x * 256 + threadIdx.x;
     if (e >= per) return;
@@ -565,7 +797,8 @@ __global__ __launch_bounds__(256) void k_attn_angle_sum(AttnArgs A)
     A.g_angles[e] = a;
 }
 
-int attn_geometry_check(const gsasr_window_attn *a)
+template <typename D>
+int attn_geometry_check(const D *a)
 {
     if (!a) return fail(GSASR_ERR_ARG, "null window-attention descriptor");
     if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
@@ -579,11 +812,20 @@ int attn_geometry_check(const gsasr_window_attn *a)
     return GSASR_OK;
 }
 
-inline int attn_wslots(const gsasr_window_attn *a) { return a->windows < ATT_TAB_WG ? a->windows : ATT_TAB_WG; }
+template <typename D>
+inline int attn_wslots(const D *a) { return a->windows < ATT_TAB_WG ? a->windows : ATT_TAB_WG; }
 
-AttnArgs attn_args(const gsasr_window_attn *a)
+// elements per global load of the bf16 forward: by the alignment of a head's slice (its offset is 2 h d bytes into a row of 2 H d)
+inline int attn_ldvec(const void *q, const void *k, const void *v, int d)
 {
-    AttnArgs A;
+    const uintptr_t any = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v;
+    return d % 8 == 0 && (any & 15) == 0 ? 8 : d % 2 == 0 && (any & 3) == 0 ? 2 : 1;
+}
+
+template <typename T, typename D>
+AttnArgsT<T> attn_args(const D *a)
+{
+    AttnArgsT<T> A;
     A.q = a->q; A.k = a->k; A.v = a->v; A.table = a->table; A.index = a->index; A.out = a->out; A.o = a->out; A.stats = a->stats;
     A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.g_table = a->g_table; A.part = (float *)a->scratch;
     A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.rows = a->table_rows;
@@ -591,13 +833,15 @@ AttnArgs attn_args(const gsasr_window_attn *a)
     A.vec = a->nk % 4 == 0 && ((uintptr_t)a->index & 15) == 0;
     A.scale = a->scale;
     A.angles = nullptr; A.cossin = nullptr; A.g_angles = nullptr; A.arows = 0; A.achunk = 0; A.aslices = 0;
+    A.ldvec = attn_ldvec(a->q, a->k, a->v, a->head_dim);
     return A;
 }
 
 constexpr int ATT_ANGLE_CHUNK = 8;      // windows a thread of k_attn_angle_grad adds, at least
 constexpr int ATT_ANGLE_SLICES = 64;    // slices (partials per angle), at most
 
-int attn_rope_geometry_check(const gsasr_window_attn_rope *a)
+template <typename D>
+int attn_rope_geometry_check(const D *a)
 {
     if (!a) return fail(GSASR_ERR_ARG, "null rotary window-attention descriptor");
     if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
@@ -618,11 +862,12 @@ inline int attn_angle_chunk(int windows)
 }
 inline int attn_angle_slices(int windows) { return (windows + attn_angle_chunk(windows) - 1) / attn_angle_chunk(windows); }
 
-inline bool attn_misaligned(const void *p) { return ((uintptr_t)p & 7) != 0; }
+inline bool attn_misaligned(const void *p, uintptr_t to = 8) { return ((uintptr_t)p & (to - 1)) != 0; }
 
-AttnArgs attn_rope_args(const gsasr_window_attn_rope *a)
+template <typename T, typename D>
+AttnArgsT<T> attn_rope_args(const D *a)
 {
-    AttnArgs A;
+    AttnArgsT<T> A;
     A.q = a->q; A.k = a->k; A.v = a->v; A.table = nullptr; A.index = nullptr; A.out = a->out; A.o = a->out; A.stats = a->stats;
     A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.g_table = nullptr; A.part = (float *)a->scratch;
     A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.rows = 0;
@@ -631,6 +876,7 @@ AttnArgs attn_rope_args(const gsasr_window_attn_rope *a)
     A.scale = a->scale;
     A.angles = a->angles; A.cossin = a->cossin; A.g_angles = a->g_angles; A.arows = a->angle_rows;
     A.achunk = attn_angle_chunk(a->windows); A.aslices = attn_angle_slices(a->windows);
+    A.ldvec = attn_ldvec(a->q, a->k, a->v, a->head_dim);
     return A;
 }
 
@@ -641,10 +887,11 @@ inline int attn_waves(int n)
     return tiles % 4 != 0 && tiles % 3 == 0 ? 3 : 4;
 }
 
-inline bool attn_tlds(const gsasr_window_attn *a) { return a->table_rows <= ATT_TAB_LDS; }
+template <typename D>
+inline bool attn_tlds(const D *a) { return a->table_rows <= ATT_TAB_LDS; }
 
-template <typename K>
-int attn_launch(K kernel, unsigned grid, int waves, size_t lds, hipStream_t st, const AttnArgs &A)
+template <typename K, typename ARGS>
+int attn_launch(K kernel, unsigned grid, int waves, size_t lds, hipStream_t st, const ARGS &A)
 {
     if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, A);
@@ -652,11 +899,8 @@ int attn_launch(K kernel, unsigned grid, int waves, size_t lds, hipStream_t st, 
     return GSASR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *a)
+template <typename D>
+size_t attn_scratch_bytes(const D *a)
 {
     if (attn_geometry_check(a)) return 0;
     // the partial table columns of the backward (one per window slot and head), or above ATT_TAB_LDS rows the table's sums
@@ -666,11 +910,123 @@ size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *a)
     return 256 + align_up((size_t)attn_wslots(a) * a->heads * a->table_rows * sizeof(float), 256);
 }
 
+// the bf16 descriptors: an activation pointer the call needs (non-null ones among the optional) must hold whole elements
+inline bool attn_bf_misaligned(std::initializer_list<const void *> ps, uintptr_t to)
+{
+    for (const void *p : ps) if (attn_misaligned(p, to)) return true;
+    return false;
+}
+
+// the backward of both element types: the three kernels and the table kernels, instantiated on T
+template <typename T, typename D>
+int attn_backward(const D *a, void *stream)
+{
+    if (int rc = attn_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out || !a->stats || !a->grad_out)
+        return fail(GSASR_ERR_ARG, "null q, k, v, table, index, out, stats or grad_out pointer");
+    if (sizeof(T) == 2 && attn_bf_misaligned({a->q, a->k, a->v, a->out, a->grad_out, a->g_q, a->g_k, a->g_v}, 2))
+        return fail(GSASR_ERR_ARG, "q, k, v, out, grad_out, g_q, g_k and g_v must be 2-byte aligned");
+    const AttnArgsT<T> A = attn_args<T>(a);
+    hipStream_t st = (hipStream_t)stream;
+    const bool tlds = attn_tlds(a);
+    const int tab = !a->g_table ? 0 : tlds ? 1 : 2;
+    if (tab && !a->scratch) return fail(GSASR_ERR_ARG, "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)");
+    if (tab == 2 && ((uintptr_t)a->scratch & 7)) return fail(GSASR_ERR_ARG, "scratch must be 8-byte aligned");
+    if (a->g_q || tab) {
+        const size_t lds = ((size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD + (tlds ? a->table_rows : 0) + (tab == 1 ? a->table_rows : 0)) * sizeof(float);
+        const unsigned grid = (unsigned)(A.wslots * a->heads);
+        const int waves = attn_waves(a->nq);
+        int rc;
+        if (tab == 2) {
+            HIP_TRY(hipMemsetAsync(a->scratch, 0, (size_t)a->table_rows * a->heads * sizeof(double), st));
+            rc = attn_launch(k_attn_bwd_q<2, false, false, T>, grid, waves, lds, st, A);
+        } else if (tab == 1) rc = attn_launch(k_attn_bwd_q<1, true, false, T>, grid, waves, lds, st, A);
+        else rc = tlds ? attn_launch(k_attn_bwd_q<0, true, false, T>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_q<0, false, false, T>, grid, waves, lds, st, A);
+        if (rc) return rc;
+        if (tab == 1) {
+            hipLaunchKernelGGL(k_attn_table_sum<T>, dim3((unsigned)((a->table_rows * a->heads + 31) / 32)), dim3(256), 0, st, A);
+            HIP_TRY(hipGetLastError());
+        }
+        if (tab == 2) {
+            hipLaunchKernelGGL(k_attn_table_round<T>, dim3((unsigned)((a->table_rows * a->heads + 255) / 256)), dim3(256), 0, st, A);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (a->g_k || a->g_v) {
+        const int nqp = (a->nq + 15) / 16 * 16;
+        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp + (tlds ? a->table_rows : 0)) * sizeof(float);
+        const unsigned grid = (unsigned)(a->windows * a->heads);
+        const int waves = attn_waves(a->nk);
+        if (int rc = tlds ? attn_launch(k_attn_bwd_kv<true, false, T>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_kv<false, false, T>, grid, waves, lds, st, A)) return rc;
+    }
+    return GSASR_OK;
+}
+
+template <typename D>
+size_t attn_rope_scratch_bytes(const D *a)
+{
+    if (attn_rope_geometry_check(a)) return 0;
+    // the slices' partial angle gradients of the backward; never 0 for a valid descriptor
+    const int slices = attn_angle_slices(a->windows);
+    const bool part = a->g_angles && slices > 1;
+    return 256 + (part ? align_up((size_t)slices * a->heads * a->angle_rows * (a->head_dim / 2) * sizeof(float), 256) : 0);
+}
+
+template <typename T, typename D>
+int attn_rope_backward(const D *a, void *stream)
+{
+    if (int rc = attn_rope_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->out || !a->stats || !a->grad_out || !a->cossin)
+        return fail(GSASR_ERR_ARG, "null q, k, v, out, stats, grad_out or cossin pointer");
+    if (a->g_angles && (!a->g_q || !a->g_k)) return fail(GSASR_ERR_ARG, "g_angles needs g_q and g_k (it is formed from them)");
+    if (sizeof(T) == 2) {
+        if (attn_bf_misaligned({a->q, a->k, a->v, a->out, a->grad_out, a->g_q, a->g_k, a->g_v}, 4) || attn_misaligned(a->cossin))
+            return fail(GSASR_ERR_ARG, "q, k, v, out, grad_out, g_q, g_k and g_v must be 4-byte aligned and cossin 8-byte aligned");
+    } else if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin) || attn_misaligned(a->g_q) || attn_misaligned(a->g_k))
+        return fail(GSASR_ERR_ARG, "q, k, cossin, g_q and g_k must be 8-byte aligned");
+    const AttnArgsT<T> A = attn_rope_args<T>(a);
+    if (a->g_angles && A.aslices > 1 && !a->scratch)
+        return fail(GSASR_ERR_ARG, "null scratch pointer (the angle gradient needs gsasr_window_attn_rope_scratch_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    if (a->g_q) {
+        const size_t lds = (size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD * sizeof(float);
+        if (int rc = attn_launch(k_attn_bwd_q<0, false, true, T>, (unsigned)(a->windows * a->heads), attn_waves(a->nq), lds, st, A)) return rc;
+    }
+    if (a->g_k || a->g_v) {
+        const int nqp = (a->nq + 15) / 16 * 16;
+        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp) * sizeof(float);
+        if (int rc = attn_launch(k_attn_bwd_kv<false, true, T>, (unsigned)(a->windows * a->heads), attn_waves(a->nk), lds, st, A)) return rc;
+    }
+    if (a->g_angles) {
+        const unsigned blocks = (unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256);
+        hipLaunchKernelGGL(k_attn_angle_grad<T>, dim3(blocks, (unsigned)A.aslices), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+        if (A.aslices > 1) {
+            hipLaunchKernelGGL(k_attn_angle_sum<T>, dim3(blocks), dim3(256), 0, st, A);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return GSASR_OK;
+}
+
+// LDS of the bf16 forward: K rows and V transposed, keys padded to whole paired steps (32), and the head's table column
+inline size_t attn_bf_fwd_lds(int nk, int table_rows_in_lds)
+{
+    const int nkp32 = (nk + 31) / 32 * 32;
+    return ((size_t)nkp32 * ATT_KLD + (size_t)32 * (nkp32 + ATT_VPAD)) * sizeof(att_bf) + (size_t)table_rows_in_lds * sizeof(float);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *a) { return attn_scratch_bytes(a); }
+
 int gsasr_window_attn_forward(const gsasr_window_attn *a, void *stream)
 {
     if (int rc = attn_geometry_check(a)) return rc;
     if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out) return fail(GSASR_ERR_ARG, "null q, k, v, table, index or out pointer");
-    const AttnArgs A = attn_args(a);
+    const AttnArgs A = attn_args<float>(a);
     const int nt = (a->nk + 15) / 16;
     const bool tlds = attn_tlds(a), stats = a->stats != nullptr;
     const size_t lds = ((size_t)2 * nt * 16 * ATT_LD + (tlds ? a->table_rows : 0)) * sizeof(float);
@@ -685,69 +1041,23 @@ int gsasr_window_attn_forward(const gsasr_window_attn *a, void *stream)
 #undef ATT_FWD
 }
 
-int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream)
-{
-    if (int rc = attn_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out || !a->stats || !a->grad_out)
-        return fail(GSASR_ERR_ARG, "null q, k, v, table, index, out, stats or grad_out pointer");
-    const AttnArgs A = attn_args(a);
-    hipStream_t st = (hipStream_t)stream;
-    const bool tlds = attn_tlds(a);
-    const int tab = !a->g_table ? 0 : tlds ? 1 : 2;
-    if (tab && !a->scratch) return fail(GSASR_ERR_ARG, "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)");
-    if (tab == 2 && ((uintptr_t)a->scratch & 7)) return fail(GSASR_ERR_ARG, "scratch must be 8-byte aligned");
-    if (a->g_q || tab) {
-        const size_t lds = ((size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD + (tlds ? a->table_rows : 0) + (tab == 1 ? a->table_rows : 0)) * sizeof(float);
-        const unsigned grid = (unsigned)(A.wslots * a->heads);
-        const int waves = attn_waves(a->nq);
-        int rc;
-        if (tab == 2) {
-            HIP_TRY(hipMemsetAsync(a->scratch, 0, (size_t)a->table_rows * a->heads * sizeof(double), st));
-            rc = attn_launch(k_attn_bwd_q<2, false>, grid, waves, lds, st, A);
-        } else if (tab == 1) rc = attn_launch(k_attn_bwd_q<1, true>, grid, waves, lds, st, A);
-        else rc = tlds ? attn_launch(k_attn_bwd_q<0, true>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_q<0, false>, grid, waves, lds, st, A);
-        if (rc) return rc;
-        if (tab == 1) {
-            hipLaunchKernelGGL(k_attn_table_sum, dim3((unsigned)((a->table_rows * a->heads + 31) / 32)), dim3(256), 0, st, A);
-            HIP_TRY(hipGetLastError());
-        }
-        if (tab == 2) {
-            hipLaunchKernelGGL(k_attn_table_round, dim3((unsigned)((a->table_rows * a->heads + 255) / 256)), dim3(256), 0, st, A);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    if (a->g_k || a->g_v) {
-        const int nqp = (a->nq + 15) / 16 * 16;
-        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp + (tlds ? a->table_rows : 0)) * sizeof(float);
-        const unsigned grid = (unsigned)(a->windows * a->heads);
-        const int waves = attn_waves(a->nk);
-        if (int rc = tlds ? attn_launch(k_attn_bwd_kv<true>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_kv<false>, grid, waves, lds, st, A)) return rc;
-    }
-    return GSASR_OK;
-}
+int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream) { return attn_backward<float>(a, stream); }
 
-size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_rope *a)
-{
-    if (attn_rope_geometry_check(a)) return 0;
-    // the slices' partial angle gradients of the backward; never 0 for a valid descriptor
-    const int slices = attn_angle_slices(a->windows);
-    const bool part = a->g_angles && slices > 1;
-    return 256 + (part ? align_up((size_t)slices * a->heads * a->angle_rows * (a->head_dim / 2) * sizeof(float), 256) : 0);
-}
+size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_rope *a) { return attn_rope_scratch_bytes(a); }
 
 int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *a, void *stream)
 {
     if (int rc = attn_rope_geometry_check(a)) return rc;
     if (!a->q || !a->k || !a->v || !a->angles || !a->out || !a->cossin) return fail(GSASR_ERR_ARG, "null q, k, v, angles, out or cossin pointer");
     if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin)) return fail(GSASR_ERR_ARG, "q, k and cossin must be 8-byte aligned");
-    const AttnArgs A = attn_rope_args(a);
+    const AttnArgs A = attn_rope_args<float>(a);
     const int nt = (a->nk + 15) / 16;
     const bool stats = a->stats != nullptr;
     const size_t lds = (size_t)2 * nt * 16 * ATT_LD * sizeof(float);
     const unsigned grid = (unsigned)(a->windows * a->heads);
     const int waves = attn_waves(a->nq);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_attn_cossin, dim3((unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_attn_cossin<float>, dim3((unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256)), dim3(256), 0, st, A);
     HIP_TRY(hipGetLastError());
 #define ATT_FWD(T) (stats ? attn_launch(k_attn_fwd<T, true, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, false, false, true>, grid, waves, lds, st, A))
     if (nt <= 3) return ATT_FWD(3);
@@ -756,37 +1066,57 @@ int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *a, void *stream
 #undef ATT_FWD
 }
 
-int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *a, void *stream)
+int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *a, void *stream) { return attn_rope_backward<float>(a, stream); }
+
+// ---- bf16 activations: the forward on the bf16 matrix instruction, the backward the kernels above on att_bf ----
+size_t gsasr_window_attn_bf16_scratch_bytes(const gsasr_window_attn_bf16 *a) { return attn_scratch_bytes(a); }
+
+int gsasr_window_attn_bf16_forward(const gsasr_window_attn_bf16 *a, void *stream)
+{
+    if (int rc = attn_geometry_check(a)) return rc;
+    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out) return fail(GSASR_ERR_ARG, "null q, k, v, table, index or out pointer");
+    if (attn_bf_misaligned({a->q, a->k, a->v, a->out}, 2)) return fail(GSASR_ERR_ARG, "q, k, v and out must be 2-byte aligned");
+    const AttnArgsT<att_bf> A = attn_args<att_bf>(a);
+    const int nt = (a->nk + 15) / 16;
+    const bool tlds = attn_tlds(a), stats = a->stats != nullptr;
+    const size_t lds = attn_bf_fwd_lds(a->nk, tlds ? a->table_rows : 0);
+    const unsigned grid = (unsigned)(a->windows * a->heads);
+    const int waves = attn_waves(a->nq);
+    hipStream_t st = (hipStream_t)stream;
+#define ATT_FWD(T) (stats ? (tlds ? attn_launch(k_attn_fwd_bf<T, true, true, false>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd_bf<T, true, false, false>, grid, waves, lds, st, A)) \
+                          : (tlds ? attn_launch(k_attn_fwd_bf<T, false, true, false>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd_bf<T, false, false, false>, grid, waves, lds, st, A)))
+    if (nt <= 3) return ATT_FWD(3);
+    if (nt <= 9) return ATT_FWD(9);
+    return ATT_FWD(16);
+#undef ATT_FWD
+}
+
+int gsasr_window_attn_bf16_backward(const gsasr_window_attn_bf16 *a, void *stream) { return attn_backward<att_bf>(a, stream); }
+
+size_t gsasr_window_attn_rope_bf16_scratch_bytes(const gsasr_window_attn_rope_bf16 *a) { return attn_rope_scratch_bytes(a); }
+
+int gsasr_window_attn_rope_bf16_forward(const gsasr_window_attn_rope_bf16 *a, void *stream)
 {
     if (int rc = attn_rope_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->out || !a->stats || !a->grad_out || !a->cossin)
-        return fail(GSASR_ERR_ARG, "null q, k, v, out, stats, grad_out or cossin pointer");
-    if (a->g_angles && (!a->g_q || !a->g_k)) return fail(GSASR_ERR_ARG, "g_angles needs g_q and g_k (it is formed from them)");
-    if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin) || attn_misaligned(a->g_q) || attn_misaligned(a->g_k))
-        return fail(GSASR_ERR_ARG, "q, k, cossin, g_q and g_k must be 8-byte aligned");
-    const AttnArgs A = attn_rope_args(a);
-    if (a->g_angles && A.aslices > 1 && !a->scratch)
-        return fail(GSASR_ERR_ARG, "null scratch pointer (the angle gradient needs gsasr_window_attn_rope_scratch_bytes)");
+    if (!a->q || !a->k || !a->v || !a->angles || !a->out || !a->cossin) return fail(GSASR_ERR_ARG, "null q, k, v, angles, out or cossin pointer");
+    if (attn_bf_misaligned({a->q, a->k, a->v, a->out}, 4) || attn_misaligned(a->cossin))
+        return fail(GSASR_ERR_ARG, "q, k, v and out must be 4-byte aligned and cossin 8-byte aligned");
+    const AttnArgsT<att_bf> A = attn_rope_args<att_bf>(a);
+    const int nt = (a->nk + 15) / 16;
+    const bool stats = a->stats != nullptr;
+    const size_t lds = attn_bf_fwd_lds(a->nk, 0);
+    const unsigned grid = (unsigned)(a->windows * a->heads);
+    const int waves = attn_waves(a->nq);
     hipStream_t st = (hipStream_t)stream;
-    if (a->g_q) {
-        const size_t lds = (size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD * sizeof(float);
-        if (int rc = attn_launch(k_attn_bwd_q<0, false, true>, (unsigned)(a->windows * a->heads), attn_waves(a->nq), lds, st, A)) return rc;
-    }
-    if (a->g_k || a->g_v) {
-        const int nqp = (a->nq + 15) / 16 * 16;
-        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp) * sizeof(float);
-        if (int rc = attn_launch(k_attn_bwd_kv<false, true>, (unsigned)(a->windows * a->heads), attn_waves(a->nk), lds, st, A)) return rc;
-    }
-    if (a->g_angles) {
-        const unsigned blocks = (unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256);
-        hipLaunchKernelGGL(k_attn_angle_grad, dim3(blocks, (unsigned)A.aslices), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        if (A.aslices > 1) {
-            hipLaunchKernelGGL(k_attn_angle_sum, dim3(blocks), dim3(256), 0, st, A);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return GSASR_OK;
+    hipLaunchKernelGGL(k_attn_cossin<att_bf>, dim3((unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+#define ATT_FWD(T) (stats ? attn_launch(k_attn_fwd_bf<T, true, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd_bf<T, false, false, true>, grid, waves, lds, st, A))
+    if (nt <= 3) return ATT_FWD(3);
+    if (nt <= 9) return ATT_FWD(9);
+    return ATT_FWD(16);
+#undef ATT_FWD
 }
+
+int gsasr_window_attn_rope_bf16_backward(const gsasr_window_attn_rope_bf16 *a, void *stream) { return attn_rope_backward<att_bf>(a, stream); }
 
 }  // extern "C"

@@ -724,6 +724,66 @@ GSASR_API size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_ro
 GSASR_API int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *attn, void *stream);
 GSASR_API int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *attn, void *stream);
 
+/* The two window attentions with bf16 activations: what the decoder's Linears hand over under torch.autocast(dtype=bfloat16)
+ * (the AMP and UltraPerformance models).  Same formulas, layouts, limits and entry points as gsasr_window_attn and
+ * gsasr_window_attn_rope above; the descriptors have the same fields in the same order, with the eight activation pointers
+ * typed gsasr_bf16 (a bf16 is the upper half of the fp32 with the same value).  The numerical contract:
+ *
+ *   q, k, v, out, grad_out, g_q, g_k, g_v   bf16 in memory;  table, angles, stats, cossin, g_table, g_angles   fp32, as above
+ *   every product accumulates in fp32.  S = scale * (sum_c q[i, c] k[j, c]) (+ B_h[i, j], fp32, added to the finished score):
+ *   `scale` multiplies the fp32 score SUM, never an operand before it is rounded.  The softmax sees the whole row in fp32: one
+ *   maximum m, one sum l of the unrounded fp32 p = exp(S - m).  p is rounded to bf16 (nearest even) ONLY as the operand of
+ *   P v:  out = (sum_j bf16(p_j) v_j) / l, rounded to bf16 once at the store;  stats = m + log l in fp32.
+ *   Rotary variant: the rotation is evaluated in fp32 from the accurate cossin table, then R(q) and R(k) are rounded to bf16
+ *   (the reference's apply_rotary_emb_single rotates x.float() and returns type_as(x)); the backward recomputes S from the
+ *   same bf16-rounded rotated operands, so the statistic is of the forward's scores up to the fp32 summation order.
+ *   Backward: dS, dP and delta stay fp32 (the products run on the exact-fp32 matrix instruction on the widened operands);
+ *   delta is formed from the bf16 out that was stored; g_q, g_k, g_v are rounded to bf16 at the store; g_table and g_angles
+ *   are accumulated and stored in fp32 as above (g_angles from the stored bf16 g_q, g_k).
+ *   out, g_q, g_k, g_v and g_angles are written once by their owner, without atomics: two calls give the same bits.
+ *
+ * The forward runs on v_mfma_f32_16x16x32_bf16: one matrix instruction per 16 x 16 score tile.  Its loads are chosen by the
+ * alignment of a head's slice: 16 bytes at a time when head_dim % 8 == 0 and q, k, v are 16-byte aligned, 4 bytes for an even
+ * head_dim and 4-byte aligned q, k, v, else 2 bytes.
+ * GSASR_ERR_ARG as for the fp32 descriptors; in addition an activation pointer the call needs that is not 2-byte aligned
+ * (rotary variant: 4-byte, for the pair loads). */
+typedef unsigned short gsasr_bf16;
+typedef struct gsasr_window_attn_bf16 {
+    int windows, heads, nq, nk, head_dim, table_rows;
+    float scale;
+    unsigned flags;       /* 0 (none defined) */
+    const gsasr_bf16 *q, *k, *v;
+    const float *table;
+    const int *index;
+    gsasr_bf16 *out;      /* written by the forward, read by the backward */
+    float *stats;
+    const gsasr_bf16 *grad_out;
+    gsasr_bf16 *g_q, *g_k, *g_v;
+    float *g_table;
+    void *scratch;
+} gsasr_window_attn_bf16;
+GSASR_API size_t gsasr_window_attn_bf16_scratch_bytes(const gsasr_window_attn_bf16 *attn);   /* as gsasr_window_attn_scratch_bytes */
+GSASR_API int gsasr_window_attn_bf16_forward(const gsasr_window_attn_bf16 *attn, void *stream);
+GSASR_API int gsasr_window_attn_bf16_backward(const gsasr_window_attn_bf16 *attn, void *stream);
+
+typedef struct gsasr_window_attn_rope_bf16 {
+    int windows, heads, nq, nk, head_dim, angle_rows;
+    float scale;
+    unsigned flags;       /* 0 (none defined) */
+    const gsasr_bf16 *q, *k, *v;
+    const float *angles;
+    gsasr_bf16 *out;      /* written by the forward, read by the backward */
+    float *stats;
+    const gsasr_bf16 *grad_out;
+    gsasr_bf16 *g_q, *g_k, *g_v;
+    float *g_angles;
+    float *cossin;        /* 8-byte aligned */
+    void *scratch;
+} gsasr_window_attn_rope_bf16;
+GSASR_API size_t gsasr_window_attn_rope_bf16_scratch_bytes(const gsasr_window_attn_rope_bf16 *attn);   /* as gsasr_window_attn_rope_scratch_bytes */
+GSASR_API int gsasr_window_attn_rope_bf16_forward(const gsasr_window_attn_rope_bf16 *attn, void *stream);
+GSASR_API int gsasr_window_attn_rope_bf16_backward(const gsasr_window_attn_rope_bf16 *attn, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate

@@ -120,8 +120,10 @@ class _BiasedWindowAttention(nn.Module):
     def forward(self, xq, xk):
         b, nq, c = xq.shape
         h = self.heads
-        if self.attention == "hip":        # the fused op on the Linears' outputs as they come: no head split, no [b, h, nq, nk] scores
+        if self.attention in ("hip", "hip_bf16"):      # the fused op on the Linears' outputs as they come: no head split, no [b, h, nq, nk] scores
             from gsasr_amd.attention import window_attention
+            if self.attention == "hip_bf16":           # bf16 in, bf16 out (for a run under bf16 autocast; outside one, cast back)
+                return self.o(window_attention(self.q(xq), self.k(xk), self.v(xk), self.bias, self.index, compute="bf16").to(xq.dtype))
             return self.o(window_attention(self.q(xq), self.k(xk), self.v(xk), self.bias, self.index))
         q = self.q(xq).view(b, nq, h, c // h).transpose(1, 2)
         k = self.k(xk).view(b, -1, h, c // h).transpose(1, 2)
@@ -156,8 +158,10 @@ class _RotaryWindowAttention(nn.Module):
         b, nq, c = xq.shape
         h = self.num_heads
         angles = rope_angles(self.rope_freqs, self.rope_t_x, self.rope_t_y)    # [heads, n*n, d/2], fp32
-        if self.attention == "hip":
+        if self.attention in ("hip", "hip_bf16"):
             from gsasr_amd.attention import window_attention_rope
+            if self.attention == "hip_bf16":
+                return self.proj(window_attention_rope(self.qhead(xq), self.khead(xk), self.vhead(xk), angles, compute="bf16").to(xq.dtype))
             return self.proj(window_attention_rope(self.qhead(xq), self.khead(xk), self.vhead(xk), angles))
         q = self.qhead(xq).view(b, nq, h, c // h).transpose(1, 2)
         k = self.khead(xk).view(b, -1, h, c // h).transpose(1, 2)
@@ -231,7 +235,8 @@ class _SeedBlock(nn.Module):
 class Fea2GSDecoder(nn.Module):
     """[B,c,h,w] (h, w multiples of the window), scale[B] -> [B, 16 h w, 9]: the reference decoder's architecture (module
     docstring), one seed per LR pixel, 16 Gaussians per seed after the two pixel shuffles, raster order of the 4h x 4w grid.
-    `attention`: "torch" (F.scaled_dot_product_attention with the bias as mask, the default) | "hip" (gsasr_amd.window_attention);
+    `attention`: "torch" (F.scaled_dot_product_attention with the bias as mask, the default) | "hip" (gsasr_amd.window_attention) |
+    "hip_bf16" (the same op with compute="bf16": for a step under torch.autocast(dtype=bfloat16));
     `scale_attention`: "mha" (nn.MultiheadAttention over the repeated scale embedding, the default) | "constant"
     (gsasr_amd.attention.constant_key_attention).  Same parameters and state dict in every mode.
     `position`: "bias" (the learned relative-position bias of utils/fea2gs.py, the default) | "rope" (the RoPE decoder of
@@ -242,8 +247,8 @@ class Fea2GSDecoder(nn.Module):
     def __init__(self, inchannel=64, channel=180, heads=6, window=12, cross_layers=2, self_blocks=6, self_layers=6,
                  attention="torch", scale_attention="mha", position="bias"):
         super().__init__()
-        if attention not in ("torch", "hip") or scale_attention not in ("mha", "constant") or position not in ("bias", "rope"):
-            raise ValueError('attention must be "torch" or "hip", scale_attention "mha" or "constant", position "bias" or "rope"')
+        if attention not in ("torch", "hip", "hip_bf16") or scale_attention not in ("mha", "constant") or position not in ("bias", "rope"):
+            raise ValueError('attention must be "torch", "hip" or "hip_bf16", scale_attention "mha" or "constant", position "bias" or "rope"')
         mode = (attention, scale_attention, position)
         self.c, self.win = channel, window
         self.seed = nn.Parameter(torch.randn(window * window, channel))

@@ -5,6 +5,10 @@ the explicit torch expression, in fp32 and under bf16 autocast, and the decoder 
 (profiles/window_attention_rope.txt).
 
     python tools/window_attention_bench.py [--reps 9] [--iters 20] [--skip-decoder] [--skip-op] [--only-hip] [--skip-bias] [--skip-rope]
+    python tools/window_attention_bench.py --bf16 [--only-hip] [--skip-decoder]      # the bf16 mode alone (profiles/window_attention_bf16.txt)
+
+`--bf16`: both ops on bf16 q, k, v under bf16 autocast -- compute="bf16", the default call (fp32 kernels behind the cast to fp32)
+and torch's reference expression, interleaved; then the decoder step under autocast with attention "torch", "hip" and "hip_bf16".
 
 Protocol: one process; every variant warmed up first; then `reps` rounds in which the variants take turns (interleaved, so a
 drift of the clock hits all of them), each turn `iters` back-to-back calls between two events on the current stream; the
@@ -139,6 +143,68 @@ def rope_op_level(args, dev):
                                           form=name, **{k: round(x, 4) for k, x in r.items()})), flush=True)
 
 
+def bf16_op_level(args, dev):
+    """both ops on bf16 inputs under bf16 autocast: compute="bf16" / the default call / torch's reference expression"""
+    for kind, (W, n, H, d) in [("rope", s) for s in ROPE_SHAPES] + [("bias", s) for s in OP_SHAPES] + [("bias", (256, 144, 6, 32))]:
+        g = torch.Generator().manual_seed(0)
+        q, k, v, wgt = (torch.randn(W, n, H * d, generator=g).to(dev).bfloat16() for _ in range(4))
+        side = int(round(n ** 0.5))
+        t = torch.arange(n, dtype=torch.float32)
+        cy, cx = torch.div(t, side, rounding_mode="floor").long(), (t % side).long()
+        if kind == "rope":
+            freqs = torch.rand(2, H, d // 2, generator=g)
+            param = ((t % side)[None, :, None] * freqs[0][:, None, :] + torch.div(t, side, rounding_mode="floor")[None, :, None] * freqs[1][:, None, :]).to(dev)
+            tail, op, ref = (), window_attention_rope, rope_reference_form
+        else:
+            param = (0.5 * torch.randn((2 * side - 1) ** 2, H, generator=g)).to(dev)
+            tail = (((cy[:, None] - cy[None, :] + side - 1) * (2 * side - 1) + cx[:, None] - cx[None, :] + side - 1).to(dev),)
+            op, ref = window_attention, lambda a, b, c, tb, ix: sdpa_form(a, b, c, tb.to(a.dtype), ix)      # (the bias as a bf16 mask, as autocast hands it)
+        forms = {"hip_bf16": lambda *a: op(*a, compute="bf16"), "hip_default": op}
+        if not args.only_hip:
+            forms["torch_reference"] = ref
+        leaves = [x.clone().requires_grad_(True) for x in (q, k, v, param)]
+
+        def fwd(fn):
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                return fn(q, k, v, param, *tail)
+
+        def fwd_bwd(fn):
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                out = fn(*leaves, *tail)
+            torch.autograd.grad(out, leaves, wgt.to(out.dtype))
+
+        for what, run in (("forward", fwd), ("forward+backward", fwd_bwd)):
+            res = interleaved({name: (lambda f=fn: run(f)) for name, fn in forms.items()}, args.reps, args.iters)
+            for name, r in res.items():
+                print(json.dumps(dict(level="op", position=kind, precision="bf16 inputs, bf16 autocast", shape=dict(W=W, n=n, H=H, d=d), what=what,
+                                      form=name, **{k: round(x, 4) for k, x in r.items()})), flush=True)
+
+
+def bf16_decoder_level(args, dev, position):
+    """the decoder step under bf16 autocast: attention "torch", "hip" (fp32 kernels behind the cast) and "hip_bf16" """
+    import c5_models
+    torch.manual_seed(0)
+    extra = dict(position="rope", channel=192) if position == "rope" else {}
+    nets = {}
+    for name in ("torch", "hip", "hip_bf16"):
+        nets[name] = c5_models.Fea2GSDecoder(attention=name, scale_attention="constant", **extra).to(dev)
+        nets[name].load_state_dict(nets["torch"].state_dict())
+    feat = torch.randn(16, 64, 48, 48, device=dev)
+    scale = torch.full((16,), 4.0, device=dev)
+
+    def step(net):
+        for p in net.parameters():
+            p.grad = None
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            loss = net(feat, scale).float().square().mean()
+        loss.backward()
+
+    res = interleaved({name: (lambda m=net: step(m)) for name, net in nets.items()}, max(3, args.reps // 2), 2, warmup=2)
+    for name, r in res.items():
+        print(json.dumps(dict(level="decoder", position=position, precision="bf16 autocast", feat=[16, 64, 48, 48], what="forward+backward",
+                              mode=f"attention={name},scale_attention=constant", **{k: round(x, 3) for k, x in r.items()})), flush=True)
+
+
 def decoder_level(args, dev, position="bias"):
     import c5_models
     torch.manual_seed(0)
@@ -172,8 +238,16 @@ def main():
     ap.add_argument("--only-hip", action="store_true")
     ap.add_argument("--skip-bias", action="store_true", help="leave out the biased op and its decoder")
     ap.add_argument("--skip-rope", action="store_true", help="leave out the rotary op and its decoder")
+    ap.add_argument("--bf16", action="store_true", help="the bf16 mode alone: both ops and the decoder step under bf16 autocast")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.bf16:
+        if not args.skip_op:
+            bf16_op_level(args, dev)
+        if not args.skip_decoder and not args.only_hip:
+            for position in ("rope", "bias"):
+                bf16_decoder_level(args, dev, position)
+        return
     if not args.skip_bias and not args.skip_op:
         op_level(args, dev)
     if not args.skip_rope and not args.skip_op:
