@@ -320,7 +320,8 @@ class BandExchange:
       backward: the local backward writes `g_records` for all three parts; the two halo parts are sent
                 back (same batched call, reversed) and `merge` adds them into the owners' gradients.
 
-    Nothing here synchronises the host.  Two conditions make a step incomplete: more than `cap` Gaussians selected
+    Nothing here synchronises the host (but for "p2p" over gloo on device tensors, a functional configuration: `_host_side_p2p`).
+    Two conditions make a step incomplete: more than `cap` Gaussians selected
     for one side, or a footprint reaching beyond the adjacent band.  `splat_band_local` poisons its image and its
     gradient with a NaN (device-side, from `counts`) when that happens, so it cannot go unnoticed; `check()` reads
     `counts` (host sync) and raises with the numbers.
@@ -432,12 +433,25 @@ class BandExchange:
             if not hasattr(self, "_ops"):
                 self._ops = {}
             self._ops[key] = ops
+        if ops and self._host_side_p2p():
+            torch.cuda.current_stream(self.records.device).synchronize()
         reqs = dist.batch_isend_irecv(ops) if ops else []
         if async_op:
             return reqs
         for r in reqs:
             r.wait()
         return []
+
+    def _host_side_p2p(self) -> bool:
+        """gloo's send / recv know nothing of streams: they read and write a device tensor's memory from the host, at once (its
+        collectives stage device tensors behind an event of the current stream, and RCCL runs everything in stream order).
+        What the stream still has to do to the buffers -- `select` filling send_up / send_down, the backward writing the halo
+        gradients, the fill of a fresh exchange's `records` -- must then be done before the swap is issued: the functional
+        gloo runs pay one stream synchronisation per swap, the product transport none."""
+        hit = getattr(self, "_p2p_host", None)
+        if hit is None:
+            hit = self._p2p_host = bool(self.records.is_cuda and dist.get_backend(self.group) == "gloo")
+        return hit
 
     @staticmethod
     def _wait(handles) -> None:

@@ -1,6 +1,16 @@
 """Multi-process CPU tests (gloo, world_size 2 and 3) of the row-band shard's collective plumbing
-(gsasr_amd/shard.py).  The local rasterizer is the CPU oracle injected as a backend -- on GPU ranks the
-same code path runs the HIP backend over RCCL (covered by tests/test_hip_parity.py::test_row_band_*)."""
+(gsasr_amd/shard.py).  The local rasterizer is the CPU oracle injected as a backend, `select` and `merge` are Python
+stand-ins: what is covered HERE is the collective plumbing of the autograd Functions on CPU tensors, nothing of the GPU side.
+
+Where the GPU side is covered:
+  * the same Functions with HipBackend on 2 and 3 real ranks that share the GPU over gloo (the kernels in the flow that calls
+    them, the stream ordering around the asynchronous swaps, `_poison_if` on a device scalar, the all_to_all_single views of the
+    edge ranks, the in-place reduce_scatter_tensor, forward_packed_into(accumulate=True)), against the float64 oracle:
+    tests/test_shard_ranks_gpu.py;
+  * k_band_select and k_band_merge alone, and the emulated exchange against the oracle: tests/test_band_kernels_gpu.py;
+  * tests/test_hip_parity.py::test_row_band_* call HipBackend.forward / backward on bands in a loop: the band PLANS, neither
+    the Functions nor a process group;
+  * RCCL itself has only met a one-rank group (tests/test_bench_dist.py)."""
 import os
 import socket
 
