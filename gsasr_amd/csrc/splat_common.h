@@ -1137,6 +1137,26 @@ struct SegTable {
     __device__ __forceinline__ unsigned chunks() const { return (total + 63u) >> 6; }
 };
 
+// lane i reads lane i-N of its row of 16 (0 in front of the row's first lane); cf. dpp_row_shl
+template <int N>
+__device__ __forceinline__ unsigned row_shr_u32(unsigned v)
+{
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + N, 0xf, 0xf, true);
+}
+
+// The wave's lanes where p holds, as a mask, from the predicate itself (__ballot(int) goes through a 0 / 1 register: a select
+// and a compare per call; here a p that IS a compare costs nothing more, any other p still costs those two).  Call sites are
+// wave-uniform.
+__device__ __forceinline__ unsigned long long wave_ballot(bool p)
+{
+    return __builtin_amdgcn_ballot_w64(p);
+}
+// the bits of the wave-uniform mask m below the calling lane, counted (two instructions; no per-lane mask is kept for it)
+__device__ __forceinline__ unsigned lanes_below(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
 // (x0, x1, y0, y1): the rectangle, inclusive -- the workgroup's tile where a coarse pass follows, the wave's own sub-tile in the
 // one-level walks.  rx == 0: the large class alone (what a kernel that reads the plan's tile lists still has to scan).
 __device__ __forceinline__ SegTable seg_table(const Params &P, const PlanView &V, int x0, int x1, int y0, int y1, int rx, int ry, int lane)
@@ -1161,10 +1181,21 @@ __device__ __forceinline__ SegTable seg_table(const Params &P, const PlanView &V
     }
     ++T.nseg;
     T.len = send - T.sbeg;
-    unsigned pin = T.len;  // inclusive prefix sum of the segment lengths over the lanes
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)pin, o);
-        if (lane >= o) pin += v;
+    // Inclusive prefix sum of the segment lengths over the lanes.  Only the first nseg lanes hold a segment (the others hold
+    // length 0) and nseg is wave-uniform, so the scan stops at the first step that reaches past them.  Up to 16 segments (x4:
+    // 6-7) sit in one row of 16 lanes: there a step is one add that reads its operand through a DPP row shift; beyond that
+    // it is an LDS permute with its address arithmetic and a dependent LDS round trip.
+    unsigned pin = T.len;
+    if (T.nseg <= 16) {
+        pin += row_shr_u32<1>(pin);
+        pin += row_shr_u32<2>(pin);
+        if (T.nseg > 4) pin += row_shr_u32<4>(pin);
+        if (T.nseg > 8) pin += row_shr_u32<8>(pin);
+    } else {
+        for (int o = 1; o < T.nseg; o <<= 1) {
+            const unsigned v = (unsigned)__shfl_up((int)pin, o);
+            if (lane >= o) pin += v;
+        }
     }
     T.pin = pin;
     T.pex = pin - T.len;
@@ -1176,18 +1207,45 @@ __device__ __forceinline__ SegTable seg_table(const Params &P, const PlanView &V
 // the chunk (wave-uniform, advanced monotonically).  Returns 0xffffffff for lanes past the end.  A chunk overlaps one or two
 // segments at 16 Gaussians per cell and 3-5 when cells are sparse (x12 inference), so every chunk is full instead of one
 // mostly-empty chunk per segment.
-__device__ __forceinline__ unsigned fwd_candidate(unsigned c, int lane, const SegTable &T, int &r)
+//
+// SegCursor: the walk's place in the table, all wave-uniform (SGPRs): segment r and its flat range [p0, p1) and first candidate b,
+// carried from call to call -- lanes of the table are read only when r advances or a chunk reaches into further segments (a
+// segment's p0 is its predecessor's p1, so an advance reads two lanes).  Chunks must be asked for in ascending order.
+struct SegCursor {
+    int r;
+    unsigned p0, p1, b;
+};
+__device__ __forceinline__ SegCursor seg_cursor(const SegTable &T)
+{
+    return SegCursor{0, 0u, (unsigned)__builtin_amdgcn_readlane((int)T.pin, 0), (unsigned)__builtin_amdgcn_readlane((int)T.sbeg, 0)};
+}
+__device__ __forceinline__ unsigned fwd_candidate(unsigned c, int lane, const SegTable &T, SegCursor &C)
 {
     const unsigned q0 = c * 64u, q = q0 + (unsigned)lane;
-    while (r < T.nseg && (unsigned)__builtin_amdgcn_readlane((int)T.pin, r) <= q0) ++r;
+    while (C.p1 <= q0 && C.r + 1 < T.nseg) {    // (behind the last segment the cursor stays on it: no lane is inside then)
+        ++C.r;
+        C.p0 = C.p1;
+        C.p1 = (unsigned)__builtin_amdgcn_readlane((int)T.pin, C.r);
+        C.b = (unsigned)__builtin_amdgcn_readlane((int)T.sbeg, C.r);
+    }
     unsigned j = 0xffffffffu;
-    for (int rr = r; rr < T.nseg; ++rr) {
-        const unsigned p0 = (unsigned)__builtin_amdgcn_readlane((int)T.pex, rr);
-        if (p0 >= q0 + 64u) break;
+    if (q - C.p0 < C.p1 - C.p0) j = C.b + (q - C.p0);    // (q0 >= p0: the cursor never passes a chunk's first segment)
+    unsigned e = C.p1;
+    for (int rr = C.r + 1; rr < T.nseg && e < q0 + 64u; ++rr) {   // the segments that begin inside the chunk
         const unsigned p1 = (unsigned)__builtin_amdgcn_readlane((int)T.pin, rr);
         const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)T.sbeg, rr);
-        if (q >= p0 && q < p1) j = b + (q - p0);
+        if (q - e < p1 - e) j = b + (q - e);
+        e = p1;
     }
+    return j;
+}
+// (the same with the segment alone carried between calls: its three values are read from the table's lanes every time)
+__device__ __forceinline__ unsigned fwd_candidate(unsigned c, int lane, const SegTable &T, int &r)
+{
+    SegCursor C{r, (unsigned)__builtin_amdgcn_readlane((int)T.pex, r), (unsigned)__builtin_amdgcn_readlane((int)T.pin, r),
+                (unsigned)__builtin_amdgcn_readlane((int)T.sbeg, r)};
+    const unsigned j = fwd_candidate(c, lane, T, C);
+    r = C.r;
     return j;
 }
 
@@ -1202,33 +1260,35 @@ __device__ __forceinline__ unsigned fwd_candidate(unsigned c, int lane, const Se
 // the barrier that completes the list; the counter is double-buffered (the other one is reset here: nobody touches it before
 // the next barrier), and the CALLER closes the round with a barrier of its own before the list is rewritten.
 template <int WAVES, int CHUNKS>
-__device__ __forceinline__ unsigned coarse_pass(const PlanView &V, const SegTable &T, int &rseg, int bx0, int bx1, int by0, int by1,
+__device__ __forceinline__ unsigned coarse_pass(const PlanView &V, const SegTable &T, SegCursor &rseg, int bx0, int bx1, int by0, int by1,
                                                 unsigned base, unsigned round, int wv, int lane, unsigned *s_list, unsigned *s_cnt)
 {
     const unsigned nchunks = T.chunks();
-    const unsigned long long below = (1ull << lane) - 1ull;
     unsigned *cnt = s_cnt + (round & 1u);
     unsigned cj[CHUNKS];
     uint2 cw[CHUNKS];
+    // The wave's slots of the round are live up to a wave-uniform count (the last round is ragged: ~7 chunks for 16 slots at x4);
+    // a dead slot is left, not tested on a dummy box.  A lane behind the last candidate of a live slot holds no window: the
+    // test below asks for the candidate first, so nothing is made up for it.
 #pragma unroll
     for (int k = 0; k < CHUNKS; ++k) {
         const unsigned c = base + (unsigned)wv + (unsigned)(WAVES * k);
-        cj[k] = c < nchunks ? fwd_candidate(c, lane, T, rseg) : 0xffffffffu;
-        cw[k] = make_uint2(0x7fffu, 0x7fffu);
+        if (c >= nchunks) break;
+        cj[k] = fwd_candidate(c, lane, T, rseg);
         if (cj[k] != 0xffffffffu) cw[k] = V.win[cj[k]];
     }
 #pragma unroll
     for (int k = 0; k < CHUNKS; ++k) {
-        const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
-        const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
-        const bool hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
-        const unsigned long long m = __ballot(hit);
-        if (m) {
-            unsigned at = 0;
-            if (lane == 0) at = atomicAdd(cnt, (unsigned)__builtin_popcountll(m));
-            at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
-            if (hit) s_list[at + (unsigned)__builtin_popcountll(m & below)] = cj[k];
+        if (base + (unsigned)wv + (unsigned)(WAVES * k) >= nchunks) break;
+        bool hit = false;
+        if (cj[k] != 0xffffffffu) {
+            const int c0 = (int)(cw[k].x & 0x7fffu), c1 = (int)(cw[k].x >> 16);
+            const int r0 = (int)(cw[k].y & 0x7fffu), r1 = (int)(cw[k].y >> 16);
+            hit = (c0 <= bx1) & (c1 >= bx0) & (r0 <= by1) & (r1 >= by0);
         }
+        // One add per hit lane as written; as compiled (the wave-level atomic optimisation) the branch's own lane mask is the
+        // ballot: one lane adds their number, every hit lane takes the returned base plus the hit lanes below it.
+        if (hit) s_list[atomicAdd(cnt, 1u)] = cj[k];
     }
     __syncthreads();
     if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0u;
@@ -1236,15 +1296,18 @@ __device__ __forceinline__ unsigned coarse_pass(const PlanView &V, const SegTabl
 }
 
 // Fine test of one candidate against one sub-tile.  The candidate's window record (PlanView::bbox): the first 24 of its 32
-// bytes, or for "no candidate" (0xffffffff) the dead box c0 = r0 = 32767 > c1 = r1 = 0, which overlaps no sub-tile.
+// bytes.  "No candidate" (0xffffffff) is live == false: bb and bs then hold nothing and are not read -- the test answers with
+// the dead box c0 = r0 = 32767 > c1 = r1 = 0, which overlaps no sub-tile, instead of every walk step filling one in.
 struct FineBox {
     uint4 bb;
     uint2 bs;
+    bool live;
 };
 __device__ __forceinline__ FineBox fine_load(const uint4 *__restrict__ bbox, unsigned j)
 {
-    FineBox b{make_uint4(0x7fffu, 0x7fffu, 0u, 0u), make_uint2(0u, 0u)};
-    if (j != 0xffffffffu) {
+    FineBox b;
+    b.live = j != 0xffffffffu;
+    if (b.live) {
         b.bb = bbox[2 * (size_t)j];
         b.bs = *reinterpret_cast<const uint2 *>(bbox + 2 * (size_t)j + 1);
     }
@@ -1264,9 +1327,10 @@ struct FineHit {
 template <bool BOUNDED, int UNITS>
 __device__ __forceinline__ FineHit fine_test(const FineBox &b, const SubTile &S, int row0)
 {
+    FineHit h{false, false, 0x7fff, 0};
+    if (!b.live) return h;
     const uint4 bb = b.bb;
     const int c0 = (int)(bb.x & 0x7fffu), c1 = (int)(bb.x >> 16);
-    FineHit h;
     h.r0 = (int)(bb.y & 0x7fffu);
     h.r1 = (int)(bb.y >> 16);
     h.hit = (c0 <= S.x1) & (c1 >= S.x0) & (h.r0 <= S.y1) & (h.r1 >= S.y0);
@@ -1290,11 +1354,12 @@ __device__ __forceinline__ void survivor_walk(const uint4 *__restrict__ bbox, co
     unsigned j = start + (unsigned)lane < n ? s_list[start + lane] : 0xffffffffu;
     FineBox b = fine_load(bbox, j);
     for (unsigned q = start; q < n; q += stride) {
+        const FineHit h = fine_test<BOUNDED, UNITS>(b, S, row0);    // (b is spent: the next record is loaded in its place, not copied there)
         const unsigned nq = q + stride + (unsigned)lane;
         const unsigned nj = nq < n ? s_list[nq] : 0xffffffffu;
-        const FineBox nb = fine_load(bbox, nj);
-        body(j, fine_test<BOUNDED, UNITS>(b, S, row0));
-        j = nj; b = nb;
+        b = fine_load(bbox, nj);
+        body(j, h);
+        j = nj;
     }
 }
 

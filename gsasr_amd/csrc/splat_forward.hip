@@ -188,25 +188,31 @@ __device__ __forceinline__ void fwd_eval_lds_pairs(const float4 *__restrict__ st
 
 // One chunk of a wave's walk: compact the hits' records (ra, rb of the hit lanes; those that need the dmax test behind the
 // others) into the wave's LDS stage and evaluate them on the lane's two pixels from broadcast LDS reads.
+// (ra, rb are read on hit lanes only; the two lists' masks are one ballot each, split by scalar arithmetic, and a chunk
+// without tested hits -- wave-uniform -- takes no step of the second list's placement.)
 template <bool BOUNDED, bool PAIR>
-__device__ __forceinline__ void fwd_stage_eval(float4 *stage, bool hit, bool needs, const float4 ra, const float4 rb, int lane, float px,
+__device__ __forceinline__ void fwd_stage_eval(float4 *stage, bool hit, bool needs, const float4 &ra, const float4 &rb, int lane, float px,
                                                v2f py, float dmax, v2f &ar, v2f &ag, v2f &ab)
 {
-    const unsigned long long below = (1ull << lane) - 1ull;
 #ifdef FWD_EXP_NOEVAL   // what-if build (tools/whatif.sh): the records are found, fetched and staged, ONE per chunk is evaluated
-    const unsigned long long mall = __ballot(hit && !needs), m0 = mall & (0ull - mall), m1 = 0ull;    // (lowest set bit)
+    const unsigned long long mall = wave_ballot(hit && !needs), m0 = mall & (0ull - mall), m1 = 0ull;    // (lowest set bit)
     hit = hit && !needs && ((m0 >> lane) & 1ull) != 0ull;
 #else
-    const unsigned long long m0 = __ballot(hit && !needs), m1 = BOUNDED ? __ballot(hit && needs) : 0ull;
+    const unsigned long long mh = wave_ballot(hit), m1 = BOUNDED ? mh & wave_ballot(needs) : 0ull, m0 = mh & ~m1;
 #endif
     const int n0 = __builtin_popcountll(m0), n1 = __builtin_popcountll(m1);
     if (n0 + n1 == 0) return;
+    const bool any1 = BOUNDED && m1 != 0ull;     // wave-uniform
     if constexpr (PAIR) {
     const int b1 = (n0 + 1) & ~1;     // first slot of the tested list (the lists are padded to whole pairs)
     __builtin_amdgcn_wave_barrier();
     if (hit) {
-        const int r = needs ? __builtin_popcountll(m1 & below) : __builtin_popcountll(m0 & below);
-        const int slot = needs ? b1 + r : r;
+        needs = any1 && needs;
+        int r = (int)lanes_below(m0), slot = r;
+        if (needs) {
+            r = (int)lanes_below(m1);
+            slot = b1 + r;
+        }
         stage_put_pair(stage, slot, ra, rb);
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         if (((needs ? n1 : n0) & 1) && r == (needs ? n1 : n0) - 1) stage_put_pair(stage, slot + 1, z, z);   // the odd list's zero record
@@ -223,7 +229,8 @@ __device__ __forceinline__ void fwd_stage_eval(float4 *stage, bool hit, bool nee
     } else {
     __builtin_amdgcn_wave_barrier();
     if (hit) {
-        const int slot = needs ? n0 + __builtin_popcountll(m1 & below) : __builtin_popcountll(m0 & below);
+        int slot = (int)lanes_below(m0);
+        if (any1 && needs) slot = n0 + (int)lanes_below(m1);
         stage[2 * slot] = ra;
         stage[2 * slot + 1] = rb;
     }
@@ -233,10 +240,10 @@ __device__ __forceinline__ void fwd_stage_eval(float4 *stage, bool hit, bool nee
     }
 }
 
-// the 32-byte record of candidate j where it is a hit (zeros elsewhere): loaded only once the fine test has said so
+// the 32-byte record of candidate j where it is a hit: loaded only once the fine test has said so.  Elsewhere ra, rb are left as
+// they are -- only hit lanes write the stage (fwd_stage_eval), so no lane reads what was not loaded, and nothing is zeroed for it.
 __device__ __forceinline__ void fwd_record(const float4 *__restrict__ rec, unsigned j, bool hit, float4 &ra, float4 &rb)
 {
-    ra = rb = make_float4(0.f, 0.f, 0.f, 0.f);
     if (hit) {
         const float4 *src = rec + 2 * (size_t)j;
         ra = src[0];
@@ -267,7 +274,7 @@ __device__ __forceinline__ void fwd_tile(const Params &P, const PlanView &V, int
     // part, part+nparts, ...), software-pipelined: the window record of the NEXT chunk is in flight while
     // the hits of the current one are evaluated.
     const unsigned nchunks = T.chunks();
-    int rseg = 0;
+    SegCursor rseg = seg_cursor(T);
     unsigned c = part;
     unsigned j = c < nchunks ? fwd_candidate(c, lane, T, rseg) : 0xffffffffu;
     FineBox b = fine_load(V.bbox, j);
@@ -311,7 +318,7 @@ __device__ __forceinline__ void fwd_block(const Params &P, const PlanView &V, in
     const SubTile S{sx0, sx1, by0, by1, sx0 >> SUBX_SHIFT, (by0 - P.row0) >> SUBY_SHIFT};
     const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
     const unsigned nchunks = T.chunks();
-    int rseg = 0;
+    SegCursor rseg = seg_cursor(T);
 
     for (unsigned base = 0, round = 0; base < nchunks; base += 4u * PARTS * COARSE_CHUNKS, ++round) {
         const unsigned n = coarse_pass<4 * PARTS, COARSE_CHUNKS>(V, T, rseg, bx0, bx1, by0, by1, base, round, wv, lane, s_list, s_cnt);
@@ -546,7 +553,7 @@ __device__ __forceinline__ int wide_class(const FineHit &h, int sy0)
 // stage the records (ra, rb) of one chunk's hits sorted by class and evaluate them: a window that ends in the upper half
 // costs one row part, not two (fwd_eval_lds16)
 template <bool BOUNDED>
-__device__ __forceinline__ void wide_stage_eval(float4 *stage, int cls, const float4 ra, const float4 rb, float px, v2f pyA, v2f pyB,
+__device__ __forceinline__ void wide_stage_eval(float4 *stage, int cls, const float4 &ra, const float4 &rb, float px, v2f pyA, v2f pyB,
                                                 float dmax, v2f (&acc)[6], int lane)
 {
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -644,7 +651,7 @@ __device__ __forceinline__ void fwd_eval_lds_pairs1(const float4 *__restrict__ s
 // one chunk of a wave's walk (cf. fwd_stage_eval, PAIR): the hits' records go to the wave's stage as interleaved pairs, the
 // tested ones behind the others, each list padded to whole pairs with a zero record
 template <bool BOUNDED>
-__device__ __forceinline__ void fwd_stage_eval1(float4 *stage, bool hit, bool needs, const float4 ra, const float4 rb, int lane, float px,
+__device__ __forceinline__ void fwd_stage_eval1(float4 *stage, bool hit, bool needs, const float4 &ra, const float4 &rb, int lane, float px,
                                                 float py, float dmax, v2f (&acc)[3])
 {
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -690,7 +697,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (by0 - P.row0) >> SUBY_SHIFT};
     const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
     const unsigned nchunks = T.chunks();
-    int rseg = 0;
+    SegCursor rseg = seg_cursor(T);
     v2f acc[3] = {(v2f){0.f, 0.f}, (v2f){0.f, 0.f}, (v2f){0.f, 0.f}};
 
     for (unsigned base = 0, round = 0; base < nchunks; base += (unsigned)(FW * COARSE_CHUNKS), ++round) {
@@ -739,7 +746,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (sy0 - P.row0) >> SUBY_SHIFT};
     const SegTable T = seg_table(P, V, bx0, bx1, by0, by1, (int)V.hdr[8], (int)V.hdr[9], lane);
     const unsigned nchunks = T.chunks();
-    int rseg = 0;
+    SegCursor rseg = seg_cursor(T);
     v2f acc[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) acc[k] = (v2f){0.f, 0.f};
@@ -880,7 +887,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     auto search = [&](bool large_only) {
         const SubTile S{sx0, sx1, sy0, sy1, sx0 >> SUBX_SHIFT, (sy0 - P.row0) >> SUBY_SHIFT};
         const SegTable T = seg_table(P, V, sx0, sx1, sy0, sy1, large_only ? 0 : (int)V.hdr[8], large_only ? 0 : (int)V.hdr[9], lane);
-        int rseg = 0;
+        SegCursor rseg = seg_cursor(T);
         for (unsigned c = 0; c < T.chunks(); ++c) {
             const unsigned j = fwd_candidate(c, lane, T, rseg);
             const FineHit h = fine_test<BOUNDED, 2>(fine_load(V.bbox, j), S, P.row0);
