@@ -235,7 +235,8 @@ struct Layout {
     int part_k;
     size_t count_bytes;  // one array of per-cell counters + extent groups (there are two, used alternately: GSASR_FLAG_PARITY)
     size_t ext_off_words; // where the extent groups start inside such an array
-    size_t dead_off_words; // ... and the counters of the dead sub-classes, ONE PER 64-BYTE LINE (count_at)
+    size_t dead_off_words; // ... and the counters of the dead sub-classes, ONE PER 64-BYTE LINE (count_at); word 1 of each line: the
+                           // largest cell count seen by the k_classify blocks that map to it (k_bin's fused scan takes the maximum)
     int ext_groups;
     size_t total;
     int ncx, ncy, ncells;

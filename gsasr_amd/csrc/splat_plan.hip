@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
                                                   float *__restrict__ o_sig, float *__restrict__ o_xy, float *__restrict__ o_col,
                                                   ViewArg VW)
 {
-    __shared__ unsigned s_rx[4], s_ry[4];
+    __shared__ unsigned s_rx[4], s_ry[4], s_mc[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     // the counters of the NEXT plan on this workspace (the other parity) are zeroed on the side
@@ -112,7 +112,10 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
     // Rank of the Gaussian inside its cell, with ONE returning atomic per (wave, distinct key): decoder
     // output is in raster order, so the 64 Gaussians of a wave fall into a handful of cells (often one,
     // at 16 Gaussians per LR pixel) and per-lane atomics on the same word would serialise at ~10 ns each.
-    unsigned rank = 0;
+    // The largest `base + group size` over the normal-class groups is the largest final count of a cell: a cell's last
+    // atomic returns its count less that group.  One atomicMax per block publishes it (below) and gives k_bin's fused scan
+    // the cutoff's input without a reduction of the histogram.
+    unsigned rank = 0, cmax = 0;
     {
         // match-any without atomics: every lane learns the lane-mask of its key's group ...
         unsigned long long mine = 0ull, todo = __ballot(key != 0xffffffffu);
@@ -125,10 +128,12 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
         // ... then ALL group leaders issue their returning atomic in one instruction (one round trip)
         if (mine) {
             const int leader = __builtin_ctzll(mine);
+            const unsigned cnt = (unsigned)__builtin_popcountll(mine);
             unsigned base = 0;
-            if (lane == leader) base = atomicAdd(&V.cell_count[count_index((int)key, P.ncells, P.dead_off)], (unsigned)__builtin_popcountll(mine));
+            if (lane == leader) base = atomicAdd(&V.cell_count[count_index((int)key, P.ncells, P.dead_off)], cnt);
             base = (unsigned)__shfl((int)base, leader);
             rank = base + (unsigned)__builtin_popcountll(mine & ((1ull << lane) - 1ull));
+            if (key < (unsigned)P.ncells) cmax = base + cnt;
         }
     }
     if (i < P.s) {
@@ -139,7 +144,8 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
     // a single word for all blocks serialises at ~12 ns per atomic; the readers then reduce groups, not blocks)
     rx = wave_max_u32(rx);
     ry = wave_max_u32(ry);
-    if (lane == 0) { s_rx[threadIdx.x >> 6] = rx; s_ry[threadIdx.x >> 6] = ry; }
+    cmax = wave_max_u32(cmax);
+    if (lane == 0) { s_rx[threadIdx.x >> 6] = rx; s_ry[threadIdx.x >> 6] = ry; s_mc[threadIdx.x >> 6] = cmax; }
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned mx = max(max(s_rx[0], s_rx[1]), max(s_rx[2], s_rx[3])), my = max(max(s_ry[0], s_ry[1]), max(s_ry[2], s_ry[3]));
@@ -147,6 +153,11 @@ __global__ __launch_bounds__(256) void k_classify(Params P, const float *__restr
             atomicMax(&V.blockmax[16 * (blockIdx.x >> 5) + 0], mx);
             atomicMax(&V.blockmax[16 * (blockIdx.x >> 5) + 1], my);
         }
+        // The largest cell count goes to word 1 of a dead sub-class' line, block b to line b % NDEAD (zeroed for the next plan
+        // with the rest of the counter array): on word 2 of the extent line, a third atomic on a line that takes two from each of
+        // 32 blocks, k_classify measured +0.2 us (profiles/plan_chain_ab.txt).  k_bin's lanes read the 128 words back.
+        const unsigned mc = max(max(s_mc[0], s_mc[1]), max(s_mc[2], s_mc[3]));
+        if (mc) atomicMax(&V.cell_count[P.dead_off + (blockIdx.x & (NDEAD - 1)) * 16 + 1], mc);
     }
 }
 
@@ -454,6 +465,7 @@ __device__ __forceinline__ void tl_emit(const Params &P, const PlanView &V, bool
 // the cell histogram in LDS itself (16 counts per thread) instead of waiting for a separate one-block scan
 // kernel -- one launch less on a latency-bound plan; block 0 publishes cell_start[] and the header.
 constexpr int FUSED_PER_THREAD = 17, FUSED_CELLS = 256 * FUSED_PER_THREAD;
+constexpr int FUSED_GROUPS = 128;   // extent groups a wave of the fused scan reduces, two per lane (FUSED_MAX_BLOCKS makes 48)
 static_assert(FUSED_CELLS == FUSED_CELLS_HOST, "make_params decides with FUSED_CELLS_HOST which plans run a scan kernel");
 
 // TLH: the plan's tile lists -- 0 none, else log2 of the tile height (4 / 5)
@@ -470,24 +482,13 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
     // of its dependent chain, not its instruction count.
     const bool valid = i < P.s;
     unsigned c[FUSED_SCAN ? FUSED_PER_THREAD : 1];   // this thread's share of the per-cell counters (scan below)
-    if (FUSED_SCAN) {
-        // (measured in round 5 and dropped: requesting them coalesced -- counter k * 256 + t by thread t -- and transposing
-        // through LDS costs a barrier more than the 60 cache lines per load it saves: k_bin 9.97 us against 9.4-9.6)
-#pragma unroll
-        for (int k = 0; k < FUSED_PER_THREAD; ++k) {
-            const int q = (int)threadIdx.x * FUSED_PER_THREAD + k;
-            c[k] = q < P.ncells + 1 + NDEAD ? V.cell_count[count_index(q, P.ncells, P.dead_off)] : 0u;
-        }
-    }
     const bool adapting = P.adapt_cells > 0.f || P.adapt_ring != 0;
-    const unsigned nlarge = FUSED_SCAN && adapting ? V.cell_count[P.ncells] : 0u;
+    // Load order: the memory counter retires loads in order, so whatever is issued in front of the Gaussian's inputs is waited
+    // for with them.  First what the windows need -- key, rank, the inputs, then the cutoff's inputs (k_classify's group lines:
+    // extents and the largest cell count; the near-dead and large counters) --, the histogram counters after them: only the scan
+    // at the end needs those, and they land under the window arithmetic.  (In the ISA: the cutoff waits with vmcnt(17), the
+    // seventeen counters still in flight, and nothing waits for them before the scan.)
     unsigned key = 0u, rnk = 0u;
-    float4 recA = make_float4(0.f, 0.f, 0.f, 0.f), recB = recA, finA = recA, finB = recA;
-    uint4 bb = make_uint4(0u, 0u, 0u, 0u), bc = bb;
-    uint4 qs = make_uint4(0u, 0xffffffffu, 0u, 0xffffffffu);   // quadrant-row spans: every column unless computed below
-    bool fine8 = false;                                        // ... computed: the tile lists' masks are cut from them
-    bool large = false;
-    unsigned fb_rx = 0u, fb_ry = 0u;
     float sx = 0.f, sy = 0.f, rho = 0.f, x = 0.f, y = 0.f, col0 = 0.f, col1 = 0.f, col2 = 0.f;
     if (valid) {
         key = V.key[i];
@@ -497,47 +498,50 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
         x = coords[i2 + 0]; y = coords[i2 + 1];
         col0 = colors[i3 + 0]; col1 = colors[i3 + 1]; col2 = colors[i3 + 2];
     }
-    // The cutoff the windows are built with (adapt_kcut): from the largest cell count -- every block reduces the histogram it
-    // holds anyway (FUSED_SCAN), or reads what the scan kernels left in the header.
+    unsigned g_mc = 0u, g_mc2 = 0u, g_nn = 0u, nlarge = 0u;
+    uint2 ga = make_uint2(0u, 0u), gb = ga;
+    if constexpr (FUSED_SCAN) {
+        // Straight-line, nothing predicated (a lane past the last group or class reads the last one again: a maximum does not
+        // mind, a counter is zeroed where it is used): behind a branch the wait counter's bookkeeping gives up the order, and
+        // every later wait becomes a wait for ALL loads in flight.  Lane k takes groups k and k + 64 (the fused scan is launched
+        // for at most FUSED_GROUPS groups), every wave the same: no LDS, no barrier.
+        static_assert(NDEAD - NDEAD_NEAR == 64, "one near-dead counter per lane");
+        const int ln = (int)threadIdx.x & 63;
+        ga = *reinterpret_cast<const uint2 *>(V.blockmax + 16 * min(ln, nblk - 1));
+        gb = *reinterpret_cast<const uint2 *>(V.blockmax + 16 * min(ln + 64, nblk - 1));
+        {   // the largest cell count: k_classify's blocks raise word 1 of the dead sub-classes' lines, block b line b % NDEAD
+            const uint2 n2 = *reinterpret_cast<const uint2 *>(V.cell_count + P.dead_off + (NDEAD_NEAR + ln) * 16);
+            g_nn = n2.x;
+            g_mc = n2.y;
+            g_mc2 = V.cell_count[P.dead_off + ln * 16 + 1];
+        }
+        nlarge = V.cell_count[P.ncells];
+        // (measured in round 5 and dropped: requesting them coalesced -- counter k * 256 + t by thread t -- and transposing
+        // through LDS costs a barrier more than the 60 cache lines per load it saves: k_bin 9.97 us against 9.4-9.6)
+#pragma unroll
+        for (int k = 0; k < FUSED_PER_THREAD; ++k) {
+            const int q = min((int)threadIdx.x * FUSED_PER_THREAD + k, P.ncells + NDEAD);
+            c[k] = V.cell_count[count_index(q, P.ncells, P.dead_off)];
+        }
+        __builtin_amdgcn_sched_barrier(0);   // (the uses stay behind the loads)
+    }
+    float4 recA = make_float4(0.f, 0.f, 0.f, 0.f), recB = recA, finA = recA, finB = recA;
+    uint4 bb = make_uint4(0u, 0u, 0u, 0u), bc = bb;
+    uint4 qs = make_uint4(0u, 0xffffffffu, 0u, 0xffffffffu);   // quadrant-row spans: every column unless computed below
+    bool fine8 = false;                                        // ... computed: the tile lists' masks are cut from them
+    bool large = false;
+    unsigned fb_rx = 0u, fb_ry = 0u;
+    // The cutoff the windows are built with (adapt_kcut): from the largest cell count and the class' largest extents -- what
+    // k_classify left in its group lines, reduced by every wave for itself (FUSED_SCAN), or what the scan kernels left in the header.
     float kc = P.kcut, kc_tau = 0.f;
     unsigned kc_K = 0u, kc_mc = 0u, kc_nn = 0u;
     if constexpr (FUSED_SCAN) {
         if (adapting) {
-            // block-wide: the largest cell count, the near-dead count (both from the histogram this block holds anyway) and the
-            // class' largest extent (every block reduces k_classify's per-block maxima: block 0 alone publishes the header
-            // further down, too late for the windows)
-            unsigned mc = 0u, nn = 0u, ext = 0u, eyt = 0u;
-#pragma unroll
-            for (int k = 0; k < FUSED_PER_THREAD; ++k) {
-                const int q = (int)threadIdx.x * FUSED_PER_THREAD + k;
-                mc = q < P.ncells ? max(mc, c[k]) : mc;
-                nn += q >= P.ncells + 1 + NDEAD_NEAR ? c[k] : 0u;      // (c[k] = 0 past the last class)
-            }
-            if (P.adapt_ring) {
-                for (int k = (int)threadIdx.x; k < nblk; k += 256) {
-                    ext = max(ext, V.blockmax[16 * k]);
-                    eyt = max(eyt, V.blockmax[16 * k + 1]);
-                }
-            }
-            mc = wave_max_u32(mc);
-            ext = wave_max_u32(ext);
-            eyt = wave_max_u32(eyt);
-            nn = wave_add_u32(nn);
-            if ((threadIdx.x & 63) == 0) {
-                s_part[threadIdx.x >> 6] = mc;
-                s_part[4 + (threadIdx.x >> 6)] = nn;
-                s_part[8 + (threadIdx.x >> 6)] = ext;
-                s_part[12 + (threadIdx.x >> 6)] = eyt;
-            }
-            __syncthreads();
-            mc = max(max(s_part[0], s_part[1]), max(s_part[2], s_part[3]));
-            nn = (s_part[4] + s_part[5]) + (s_part[6] + s_part[7]);
-            ext = max(max(s_part[8], s_part[9]), max(s_part[10], s_part[11]));
-            eyt = max(max(s_part[12], s_part[13]), max(s_part[14], s_part[15]));
-            __syncthreads();   // (s_part is reused by the scan below)
-            kc = adapt_kcut(P, mc, nlarge, nn, ext, eyt, kc_tau, kc_K);
-            kc_mc = mc;
-            kc_nn = nn;
+            kc_mc = wave_max_u32(max(g_mc, g_mc2));
+            kc_nn = wave_add_u32(g_nn);
+            const unsigned ext = wave_max_u32(max(ga.x, gb.x)), eyt = wave_max_u32(max(ga.y, gb.y));
+            // (the ring bound alone takes the extents)
+            kc = adapt_kcut(P, kc_mc, nlarge, kc_nn, P.adapt_ring ? ext : 0u, P.adapt_ring ? eyt : 0u, kc_tau, kc_K);
         } else {
             kc_tau = 0.5f * P.kcut * P.kcut;
         }
@@ -725,6 +729,8 @@ __global__ __launch_bounds__(256) void k_bin(Params P, const float *__restrict__
         const int b0 = t * FUSED_PER_THREAD;
         unsigned sum = 0;
 #pragma unroll
+        for (int k = 0; k < FUSED_PER_THREAD; ++k) c[k] = b0 + k < ncls ? c[k] : 0u;      // (loaded unpredicated: see the head)
+#pragma unroll
         for (int k = 0; k < FUSED_PER_THREAD; ++k) sum += c[k];
         // block scan of the 256 partial sums: inside the waves with shuffles, across the four waves through LDS
         // (one barrier instead of the sixteen of a Hillis-Steele loop over s_part)
@@ -858,7 +864,7 @@ int plan_impl(const float *sigmas, const float *coords, const float *colors, con
     const int ncls = L.ncells + 1 + NDEAD;
     const unsigned nbin = (unsigned)((dims->s + 255) / 256);
     static const int fused_max_blocks = dev_switch("GSASR_SPLAT_FUSED_MAX") ? atoi(dev_switch("GSASR_SPLAT_FUSED_MAX")) : FUSED_MAX_BLOCKS;
-    if (ncls <= FUSED_CELLS && dims->s > 0 && (int)nbin <= fused_max_blocks) {
+    if (ncls <= FUSED_CELLS && dims->s > 0 && (int)nbin <= fused_max_blocks && L.ext_groups <= FUSED_GROUPS) {
         // small grid, not too many blocks: k_bin rebuilds the scan per block (no separate scan launch)
 #define GSASR_BIN_V(F, ISVIEW) do { \
         const int tlh = P.tl_hlog; \
