@@ -1260,64 +1260,6 @@ def _chk_act(t: torch.Tensor, name: str, bf16: bool) -> int:
     return t.data_ptr()
 
 
-def _attn_fn(stem: str, bf16: bool, what: str) -> str:
-    return f"{stem}_bf16_{what}" if bf16 else f"{stem}_{what}"
-
-
-def _window_attn(q, k, v, table, index, scale: float):
-    """the descriptor of the call; bf16 activations (`q`'s dtype) select gsasr_window_attn_bf16"""
-    bf16 = q.dtype == torch.bfloat16
-    for t, name in ((q, "q"), (k, "k"), (v, "v")):
-        _chk_act(t, name, bf16)
-    _chk(table, "bias_table")
-    if index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous():
-        raise RuntimeError("bias_index must be a contiguous int32 CUDA tensor")
-    heads = int(table.shape[1])
-    d = make_window_attn(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, table.shape[0], scale, bf16)
-    d.q, d.k, d.v, d.table, d.index = q.data_ptr(), k.data_ptr(), v.data_ptr(), table.data_ptr(), index.data_ptr()
-    return d
-
-
-def window_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table: torch.Tensor, index: torch.Tensor, scale: float,
-                        want_stats: bool = True):
-    """gsasr_window_attn_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `table` `[T,H]` fp32 contiguous, `index` int32
-    `[nq,nk]` (validated by the caller) -> (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None).  bf16 `q`, `k`, `v`:
-    gsasr_window_attn_bf16_forward, `out` bf16"""
-    d = _window_attn(q, k, v, table, index, scale)
-    fn = _attn_fn("gsasr_window_attn", q.dtype == torch.bfloat16, "forward")
-    dev = q.device
-    with _on(dev):
-        out = torch.empty_like(q)
-        stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
-        d.out, d.stats = out.data_ptr(), None if stats is None else stats.data_ptr()
-        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
-    return out, stats
-
-
-def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_out, need=(True, True, True, True)):
-    """gsasr_window_attn_backward (bf16 activations: gsasr_window_attn_bf16_backward) -> (g_q, g_k, g_v, g_table), None where
-    `need` is False"""
-    d = _window_attn(q, k, v, table, index, scale)
-    bf16 = q.dtype == torch.bfloat16
-    fn_bytes, fn = _attn_fn("gsasr_window_attn", bf16, "scratch_bytes"), _attn_fn("gsasr_window_attn", bf16, "backward")
-    _chk_act(out, "out", bf16), _chk(stats, "stats"), _chk_act(grad_out, "grad_out", bf16)
-    if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq):
-        raise RuntimeError("out / grad_out must have q's shape and stats [W,H,nq]")
-    dev = q.device
-    with _on(dev):
-        grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, table), need)]
-        d.out, d.stats, d.grad_out = out.data_ptr(), stats.data_ptr(), grad_out.data_ptr()
-        d.g_q, d.g_k, d.g_v, d.g_table = [None if g is None else g.data_ptr() for g in grads]
-        n = int(getattr(lib(), fn_bytes)(ctypes.byref(d)))
-        if n == 0:
-            check(-1, fn_bytes)
-        scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
-        d.scratch = scratch.data_ptr()
-        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
-    return tuple(grads)
-
-
-# ---- the decoder's window attention with a rotary embedding (include/gsasr_splat.h: gsasr_window_attn_rope) -----
 def make_window_attn_rope(windows: int, heads: int, nq: int, nk: int, head_dim: int, angle_rows: int, scale: float, bf16: bool = False):
     """a gsasr_window_attn_rope (`bf16`: gsasr_window_attn_rope_bf16) descriptor without pointers"""
     d = (WindowAttnRopeBf16 if bf16 else WindowAttnRope)(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(angle_rows))
@@ -1325,56 +1267,107 @@ def make_window_attn_rope(windows: int, heads: int, nq: int, nk: int, head_dim: 
     return d
 
 
-def _window_attn_rope(q, k, v, angles, scale: float):
-    """the descriptor of the call; bf16 activations (`q`'s dtype) select gsasr_window_attn_rope_bf16"""
+# (rope, bf16) -> the family's entry points
+_ATTN_FNS = {(rope, bf16): {what: f"gsasr_window_attn{'_rope' if rope else ''}{'_bf16' if bf16 else ''}_{what}" for what in ("forward", "backward", "scratch_bytes")}
+             for rope in (False, True) for bf16 in (False, True)}
+
+
+def _attn_desc(q, k, v, side, rope: bool, scale: float):
+    """the descriptor of a call with q, k, v and `side` (the bias table `[T,H]`, or with `rope` the angles `[H,N,d/2]`) filled in,
+    and the names of its entry points; bf16 activations (`q`'s dtype) select the bf16 family"""
     bf16 = q.dtype == torch.bfloat16
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         _chk_act(t, name, bf16)
-    _chk(angles, "angles")
-    heads = int(angles.shape[0])
-    d = make_window_attn_rope(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, angles.shape[1], scale, bf16)
-    d.q, d.k, d.v, d.angles = q.data_ptr(), k.data_ptr(), v.data_ptr(), angles.data_ptr()
-    return d
+    if rope:
+        heads = int(side.shape[0])
+        d = make_window_attn_rope(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, side.shape[1], scale, bf16)
+        d.angles = _chk(side, "angles")
+    else:
+        heads = int(side.shape[1])
+        d = make_window_attn(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, side.shape[0], scale, bf16)
+        d.table = _chk(side, "bias_table")
+    d.q, d.k, d.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
+    return d, _ATTN_FNS[rope, bf16]
 
 
-def window_attn_rope_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, angles: torch.Tensor, scale: float, want_stats: bool = True):
-    """gsasr_window_attn_rope_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `angles` `[H,N,d/2]` fp32 contiguous ->
-    (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None, the (cos, sin) table `[H,N,d/2,2]` the backward reads).  bf16
-    `q`, `k`, `v`: gsasr_window_attn_rope_bf16_forward, `out` bf16"""
-    d = _window_attn_rope(q, k, v, angles, scale)
-    fn = _attn_fn("gsasr_window_attn_rope", q.dtype == torch.bfloat16, "forward")
+def _attn_forward(d, fns, q, want_stats: bool):
+    """`out` and (if wanted) the rows' log-sum-exp allocated and the forward called -> (out, stats or None)"""
     dev = q.device
     with _on(dev):
         out = torch.empty_like(q)
         stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
-        cossin = torch.empty(*angles.shape, 2, dtype=torch.float32, device=dev)
-        d.out, d.stats, d.cossin = out.data_ptr(), None if stats is None else stats.data_ptr(), cossin.data_ptr()
-        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
-    return out, stats, cossin
+        d.out, d.stats = out.data_ptr(), None if stats is None else stats.data_ptr()
+        check(getattr(lib(), fns["forward"])(ctypes.byref(d), _stream(dev)), fns["forward"])
+    return out, stats
+
+
+def _attn_backward(d, fns, q, out, stats, grad_out, **grads):
+    """out, stats and grad_out checked, the gradient pointers set (`grads`: field -> tensor or None), the scratch asked for
+    (0: the descriptor's error is raised) and allocated, the backward called"""
+    bf16 = q.dtype == torch.bfloat16
+    _chk_act(out, "out", bf16), _chk(stats, "stats"), _chk_act(grad_out, "grad_out", bf16)
+    if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq):
+        raise RuntimeError("out / grad_out must have q's shape and stats [W,H,nq]")
+    dev = q.device
+    with _on(dev):
+        d.out, d.stats, d.grad_out = out.data_ptr(), stats.data_ptr(), grad_out.data_ptr()
+        for field, g in grads.items():
+            setattr(d, field, None if g is None else g.data_ptr())
+        n = int(getattr(lib(), fns["scratch_bytes"])(ctypes.byref(d)))
+        if n == 0:
+            check(-1, fns["scratch_bytes"])
+        scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        d.scratch = scratch.data_ptr()
+        check(getattr(lib(), fns["backward"])(ctypes.byref(d), _stream(dev)), fns["backward"])
+
+
+def _attn_index(d, index):
+    if index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous():
+        raise RuntimeError("bias_index must be a contiguous int32 CUDA tensor")
+    d.index = index.data_ptr()
+
+
+def window_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table: torch.Tensor, index: torch.Tensor, scale: float,
+                        want_stats: bool = True):
+    """gsasr_window_attn_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `table` `[T,H]` fp32 contiguous, `index` int32
+    `[nq,nk]` (validated by the caller) -> (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None).  bf16 `q`, `k`, `v`:
+    gsasr_window_attn_bf16_forward, `out` bf16"""
+    d, fns = _attn_desc(q, k, v, table, False, scale)
+    _attn_index(d, index)
+    return _attn_forward(d, fns, q, want_stats)
+
+
+def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_out, need=(True, True, True, True)):
+    """gsasr_window_attn_backward (bf16 activations: gsasr_window_attn_bf16_backward) -> (g_q, g_k, g_v, g_table), None where
+    `need` is False"""
+    d, fns = _attn_desc(q, k, v, table, False, scale)
+    _attn_index(d, index)
+    grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, table), need)]
+    _attn_backward(d, fns, q, out, stats, grad_out, **dict(zip(("g_q", "g_k", "g_v", "g_table"), grads)))
+    return tuple(grads)
+
+
+# ---- the decoder's window attention with a rotary embedding (include/gsasr_splat.h: gsasr_window_attn_rope) -----
+def window_attn_rope_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, angles: torch.Tensor, scale: float, want_stats: bool = True):
+    """gsasr_window_attn_rope_forward: `q` `[W,nq,H*d]`, `k`, `v` `[W,nk,H*d]`, `angles` `[H,N,d/2]` fp32 contiguous ->
+    (out `[W,nq,H*d]`, the rows' log-sum-exp `[W,H,nq]` or None, the (cos, sin) table `[H,N,d/2,2]` the backward reads).  bf16
+    `q`, `k`, `v`: gsasr_window_attn_rope_bf16_forward, `out` bf16"""
+    d, fns = _attn_desc(q, k, v, angles, True, scale)
+    cossin = torch.empty(*angles.shape, 2, dtype=torch.float32, device=q.device)
+    d.cossin = cossin.data_ptr()
+    return (*_attn_forward(d, fns, q, want_stats), cossin)
 
 
 def window_attn_rope_backward(q, k, v, angles, scale: float, out, stats, cossin, grad_out, need=(True, True, True, True)):
     """gsasr_window_attn_rope_backward -> (g_q, g_k, g_v, g_angles), None where `need` is False (the angle gradient is formed
     from g_q and g_k: both are computed for it, and dropped here when not needed themselves)"""
-    d = _window_attn_rope(q, k, v, angles, scale)
-    bf16 = q.dtype == torch.bfloat16
-    fn_bytes, fn = _attn_fn("gsasr_window_attn_rope", bf16, "scratch_bytes"), _attn_fn("gsasr_window_attn_rope", bf16, "backward")
-    _chk_act(out, "out", bf16), _chk(stats, "stats"), _chk(cossin, "cossin"), _chk_act(grad_out, "grad_out", bf16)
-    if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq) or \
-            tuple(cossin.shape) != (*angles.shape, 2):
+    d, fns = _attn_desc(q, k, v, angles, True, scale)
+    d.cossin = _chk(cossin, "cossin")
+    if tuple(cossin.shape) != (*angles.shape, 2):
         raise RuntimeError("out / grad_out must have q's shape, stats [W,H,nq] and cossin angles' shape + [2]")
-    dev = q.device
-    with _on(dev):
-        make = (need[0] or need[3], need[1] or need[3], need[2], need[3])
-        grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, angles), make)]
-        d.out, d.stats, d.cossin, d.grad_out = out.data_ptr(), stats.data_ptr(), cossin.data_ptr(), grad_out.data_ptr()
-        d.g_q, d.g_k, d.g_v, d.g_angles = [None if g is None else g.data_ptr() for g in grads]
-        n = int(getattr(lib(), fn_bytes)(ctypes.byref(d)))
-        if n == 0:
-            check(-1, fn_bytes)
-        scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
-        d.scratch = scratch.data_ptr()
-        check(getattr(lib(), fn)(ctypes.byref(d), _stream(dev)), fn)
+    make = (need[0] or need[3], need[1] or need[3], need[2], need[3])
+    grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, angles), make)]
+    _attn_backward(d, fns, q, out, stats, grad_out, **dict(zip(("g_q", "g_k", "g_v", "g_angles"), grads)))
     return tuple(g if n else None for g, n in zip(grads, need))
 
 

@@ -83,52 +83,78 @@ def _checked_index(bias_index, rows: int, device):
     return copy
 
 
-class _WindowAttention(torch.autograd.Function):
-    """(q, k, v, table, int32 index, scale, keep) -> out; `keep`: save the row statistic for a backward"""
-
-    @staticmethod
-    @fp32_boundary_fwd
-    def forward(ctx, q, k, v, table, index, scale, keep):
-        from . import _cabi
-        q, k, v, table = q.contiguous(), k.contiguous(), v.contiguous(), table.contiguous()
-        out, stats = _cabi.window_attn_forward(q, k, v, table, index, scale, want_stats=keep)
-        if keep:
-            ctx.save_for_backward(q, k, v, table, index, out, stats)
-            ctx.scale = scale
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    @fp32_boundary_bwd
-    def backward(ctx, grad_out):
-        from . import _cabi
-        q, k, v, table, index, out, stats = ctx.saved_tensors
-        g = _cabi.window_attn_backward(q, k, v, table, index, ctx.scale, out, stats, grad_out.to(torch.float32).contiguous(),
-                                       need=tuple(ctx.needs_input_grad[:4]))
-        return (*g, None, None, None)
+def _node(name, doc, forward, backward, dtype):
+    """the autograd node of a family (`forward(ctx, ...)`, `backward(ctx, grad_out)` below) on activations of `dtype`, which
+    `grad_out` is cast to.  fp32: the fp32 boundary around both directions (under autocast the inputs are cast to fp32).  bf16:
+    none -- the caller casts, and disables autocast around `apply`"""
+    def bwd(ctx, grad_out):
+        return backward(ctx, grad_out.to(dtype).contiguous())
+    if dtype == torch.float32:
+        forward, bwd = fp32_boundary_fwd(forward), fp32_boundary_bwd(bwd)
+    return type(name, (torch.autograd.Function,), {"__doc__": doc, "forward": staticmethod(forward),
+                                                    "backward": staticmethod(torch.autograd.function.once_differentiable(bwd))})
 
 
-class _WindowAttentionBf16(torch.autograd.Function):
-    """_WindowAttention on bf16 q, k, v and an fp32 table (the caller casts, and disables autocast around `apply`) -> bf16 out"""
+def _biased_forward(ctx, q, k, v, table, index, scale, keep):
+    from . import _cabi
+    q, k, v, table = q.contiguous(), k.contiguous(), v.contiguous(), table.contiguous()
+    out, stats = _cabi.window_attn_forward(q, k, v, table, index, scale, want_stats=keep)
+    if keep:
+        ctx.save_for_backward(q, k, v, table, index, out, stats)
+        ctx.scale = scale
+    return out
 
-    @staticmethod
-    def forward(ctx, q, k, v, table, index, scale, keep):
-        from . import _cabi
-        q, k, v, table = q.contiguous(), k.contiguous(), v.contiguous(), table.contiguous()
-        out, stats = _cabi.window_attn_forward(q, k, v, table, index, scale, want_stats=keep)
-        if keep:
-            ctx.save_for_backward(q, k, v, table, index, out, stats)
-            ctx.scale = scale
-        return out
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        from . import _cabi
-        q, k, v, table, index, out, stats = ctx.saved_tensors
-        g = _cabi.window_attn_backward(q, k, v, table, index, ctx.scale, out, stats, grad_out.to(torch.bfloat16).contiguous(),
-                                       need=tuple(ctx.needs_input_grad[:4]))
-        return (*g, None, None, None)
+def _biased_backward(ctx, grad_out):
+    from . import _cabi
+    q, k, v, table, index, out, stats = ctx.saved_tensors
+    g = _cabi.window_attn_backward(q, k, v, table, index, ctx.scale, out, stats, grad_out, need=tuple(ctx.needs_input_grad[:4]))
+    return (*g, None, None, None)
+
+
+_WindowAttention = _node("_WindowAttention", "(q, k, v, table, int32 index, scale, keep) -> out; `keep`: save the row statistic for a backward",
+                         _biased_forward, _biased_backward, torch.float32)
+_WindowAttentionBf16 = _node("_WindowAttentionBf16", "_WindowAttention on bf16 q, k, v and an fp32 table -> bf16 out",
+                             _biased_forward, _biased_backward, torch.bfloat16)
+
+
+def _check_qkv(q, k, v, side, side_name, compute):
+    """what both ops ask of `compute`, of q, k, v and of the dtype of their table / angles `side` -> (W, nq, nk, C)"""
+    _check_compute(compute)
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (side, side_name)):
+        if not (torch.is_tensor(t) and t.dtype.is_floating_point):
+            raise ValueError(f"{name} must be a floating-point tensor")
+    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: expected [W,nq,C], [W,nk,C], [W,nk,C]")
+    return int(q.shape[0]), int(q.shape[1]), int(k.shape[1]), int(q.shape[2])
+
+
+def _check_limits(W, nq, nk, d):
+    if W < 1 or not 1 <= nq <= MAX_TOKENS or not 1 <= nk <= MAX_TOKENS:
+        raise ValueError(f"need W >= 1 and 1 <= nq, nk <= {MAX_TOKENS} (got W {W}, nq {nq}, nk {nk})")
+    if d > MAX_HEAD_DIM:
+        raise ValueError(f"head dimension {d} exceeds {MAX_HEAD_DIM}")
+
+
+def _run(nodes, torch_forms, compute, d, scale, q, k, v, side, side_name, *index):
+    """the end of both ops, (`nodes`, `torch_forms`) = their (fp32, bf16) pair.  CPU tensors: the torch form.  bf16: q, k, v cast
+    to bf16 and `side` to fp32 if they are not, the node with autocast off.  fp32: all four cast to fp32, the node"""
+    scale = float(d ** -0.5 if scale is None else scale)
+    if not (q.device == k.device == v.device == side.device):
+        raise ValueError(f"q, k, v and {side_name} must be on one device")
+    bf16 = compute == "bf16"
+    if index:
+        index = (_checked_index(index[0], side.shape[0], q.device),)
+    if not q.is_cuda:
+        return torch_forms[bf16](q, k, v, side, *index, scale)
+    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, side))
+    if bf16:
+        q, k, v = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
+        side = side if side.dtype == torch.float32 else side.float()
+        with torch.autocast("cuda", enabled=False):
+            return nodes[1].apply(q, k, v, side, *index, scale, keep)
+    q, k, v, side = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, side))
+    return nodes[0].apply(q, k, v, side, *index, scale, keep)
 
 
 def window_attention(q, k, v, bias_table, bias_index, scale=None, compute="fp32"):
@@ -137,44 +163,19 @@ def window_attention(q, k, v, bias_table, bias_index, scale=None, compute="fp32"
     a non-integer or out-of-range index, or mismatched shapes: ValueError before any launch.  `scale`: default d ** -0.5.
     `compute`: "fp32" (fp32 result; other dtypes are cast to fp32) or "bf16" (q, k, v cast to bf16 if they are not, the table to
     fp32, a bf16 result: `window_attention_bf16_torch`); gradients arrive in each input's own dtype."""
-    _check_compute(compute)
-    for t, name in ((q, "q"), (k, "k"), (v, "v"), (bias_table, "bias_table")):
-        if not (torch.is_tensor(t) and t.dtype.is_floating_point):
-            raise ValueError(f"{name} must be a floating-point tensor")
+    W, nq, nk, C = _check_qkv(q, k, v, bias_table, "bias_table", compute)
     if not torch.is_tensor(bias_index) or bias_index.dtype.is_floating_point or bias_index.dtype in (torch.bool, torch.complex64, torch.complex128):
         raise ValueError("bias_index must be an integer tensor")
-    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
-        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: expected [W,nq,C], [W,nk,C], [W,nk,C]")
-    W, nq, C = (int(s) for s in q.shape)
-    nk = int(k.shape[1])
     if bias_table.dim() != 2 or bias_table.shape[0] < 1 or bias_table.shape[1] < 1:
         raise ValueError(f"bias_table has shape {tuple(bias_table.shape)}, expected [T,H]")
-    T, H = (int(s) for s in bias_table.shape)
+    H = int(bias_table.shape[1])
     if C % H or C == 0:
         raise ValueError(f"{C} channels are not {H} heads (the bias_table's columns) times a head dimension")
-    d = C // H
-    if W < 1 or not 1 <= nq <= MAX_TOKENS or not 1 <= nk <= MAX_TOKENS:
-        raise ValueError(f"need W >= 1 and 1 <= nq, nk <= {MAX_TOKENS} (got W {W}, nq {nq}, nk {nk})")
-    if d > MAX_HEAD_DIM:
-        raise ValueError(f"head dimension {d} exceeds {MAX_HEAD_DIM}")
+    _check_limits(W, nq, nk, C // H)
     if tuple(bias_index.shape) != (nq, nk):
         raise ValueError(f"bias_index has shape {tuple(bias_index.shape)}, expected [{nq}, {nk}]")
-    scale = float(d ** -0.5 if scale is None else scale)
-    if not (q.device == k.device == v.device == bias_table.device):
-        raise ValueError("q, k, v and bias_table must be on one device")
-    index = _checked_index(bias_index, T, q.device)
-    if compute == "bf16" and not q.is_cuda:
-        return window_attention_bf16_torch(q, k, v, bias_table, index, scale)
-    if not q.is_cuda:
-        return window_attention_torch(q, k, v, bias_table, index, scale)
-    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, bias_table))
-    if compute == "bf16":
-        q, k, v = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
-        bias_table = bias_table if bias_table.dtype == torch.float32 else bias_table.float()
-        with torch.autocast("cuda", enabled=False):
-            return _WindowAttentionBf16.apply(q, k, v, bias_table, index, scale, keep)
-    q, k, v, bias_table = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, bias_table))
-    return _WindowAttention.apply(q, k, v, bias_table, index, scale, keep)
+    return _run((_WindowAttention, _WindowAttentionBf16), (window_attention_torch, window_attention_bf16_torch), compute, C // H, scale,
+                q, k, v, bias_table, "bias_table", bias_index)
 
 
 def _rotate(x, cos, sin):
@@ -208,52 +209,27 @@ def window_attention_rope_bf16_torch(q, k, v, angles, scale=None):
     return window_attention_rope_torch(*_bf16_rounded(q, k, v), angles.float(), scale).to(torch.bfloat16)
 
 
-class _WindowAttentionRope(torch.autograd.Function):
-    """(q, k, v, angles, scale, keep) -> out; `keep`: save the row statistic and the (cos, sin) table for a backward"""
-
-    @staticmethod
-    @fp32_boundary_fwd
-    def forward(ctx, q, k, v, angles, scale, keep):
-        from . import _cabi
-        q, k, v, angles = q.contiguous(), k.contiguous(), v.contiguous(), angles.contiguous()
-        out, stats, cossin = _cabi.window_attn_rope_forward(q, k, v, angles, scale, want_stats=keep)
-        if keep:
-            ctx.save_for_backward(q, k, v, angles, out, stats, cossin)
-            ctx.scale = scale
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    @fp32_boundary_bwd
-    def backward(ctx, grad_out):
-        from . import _cabi
-        q, k, v, angles, out, stats, cossin = ctx.saved_tensors
-        g = _cabi.window_attn_rope_backward(q, k, v, angles, ctx.scale, out, stats, cossin, grad_out.to(torch.float32).contiguous(),
-                                            need=tuple(ctx.needs_input_grad[:4]))
-        return (*g, None, None)
+def _rope_forward(ctx, q, k, v, angles, scale, keep):
+    from . import _cabi
+    q, k, v, angles = q.contiguous(), k.contiguous(), v.contiguous(), angles.contiguous()
+    out, stats, cossin = _cabi.window_attn_rope_forward(q, k, v, angles, scale, want_stats=keep)
+    if keep:
+        ctx.save_for_backward(q, k, v, angles, out, stats, cossin)
+        ctx.scale = scale
+    return out
 
 
-class _WindowAttentionRopeBf16(torch.autograd.Function):
-    """_WindowAttentionRope on bf16 q, k, v and fp32 angles (the caller casts, and disables autocast around `apply`) -> bf16 out"""
+def _rope_backward(ctx, grad_out):
+    from . import _cabi
+    q, k, v, angles, out, stats, cossin = ctx.saved_tensors
+    g = _cabi.window_attn_rope_backward(q, k, v, angles, ctx.scale, out, stats, cossin, grad_out, need=tuple(ctx.needs_input_grad[:4]))
+    return (*g, None, None)
 
-    @staticmethod
-    def forward(ctx, q, k, v, angles, scale, keep):
-        from . import _cabi
-        q, k, v, angles = q.contiguous(), k.contiguous(), v.contiguous(), angles.contiguous()
-        out, stats, cossin = _cabi.window_attn_rope_forward(q, k, v, angles, scale, want_stats=keep)
-        if keep:
-            ctx.save_for_backward(q, k, v, angles, out, stats, cossin)
-            ctx.scale = scale
-        return out
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        from . import _cabi
-        q, k, v, angles, out, stats, cossin = ctx.saved_tensors
-        g = _cabi.window_attn_rope_backward(q, k, v, angles, ctx.scale, out, stats, cossin, grad_out.to(torch.bfloat16).contiguous(),
-                                            need=tuple(ctx.needs_input_grad[:4]))
-        return (*g, None, None)
+_WindowAttentionRope = _node("_WindowAttentionRope", "(q, k, v, angles, scale, keep) -> out; `keep`: save the row statistic and the (cos, sin) "
+                             "table for a backward", _rope_forward, _rope_backward, torch.float32)
+_WindowAttentionRopeBf16 = _node("_WindowAttentionRopeBf16", "_WindowAttentionRope on bf16 q, k, v and fp32 angles -> bf16 out",
+                                 _rope_forward, _rope_backward, torch.bfloat16)
 
 
 def window_attention_rope(q, k, v, angles, scale=None, compute="fp32"):
@@ -262,41 +238,17 @@ def window_attention_rope(q, k, v, angles, scale=None, compute="fp32"):
     d even with 2 <= d <= 32, angles [H, N >= max(nq, nk), d/2] floating point on the inputs' device; anything else: ValueError
     before any launch.  `scale`: default d ** -0.5.  `compute`: "fp32" or "bf16", as in `window_attention` (bf16: the angles are
     cast to fp32, the rotation is evaluated in fp32 and the rotated q, k rounded to bf16)."""
-    _check_compute(compute)
-    for t, name in ((q, "q"), (k, "k"), (v, "v"), (angles, "angles")):
-        if not (torch.is_tensor(t) and t.dtype.is_floating_point):
-            raise ValueError(f"{name} must be a floating-point tensor")
-    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
-        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: expected [W,nq,C], [W,nk,C], [W,nk,C]")
-    W, nq, C = (int(s) for s in q.shape)
-    nk = int(k.shape[1])
+    W, nq, nk, C = _check_qkv(q, k, v, angles, "angles", compute)
     if angles.dim() != 3 or angles.shape[0] < 1 or angles.shape[2] < 1:
         raise ValueError(f"angles has shape {tuple(angles.shape)}, expected [H,N,d/2]")
     H, N, half = (int(s) for s in angles.shape)
     if C != H * 2 * half:
         raise ValueError(f"{C} channels are not {H} heads (angles' first extent) times a head dimension of {2 * half} (twice its last)")
-    d = 2 * half
-    if W < 1 or not 1 <= nq <= MAX_TOKENS or not 1 <= nk <= MAX_TOKENS:
-        raise ValueError(f"need W >= 1 and 1 <= nq, nk <= {MAX_TOKENS} (got W {W}, nq {nq}, nk {nk})")
-    if d > MAX_HEAD_DIM:
-        raise ValueError(f"head dimension {d} exceeds {MAX_HEAD_DIM}")
+    _check_limits(W, nq, nk, 2 * half)
     if N < max(nq, nk):
         raise ValueError(f"angles has {N} rows, fewer than max(nq, nk) = {max(nq, nk)}")
-    scale = float(d ** -0.5 if scale is None else scale)
-    if not (q.device == k.device == v.device == angles.device):
-        raise ValueError("q, k, v and angles must be on one device")
-    if compute == "bf16" and not q.is_cuda:
-        return window_attention_rope_bf16_torch(q, k, v, angles, scale)
-    if not q.is_cuda:
-        return window_attention_rope_torch(q, k, v, angles, scale)
-    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, angles))
-    if compute == "bf16":
-        q, k, v = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
-        angles = angles if angles.dtype == torch.float32 else angles.float()
-        with torch.autocast("cuda", enabled=False):
-            return _WindowAttentionRopeBf16.apply(q, k, v, angles, scale, keep)
-    q, k, v, angles = (t if t.dtype == torch.float32 else t.float() for t in (q, k, v, angles))
-    return _WindowAttentionRope.apply(q, k, v, angles, scale, keep)
+    return _run((_WindowAttentionRope, _WindowAttentionRopeBf16), (window_attention_rope_torch, window_attention_rope_bf16_torch), compute,
+                2 * half, scale, q, k, v, angles, "angles")
 
 
 _ATTRS = ("qhead", "khead", "vhead", "proj", "relative_position_bias_table", "relative_position_index", "num_heads")

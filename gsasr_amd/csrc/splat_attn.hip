@@ -46,7 +46,19 @@
 // k_attn_fwd on v_mfma_f32_16x16x32_bf16 -- one instruction per score tile, V staged transposed for the permuted k order of P.
 // Backward: the kernels above instantiated on the element type T = att_bf (loads widen, stores round to nearest even, the
 // rotated operands are rounded to bf16 where they are formed); the products stay on the exact-fp32 instruction.
+//
+// The host layer is written once for the four descriptor types.  AttnFamily<descriptor> (AttnBiased or AttnRotary on float or
+// att_bf) states what differs: the required pointers, the alignment rule, the head_dim and table_rows / angle_rows rules, the
+// scratch, each with its message, and the family's fields of AttnArgsT.  attn_check, attn_args, attn_forward and attn_backward
+// are templates on the descriptor and the twelve extern "C" functions one call each; a new variant is a family and its three
+// entry points.  att_pick turns the runtime (key tiles -> MAXT 3 / 9 / 16, stats, table in LDS, TAB) into template arguments;
+// the dynamic LDS of a kernel is one struct (AttLdsQ, AttLdsKV, AttLdsFwdBf) that the kernel walks to its pointers and the
+// host asks for the byte count.  The four kernels that touch no activation take AttnAux and exist once.
 #include "splat_common.h"
+
+#include <algorithm>
+#include <initializer_list>
+#include <type_traits>
 
 using namespace gsasr_detail;
 
@@ -84,6 +96,31 @@ struct AttnArgsT {
     int ldvec;      // bf16 forward: elements per global load of q, k, v (8, 2 or 1: the head's slice is 16-, 4- or 2-byte aligned)
 };
 typedef AttnArgsT<float> AttnArgs;
+
+// what the kernels that touch no activation read (k_attn_table_sum, k_attn_table_round, k_attn_cossin, k_attn_angle_sum)
+// (no two integers that one of them reads lie side by side unless they did in AttnArgsT: each kernel keeps its scalar loads)
+struct AttnAux {
+    float *g_table, *part; int heads; const float *angles; float *cossin; int d; float *g_angles;
+    int arows, rows, wslots, aslices;
+};
+
+// The dynamic LDS of an activation kernel is described in ONE place: a struct with the sizes of its sub-buffers in the order
+// they lie in, and their sum.  The kernel walks the sizes to its pointers, the host launches with bytes().
+// k_attn_fwd and k_attn_bwd_q, in floats: K and V (`kv` each: [keys padded to tiles][ATT_LD]), the head's table column (`tb`:
+// the table's rows with TLDS, else 0), the binned table gradient (`tab`: the rows with TAB 1, else 0)
+struct AttLdsQ {
+    int kv, tb, tab;
+    __host__ __device__ AttLdsQ(int nk, int tb_rows, int tab_rows = 0) : kv((((nk + 15) >> 4) << 4) * ATT_LD), tb(tb_rows), tab(tab_rows) {}
+    __host__ size_t bytes() const { return ((size_t)kv + kv + tb + tab) * sizeof(float); }
+};
+
+// k_attn_bwd_kv, in floats: scale Q and dO (`qg` each: [queries padded to tiles][ATT_LD]), the statistic and delta (`nqp` each),
+// the table column (`tb`)
+struct AttLdsKV {
+    int nqp, qg, tb;
+    __host__ __device__ AttLdsKV(int nq, int tb_rows) : nqp(((nq + 15) >> 4) << 4), qg(nqp * ATT_LD), tb(tb_rows) {}
+    __host__ size_t bytes() const { return ((size_t)qg + qg + nqp + nqp + tb) * sizeof(float); }
+};
 
 // one activation as fp32, a column pair as fp32, and the store: bf16 widens exactly and is rounded to nearest even at the store
 __device__ __forceinline__ float att_ld(const float *p) { return *p; }
@@ -235,6 +272,13 @@ __device__ __forceinline__ att_f4 att_tile(const float *s_a, int row0, int c16, 
     return acc;
 }
 
+// the thread's place in its workgroup and in the MFMA layouts: {wave, waves, c16 = lane & 15, g = lane >> 4}
+struct AttLane { int wave, nwaves, c16, g; };
+__device__ __forceinline__ AttLane att_lane() { return {(int)(threadIdx.x >> 6), (int)(blockDim.x >> 6), (int)(threadIdx.x & 15), (int)(threadIdx.x & 63) >> 4}; }
+
+// the backward kernels' index pipeline, two tiles ahead: this tile's index <- the next tile's <- the one just loaded
+__device__ __forceinline__ void att_shift(int &ix, int &ix1, int ixn) { ix = ix1; ix1 = ixn; }
+
 // ROPE: q and k rotated (K as it is staged, the query row in registers; rotate, then scale), no table / index / bias
 template <int MAXT, bool STATS, bool TLDS, bool ROPE = false>
 __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
@@ -243,14 +287,15 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
     const int nt = (nk + 15) >> 4, nkp = nt << 4;
-    float *s_k = s_mem, *s_v = s_mem + nkp * ATT_LD, *s_tb = s_v + nkp * ATT_LD;
+    const AttLdsQ L(nk, TLDS ? A.rows : 0);
+    float *s_k = s_mem, *s_v = s_k + L.kv, *s_tb = s_v + L.kv;
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
     if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * C + h * d, cs, nk, nkp, d, C, 1.f);
     else att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
     att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const auto [wave, nwaves, c16, g] = att_lane();
     const int nqt = (nq + 15) >> 4;
     for (int qt = wave; qt < nqt; qt += nwaves) {
         const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
@@ -260,10 +305,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
         att_f4 sc[MAXT];
         const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
         float m = -INFINITY;
-        // the biases of the whole row first, for every tile the instantiation has (indices past nk are clamped, so nothing here
-        // depends on nt and all the loads are in flight together).  They are ADDED to the finished products, as the torch
-        // expression does: as the chains' initial accumulators a bias of 50 costs the eight products their low bits
-        att_f4 bs[ROPE ? 1 : MAXT];
+        att_f4 bs[ROPE ? 1 : MAXT];         // (the whole row's biases first)
 #pragma unroll
         for (int t = 0; t < (ROPE ? 0 : MAXT); ++t) {
             int ix[4];
@@ -414,6 +456,14 @@ __device__ __forceinline__ att_bf8 att_load_q_bf(const att_bf *__restrict__ row,
     return att_frag(w[0], w[1], w[2], w[3]);
 }
 
+// the dynamic LDS of k_attn_fwd_bf (as AttLdsQ): K (`k` bf16: [keys padded to paired steps of 32][ATT_KLD]), V transposed (`vt`
+// bf16: [32][vld]), then the head's table column (`tb` floats)
+struct AttLdsFwdBf {
+    int nkp32, vld, k, vt, tb;
+    __host__ __device__ AttLdsFwdBf(int nk, int tb_rows) : nkp32(((nk + 31) >> 5) << 5), vld(nkp32 + ATT_VPAD), k(nkp32 * ATT_KLD), vt(32 * vld), tb(tb_rows) {}
+    __host__ size_t bytes() const { return ((size_t)k + vt) * sizeof(att_bf) + tb * sizeof(float); }
+};
+
 // The geometry of k_attn_fwd (one workgroup per (window, head), a wave takes 16 queries, the lane holds its query's whole score
 // row in fp32: one maximum, one sum of the unrounded p).  scale multiplies the fp32 score sum; p is rounded to bf16 only as the
 // operand of P V; out is rounded once at the store.  include/gsasr_splat.h has the contract.
@@ -423,9 +473,11 @@ __global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
-    const int nt = (nk + 15) >> 4, nkp32 = ((nk + 31) >> 5) << 5, vld = nkp32 + ATT_VPAD;
-    att_bf *s_k = reinterpret_cast<att_bf *>(s_mem), *s_vt = s_k + nkp32 * ATT_KLD;
-    float *s_tb = reinterpret_cast<float *>(s_vt + 32 * vld);
+    const int nt = (nk + 15) >> 4;
+    const AttLdsFwdBf L(nk, TLDS ? A.rows : 0);
+    const int nkp32 = L.nkp32, vld = L.vld;
+    att_bf *s_k = reinterpret_cast<att_bf *>(s_mem), *s_vt = s_k + L.k;
+    float *s_tb = reinterpret_cast<float *>(s_vt + L.vt);
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
     const att_bf *ksrc = A.k + (size_t)w * nk * C + h * d, *vsrc = A.v + (size_t)w * nk * C + h * d;
     if (A.ldvec == 8) att_stage_kv_bf<8, ROPE>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
@@ -433,7 +485,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
     else if (!ROPE) att_stage_kv_bf<1, false>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const auto [wave, nwaves, c16, g] = att_lane();
     const int nqt = (nq + 15) >> 4;
     for (int qt = wave; qt < nqt; qt += nwaves) {
         const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
@@ -446,7 +498,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
         att_f4 sc[MAXT];
         const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
         float m = -INFINITY;
-        att_f4 bs[ROPE ? 1 : MAXT];         // (the whole row's biases first, as in k_attn_fwd)
+        att_f4 bs[ROPE ? 1 : MAXT];         // (the whole row's biases first)
 #pragma unroll
         for (int t = 0; t < (ROPE ? 0 : MAXT); ++t) {
             int ix[4];
@@ -517,8 +569,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
     const int slot = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
     const int nt = (nk + 15) >> 4, nkp = nt << 4, nqt = (nq + 15) >> 4;
-    float *s_k = s_mem, *s_v = s_mem + nkp * ATT_LD, *s_tb = s_v + nkp * ATT_LD, *s_tab = s_tb + (TLDS ? A.rows : 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const AttLdsQ L(nk, TLDS ? A.rows : 0, TAB == 1 ? A.rows : 0);
+    float *s_k = s_mem, *s_v = s_k + L.kv, *s_tb = s_v + L.kv, *s_tab = s_tb + L.tb;
+    const auto [wave, nwaves, c16, g] = att_lane();
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
     if (TAB == 1) for (int t = threadIdx.x; t < A.rows; t += blockDim.x) s_tab[t] = 0.f;
     if (TLDS) att_stage_table(s_tb, A, h);
@@ -578,8 +631,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
                     ds[r] = p * (dp[r] - delta);
                     if (TAB == 1 && valid) atomicAdd(&s_tab[ix[r]], ds[r]);
                     if (TAB == 2 && valid) atomicAdd(reinterpret_cast<double *>(A.part) + (size_t)ix[r] * A.heads + h, (double)ds[r]);
-                    ix[r] = ix1[r];
-                    ix1[r] = ixn[r];
+                    att_shift(ix[r], ix1[r], ixn[r]);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -614,8 +666,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
 
 // g_table[t, h] = the partial columns of head h added in a fixed order: 32 entries per workgroup, eight threads per entry
 // each adding the slots s = slice, slice + 8, ... (short chains of independent loads), then the eight sums in slice order
-template <typename T = float>
-__global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgsT<T> A)
+__global__ __launch_bounds__(256) void k_attn_table_sum(AttnAux A)
 {
     __shared__ float s_sum[8][32];
     const int e = blockIdx.x * 32 + (threadIdx.x & 31), slice = threadIdx.x >> 5;
@@ -632,8 +683,7 @@ __global__ __launch_bounds__(256) void k_attn_table_sum(AttnArgsT<T> A)
 }
 
 // g_table = the double sums of the TAB == 2 walk, rounded once
-template <typename T = float>
-__global__ __launch_bounds__(256) void k_attn_table_round(AttnArgsT<T> A)
+__global__ __launch_bounds__(256) void k_attn_table_round(AttnAux A)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < A.rows * A.heads) A.g_table[e] = (float)reinterpret_cast<const double *>(A.part)[e];
@@ -647,7 +697,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
     const int nqt = (nq + 15) >> 4, nqp = nqt << 4, nkt = (nk + 15) >> 4;
-    float *s_q = s_mem, *s_g = s_mem + nqp * ATT_LD, *s_lse = s_g + nqp * ATT_LD, *s_delta = s_lse + nqp, *s_tb = s_delta + nqp;
+    const AttLdsKV L(nq, TLDS ? A.rows : 0);
+    float *s_q = s_mem, *s_g = s_q + L.qg, *s_lse = s_g + L.qg, *s_delta = s_lse + L.nqp, *s_tb = s_delta + L.nqp;
     const size_t qbase = (size_t)w * nq * C + h * d;
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
     if (ROPE) att_stage_rot(s_q, A.q + qbase, cs, nq, nqp, d, C, A.scale);
@@ -665,7 +716,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
         s_lse[i] = i < nq ? A.stats[((size_t)w * A.heads + h) * nq + i] : 0.f;
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, c16 = lane & 15, g = lane >> 4;
+    const auto [wave, nwaves, c16, g] = att_lane();
     for (int kt = wave; kt < nkt; kt += nwaves) {
         const int j = kt * 16 + c16, jc = min(j, nk - 1);
         const bool jv = j < nk;
@@ -709,8 +760,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
                 const int i = 16 * t + 4 * g + r;
                 p[r] = (jv && i < nq) ? att_exp((ROPE ? sc[r] : sc[r] + b[r]) - lse[r]) : 0.f;
                 ds[r] = p[r] * (dp[r] - dl[r]);
-                ix[r] = ix1[r];
-                ix1[r] = ixn[r];
+                att_shift(ix[r], ix1[r], ixn[r]);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -745,8 +795,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
 
 // cossin[h, n, j] = (cos, sin) of angles[h, n, j], once per call: the accurate sincosf (angles reach tens of radians, where the
 // hardware's v_sin_f32 / v_cos_f32 lose the bits the scores need), read by every workgroup of the three attention kernels
-template <typename T = float>
-__global__ __launch_bounds__(256) void k_attn_cossin(AttnArgsT<T> A)
+__global__ __launch_bounds__(256) void k_attn_cossin(AttnAux A)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= A.heads * A.arows * (A.d >> 1)) return;
@@ -787,8 +836,7 @@ __global__ __launch_bounds__(256) void k_attn_angle_grad(AttnArgsT<T> A)
 }
 
 // g_angles = the slices' partials added in slice order
-template <typename T = float>
-__global__ __launch_bounds__(256) void k_attn_angle_sum(AttnArgsT<T> A)
+__global__ __launch_bounds__(256) void k_attn_angle_sum(AttnAux A)
 {
     const int per = A.heads * A.arows * (A.d >> 1), e = blockIdx.x * 256 + threadIdx.x;
     if (e >= per) return;
@@ -797,88 +845,158 @@ __global__ __launch_bounds__(256) void k_attn_angle_sum(AttnArgsT<T> A)
     A.g_angles[e] = a;
 }
 
-template <typename D>
-int attn_geometry_check(const D *a)
-{
-    if (!a) return fail(GSASR_ERR_ARG, "null window-attention descriptor");
-    if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
-    if (a->nq < 1 || a->nq > ATT_MAX_N || a->nk < 1 || a->nk > ATT_MAX_N) return fail(GSASR_ERR_ARG, "need 1 <= nq, nk <= 256");
-    if (a->head_dim < 1 || a->head_dim > ATT_MAX_D) return fail(GSASR_ERR_ARG, "need 1 <= head_dim <= 32");
-    if (a->table_rows < 1) return fail(GSASR_ERR_ARG, "table_rows must be at least 1");
-    if (a->flags) return fail(GSASR_ERR_ARG, "unknown flags (none are defined)");
-    if (!(a->scale == a->scale)) return fail(GSASR_ERR_ARG, "scale is NaN");
-    if ((long long)a->windows * a->heads > 0x7fffffffLL || (long long)a->table_rows * a->heads > 0x7fffffffLL)
-        return fail(GSASR_ERR_ARG, "windows * heads or table_rows * heads exceeds 2^31 - 1");
-    return GSASR_OK;
-}
-
-template <typename D>
-inline int attn_wslots(const D *a) { return a->windows < ATT_TAB_WG ? a->windows : ATT_TAB_WG; }
-
-// elements per global load of the bf16 forward: by the alignment of a head's slice (its offset is 2 h d bytes into a row of 2 H d)
-inline int attn_ldvec(const void *q, const void *k, const void *v, int d)
-{
-    const uintptr_t any = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v;
-    return d % 8 == 0 && (any & 15) == 0 ? 8 : d % 2 == 0 && (any & 3) == 0 ? 2 : 1;
-}
-
-template <typename T, typename D>
-AttnArgsT<T> attn_args(const D *a)
-{
-    AttnArgsT<T> A;
-    A.q = a->q; A.k = a->k; A.v = a->v; A.table = a->table; A.index = a->index; A.out = a->out; A.o = a->out; A.stats = a->stats;
-    A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.g_table = a->g_table; A.part = (float *)a->scratch;
-    A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.rows = a->table_rows;
-    A.wslots = attn_wslots(a);
-    A.vec = a->nk % 4 == 0 && ((uintptr_t)a->index & 15) == 0;
-    A.scale = a->scale;
-    A.angles = nullptr; A.cossin = nullptr; A.g_angles = nullptr; A.arows = 0; A.achunk = 0; A.aslices = 0;
-    A.ldvec = attn_ldvec(a->q, a->k, a->v, a->head_dim);
-    return A;
-}
-
+// ---- the host layer: one path for the four descriptor families (the head comment has the plan) ------------------------
 constexpr int ATT_ANGLE_CHUNK = 8;      // windows a thread of k_attn_angle_grad adds, at least
 constexpr int ATT_ANGLE_SLICES = 64;    // slices (partials per angle), at most
 
-template <typename D>
-int attn_rope_geometry_check(const D *a)
-{
-    if (!a) return fail(GSASR_ERR_ARG, "null rotary window-attention descriptor");
-    if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
-    if (a->nq < 1 || a->nq > ATT_MAX_N || a->nk < 1 || a->nk > ATT_MAX_N) return fail(GSASR_ERR_ARG, "need 1 <= nq, nk <= 256");
-    if (a->head_dim < 2 || a->head_dim > ATT_MAX_D || a->head_dim % 2) return fail(GSASR_ERR_ARG, "need an even head_dim, 2 <= head_dim <= 32");
-    if (a->angle_rows < (a->nq > a->nk ? a->nq : a->nk)) return fail(GSASR_ERR_ARG, "angle_rows must be at least max(nq, nk)");
-    if (a->flags) return fail(GSASR_ERR_ARG, "unknown flags (none are defined)");
-    if (!(a->scale == a->scale)) return fail(GSASR_ERR_ARG, "scale is NaN");
-    if ((long long)a->windows * a->heads > 0x7fffffffLL || (long long)a->angle_rows * a->heads * (a->head_dim / 2) > 0x7fffffffLL)
-        return fail(GSASR_ERR_ARG, "windows * heads or heads * angle_rows * head_dim / 2 exceeds 2^31 - 1");
-    return GSASR_OK;
-}
-
-inline int attn_angle_chunk(int windows)
-{
-    const int even = (windows + ATT_ANGLE_SLICES - 1) / ATT_ANGLE_SLICES;
-    return even > ATT_ANGLE_CHUNK ? even : ATT_ANGLE_CHUNK;
-}
+inline int attn_angle_chunk(int windows) { return std::max((windows + ATT_ANGLE_SLICES - 1) / ATT_ANGLE_SLICES, ATT_ANGLE_CHUNK); }
 inline int attn_angle_slices(int windows) { return (windows + attn_angle_chunk(windows) - 1) / attn_angle_chunk(windows); }
 
-inline bool attn_misaligned(const void *p, uintptr_t to = 8) { return ((uintptr_t)p & (to - 1)) != 0; }
-
-template <typename T, typename D>
-AttnArgsT<T> attn_rope_args(const D *a)
+// true when one of the pointers is not a multiple of `to` (an activation pointer the call does not need may be null)
+inline bool attn_misaligned(uintptr_t to, std::initializer_list<const void *> ps)
 {
-    AttnArgsT<T> A;
-    A.q = a->q; A.k = a->k; A.v = a->v; A.table = nullptr; A.index = nullptr; A.out = a->out; A.o = a->out; A.stats = a->stats;
-    A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.g_table = nullptr; A.part = (float *)a->scratch;
-    A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.rows = 0;
-    A.wslots = a->windows;      // (no table to bin: one workgroup of k_attn_bwd_q per window and head)
-    A.vec = false;
-    A.scale = a->scale;
-    A.angles = a->angles; A.cossin = a->cossin; A.g_angles = a->g_angles; A.arows = a->angle_rows;
-    A.achunk = attn_angle_chunk(a->windows); A.aslices = attn_angle_slices(a->windows);
-    A.ldvec = attn_ldvec(a->q, a->k, a->v, a->head_dim);
+    for (const void *p : ps) if ((uintptr_t)p & (to - 1)) return true;
+    return false;
+}
+
+// A family states what its descriptor D must hold -- every check returns the message of the first defect, or nullptr, for a
+// forward or (`bwd`) a backward -- and fills its own fields of the kernels' arguments.  T: the activations' element type.
+// The biased family (gsasr_window_attn, gsasr_window_attn_bf16):
+template <typename D, typename ELEM>
+struct AttnBiased {
+    typedef ELEM T;
+    static constexpr bool ROPE = false;
+    static constexpr const char *NULL_DESC = "null window-attention descriptor", *TOO_MANY = "windows * heads or table_rows * heads exceeds 2^31 - 1";
+    static const char *bad_size(const D *a)
+    {
+        return a->head_dim < 1 || a->head_dim > ATT_MAX_D ? "need 1 <= head_dim <= 32" : a->table_rows < 1 ? "table_rows must be at least 1" : nullptr;
+    }
+    static long long side_elems(const D *a) { return (long long)a->table_rows * a->heads; }
+    static const char *missing(const D *a, bool bwd)
+    {
+        const bool fwd = a->q && a->k && a->v && a->table && a->index && a->out;
+        if (!bwd) return fwd ? nullptr : "null q, k, v, table, index or out pointer";
+        return fwd && a->stats && a->grad_out ? nullptr : "null q, k, v, table, index, out, stats or grad_out pointer";
+    }
+    static const char *misaligned(const D *a, bool bwd)
+    {
+        if (sizeof(T) != 2) return nullptr;
+        if (!bwd) return attn_misaligned(2, {a->q, a->k, a->v, a->out}) ? "q, k, v and out must be 2-byte aligned" : nullptr;
+        return attn_misaligned(2, {a->q, a->k, a->v, a->out, a->grad_out, a->g_q, a->g_k, a->g_v}) ? "q, k, v, out, grad_out, g_q, g_k and g_v must be 2-byte aligned" : nullptr;
+    }
+    static int wslots(const D *a) { return a->windows < ATT_TAB_WG ? a->windows : ATT_TAB_WG; }
+    // d table (k_attn_bwd_q's TAB): 0 none, 1 binned in LDS into partial columns, 2 double atomics on the scratch
+    static int tab(const D *a) { return !a->g_table ? 0 : a->table_rows <= ATT_TAB_LDS ? 1 : 2; }
+    static const char *bad_scratch(const D *a)
+    {
+        if (tab(a) && !a->scratch) return "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)";
+        return tab(a) == 2 && ((uintptr_t)a->scratch & 7) ? "scratch must be 8-byte aligned" : nullptr;
+    }
+    // the backward's partial table columns (one per window slot and head), or above ATT_TAB_LDS rows the table's sums in double
+    static size_t scratch(const D *a)
+    {
+        return align_up((tab(a) == 2 ? sizeof(double) : tab(a) * wslots(a) * sizeof(float)) * a->heads * a->table_rows, 256);
+    }
+    static void fill(AttnArgsT<T> &A, const D *a)
+    {
+        A.table = a->table; A.index = a->index; A.g_table = a->g_table; A.rows = a->table_rows; A.wslots = wslots(a);
+        A.vec = a->nk % 4 == 0 && ((uintptr_t)a->index & 15) == 0;
+    }
+};
+
+// the rotary family (gsasr_window_attn_rope, gsasr_window_attn_rope_bf16): no table, no index; the angles and their (cos, sin)
+template <typename D, typename ELEM>
+struct AttnRotary {
+    typedef ELEM T;
+    static constexpr bool ROPE = true;
+    static constexpr const char *NULL_DESC = "null rotary window-attention descriptor", *TOO_MANY = "windows * heads or heads * angle_rows * head_dim / 2 exceeds 2^31 - 1";
+    static const char *bad_size(const D *a)
+    {
+        if (a->head_dim < 2 || a->head_dim > ATT_MAX_D || a->head_dim % 2) return "need an even head_dim, 2 <= head_dim <= 32";
+        return a->angle_rows < (a->nq > a->nk ? a->nq : a->nk) ? "angle_rows must be at least max(nq, nk)" : nullptr;
+    }
+    static long long side_elems(const D *a) { return (long long)a->angle_rows * a->heads * (a->head_dim / 2); }
+    static const char *missing(const D *a, bool bwd)
+    {
+        const bool both = a->q && a->k && a->v && a->out && a->cossin;
+        if (!bwd) return both && a->angles ? nullptr : "null q, k, v, angles, out or cossin pointer";
+        if (!both || !a->stats || !a->grad_out) return "null q, k, v, out, stats, grad_out or cossin pointer";
+        return a->g_angles && (!a->g_q || !a->g_k) ? "g_angles needs g_q and g_k (it is formed from them)" : nullptr;
+    }
+    static const char *misaligned(const D *a, bool bwd)
+    {
+        const bool cs = attn_misaligned(8, {a->cossin});
+        if (sizeof(T) != 2) {       // (column pairs are read and written 8 bytes at a time)
+            if (!bwd) return cs || attn_misaligned(8, {a->q, a->k}) ? "q, k and cossin must be 8-byte aligned" : nullptr;
+            return cs || attn_misaligned(8, {a->q, a->k, a->g_q, a->g_k}) ? "q, k, cossin, g_q and g_k must be 8-byte aligned" : nullptr;
+        }
+        if (!bwd) return cs || attn_misaligned(4, {a->q, a->k, a->v, a->out}) ? "q, k, v and out must be 4-byte aligned and cossin 8-byte aligned" : nullptr;
+        return cs || attn_misaligned(4, {a->q, a->k, a->v, a->out, a->grad_out, a->g_q, a->g_k, a->g_v})
+                   ? "q, k, v, out, grad_out, g_q, g_k and g_v must be 4-byte aligned and cossin 8-byte aligned" : nullptr;
+    }
+    static int tab(const D *) { return 0; }
+    // the slices' partial angle gradients of the backward
+    static size_t scratch(const D *a)
+    {
+        const int slices = attn_angle_slices(a->windows);
+        return a->g_angles && slices > 1 ? align_up((size_t)slices * a->heads * a->angle_rows * (a->head_dim / 2) * sizeof(float), 256) : 0;
+    }
+    static const char *bad_scratch(const D *a)
+    {
+        return scratch(a) && !a->scratch ? "null scratch pointer (the angle gradient needs gsasr_window_attn_rope_scratch_bytes)" : nullptr;
+    }
+    static void fill(AttnArgsT<T> &A, const D *a)
+    {
+        A.wslots = a->windows;      // (no table to bin: one workgroup of k_attn_bwd_q per window and head)
+        A.angles = a->angles; A.cossin = a->cossin; A.g_angles = a->g_angles; A.arows = a->angle_rows;
+        A.achunk = attn_angle_chunk(a->windows); A.aslices = attn_angle_slices(a->windows);
+    }
+};
+
+template <typename D> struct AttnFamily;
+template <> struct AttnFamily<gsasr_window_attn> : AttnBiased<gsasr_window_attn, float> {};
+template <> struct AttnFamily<gsasr_window_attn_bf16> : AttnBiased<gsasr_window_attn_bf16, att_bf> {};
+template <> struct AttnFamily<gsasr_window_attn_rope> : AttnRotary<gsasr_window_attn_rope, float> {};
+template <> struct AttnFamily<gsasr_window_attn_rope_bf16> : AttnRotary<gsasr_window_attn_rope_bf16, att_bf> {};
+
+// the sizes, flags and scale of a descriptor (no pointer is looked at), then with `call` = 1 a forward's or 2 a backward's pointers
+template <typename D>
+int attn_check(const D *a, int call = 0)
+{
+    typedef AttnFamily<D> F;
+    if (!a) return fail(GSASR_ERR_ARG, F::NULL_DESC);
+    if (a->windows < 1 || a->heads < 1) return fail(GSASR_ERR_ARG, "windows and heads must be at least 1");
+    if (a->nq < 1 || a->nq > ATT_MAX_N || a->nk < 1 || a->nk > ATT_MAX_N) return fail(GSASR_ERR_ARG, "need 1 <= nq, nk <= 256");
+    if (const char *msg = F::bad_size(a)) return fail(GSASR_ERR_ARG, msg);
+    if (a->flags) return fail(GSASR_ERR_ARG, "unknown flags (none are defined)");
+    if (!(a->scale == a->scale)) return fail(GSASR_ERR_ARG, "scale is NaN");
+    if ((long long)a->windows * a->heads > 0x7fffffffLL || F::side_elems(a) > 0x7fffffffLL) return fail(GSASR_ERR_ARG, F::TOO_MANY);
+    const char *msg = call ? F::missing(a, call == 2) : nullptr;
+    if (call && !msg) msg = F::misaligned(a, call == 2);
+    if (call == 2 && !msg) msg = F::bad_scratch(a);
+    return msg ? fail(GSASR_ERR_ARG, msg) : GSASR_OK;
+}
+
+// never 0 for a valid descriptor
+template <typename D>
+size_t attn_scratch_bytes(const D *a) { return attn_check(a) ? 0 : 256 + AttnFamily<D>::scratch(a); }
+
+template <typename D>
+AttnArgsT<typename AttnFamily<D>::T> attn_args(const D *a)
+{
+    AttnArgsT<typename AttnFamily<D>::T> A = {};
+    A.q = a->q; A.k = a->k; A.v = a->v; A.out = a->out; A.o = a->out; A.stats = a->stats;
+    A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.part = (float *)a->scratch;
+    A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.scale = a->scale;
+    // elements per global load of the bf16 forward: by the alignment of a head's slice (its offset is 2 h d bytes into a row of 2 H d)
+    const uintptr_t any = (uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v;
+    A.ldvec = A.d % 8 == 0 && (any & 15) == 0 ? 8 : A.d % 2 == 0 && (any & 3) == 0 ? 2 : 1;
+    AttnFamily<D>::fill(A, a);
     return A;
 }
+
+template <typename T>
+AttnAux attn_aux(const AttnArgsT<T> &A) { return {A.g_table, A.part, A.heads, A.angles, A.cossin, A.d, A.g_angles, A.arows, A.rows, A.wslots, A.aslices}; }
 
 // waves per workgroup, one 16-row tile per wave and turn: three when that deals the tiles evenly and four do not (144 tokens = 9 tiles)
 inline int attn_waves(int n)
@@ -887,133 +1005,92 @@ inline int attn_waves(int n)
     return tiles % 4 != 0 && tiles % 3 == 0 ? 3 : 4;
 }
 
-template <typename D>
-inline bool attn_tlds(const D *a) { return a->table_rows <= ATT_TAB_LDS; }
-
 template <typename K, typename ARGS>
-int attn_launch(K kernel, unsigned grid, int waves, size_t lds, hipStream_t st, const ARGS &A)
+int attn_launch(K kernel, dim3 grid, int waves, size_t lds, hipStream_t st, const ARGS &A)
 {
     if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, A);
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * waves), lds, st, A);
     HIP_TRY(hipGetLastError());
     return GSASR_OK;
 }
 
+// f(std::integral_constant<int, N>) for the first N of the list with v <= N (the last one otherwise): a runtime value as a
+// template argument.  Every MAXT, STATS, TLDS and TAB of a launch comes through here
+template <int N, int... MORE, typename F>
+int att_pick(int v, F &&f)
+{
+    if constexpr (sizeof...(MORE) == 0) return f(std::integral_constant<int, N>());
+    else return v <= N ? f(std::integral_constant<int, N>()) : att_pick<MORE...>(v, f);
+}
+
 template <typename D>
-size_t attn_scratch_bytes(const D *a)
+int attn_forward(const D *a, void *stream)
 {
-    if (attn_geometry_check(a)) return 0;
-    // the partial table columns of the backward (one per window slot and head), or above ATT_TAB_LDS rows the table's sums
-    // in double; never 0 for a valid descriptor
-    if (!a->g_table) return 256;
-    if (a->table_rows > ATT_TAB_LDS) return 256 + align_up((size_t)a->table_rows * a->heads * sizeof(double), 256);
-    return 256 + align_up((size_t)attn_wslots(a) * a->heads * a->table_rows * sizeof(float), 256);
+    typedef AttnFamily<D> F;
+    typedef typename F::T T;
+    if (int rc = attn_check(a, 1)) return rc;
+    const AttnArgsT<T> A = attn_args(a);
+    hipStream_t st = (hipStream_t)stream;
+    if (F::ROPE) if (int rc = attn_launch(k_attn_cossin, (unsigned)((A.heads * A.arows * (A.d / 2) + 255) / 256), 4, 0, st, attn_aux(A))) return rc;
+    const unsigned grid = (unsigned)(A.windows * A.heads);
+    const int waves = attn_waves(A.nq);
+    const bool tlds = !F::ROPE && A.rows <= ATT_TAB_LDS;
+    return att_pick<3, 9, 16>((A.nk + 15) / 16, [&](auto maxt) { return att_pick<0, 1>(A.stats != nullptr, [&](auto stats) { return att_pick<0, 1>(tlds, [&](auto tl) {
+        constexpr int MAXT = decltype(maxt)::value;
+        constexpr bool STATS = decltype(stats)::value, TLDS = decltype(tl)::value && !F::ROPE;
+        if constexpr (sizeof(T) == 2) return attn_launch(k_attn_fwd_bf<MAXT, STATS, TLDS, F::ROPE>, grid, waves, AttLdsFwdBf(A.nk, TLDS ? A.rows : 0).bytes(), st, A);
+        else return attn_launch(k_attn_fwd<MAXT, STATS, TLDS, F::ROPE>, grid, waves, AttLdsQ(A.nk, TLDS ? A.rows : 0).bytes(), st, A);
+    }); }); });
 }
 
-// the bf16 descriptors: an activation pointer the call needs (non-null ones among the optional) must hold whole elements
-inline bool attn_bf_misaligned(std::initializer_list<const void *> ps, uintptr_t to)
+// d table after k_attn_bwd_q: the partial columns added in a fixed order (TAB 1), or the double sums rounded (TAB 2)
+template <typename T>
+int attn_table_tail(const AttnArgsT<T> &A, int tab, hipStream_t st)
 {
-    for (const void *p : ps) if (attn_misaligned(p, to)) return true;
-    return false;
+    const unsigned n = (unsigned)(A.rows * A.heads);
+    return tab == 1 ? attn_launch(k_attn_table_sum, (n + 31) / 32, 4, 0, st, attn_aux(A)) : attn_launch(k_attn_table_round, (n + 255) / 256, 4, 0, st, attn_aux(A));
 }
 
-// the backward of both element types: the three kernels and the table kernels, instantiated on T
-template <typename T, typename D>
+// d angles after both kernels: from q, k and their gradients, a slice of windows per thread, then the slices in order
+template <typename T>
+int attn_angle_tail(const AttnArgsT<T> &A, hipStream_t st)
+{
+    if (!A.g_angles) return GSASR_OK;
+    const unsigned blocks = (unsigned)((A.heads * A.arows * (A.d / 2) + 255) / 256);
+    if (int rc = attn_launch(k_attn_angle_grad<T>, dim3(blocks, (unsigned)A.aslices), 4, 0, st, A)) return rc;
+    return A.aslices > 1 ? attn_launch(k_attn_angle_sum, blocks, 4, 0, st, attn_aux(A)) : GSASR_OK;
+}
+
+// the backward of every family: k_attn_bwd_q (dq, d table), k_attn_bwd_kv (dk, dv), each followed by the family's own tail
+template <typename D>
 int attn_backward(const D *a, void *stream)
 {
-    if (int rc = attn_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out || !a->stats || !a->grad_out)
-        return fail(GSASR_ERR_ARG, "null q, k, v, table, index, out, stats or grad_out pointer");
-    if (sizeof(T) == 2 && attn_bf_misaligned({a->q, a->k, a->v, a->out, a->grad_out, a->g_q, a->g_k, a->g_v}, 2))
-        return fail(GSASR_ERR_ARG, "q, k, v, out, grad_out, g_q, g_k and g_v must be 2-byte aligned");
-    const AttnArgsT<T> A = attn_args<T>(a);
+    typedef AttnFamily<D> F;
+    typedef typename F::T T;
+    if (int rc = attn_check(a, 2)) return rc;
+    const AttnArgsT<T> A = attn_args(a);
     hipStream_t st = (hipStream_t)stream;
-    const bool tlds = attn_tlds(a);
-    const int tab = !a->g_table ? 0 : tlds ? 1 : 2;
-    if (tab && !a->scratch) return fail(GSASR_ERR_ARG, "null scratch pointer (the table gradient needs gsasr_window_attn_scratch_bytes)");
-    if (tab == 2 && ((uintptr_t)a->scratch & 7)) return fail(GSASR_ERR_ARG, "scratch must be 8-byte aligned");
-    if (a->g_q || tab) {
-        const size_t lds = ((size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD + (tlds ? a->table_rows : 0) + (tab == 1 ? a->table_rows : 0)) * sizeof(float);
-        const unsigned grid = (unsigned)(A.wslots * a->heads);
-        const int waves = attn_waves(a->nq);
-        int rc;
-        if (tab == 2) {
-            HIP_TRY(hipMemsetAsync(a->scratch, 0, (size_t)a->table_rows * a->heads * sizeof(double), st));
-            rc = attn_launch(k_attn_bwd_q<2, false, false, T>, grid, waves, lds, st, A);
-        } else if (tab == 1) rc = attn_launch(k_attn_bwd_q<1, true, false, T>, grid, waves, lds, st, A);
-        else rc = tlds ? attn_launch(k_attn_bwd_q<0, true, false, T>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_q<0, false, false, T>, grid, waves, lds, st, A);
+    const int tab = F::tab(a);
+    const bool tlds = !F::ROPE && A.rows <= ATT_TAB_LDS;
+    if (A.g_q || tab) {
+        if (tab == 2) HIP_TRY(hipMemsetAsync(A.part, 0, (size_t)A.rows * A.heads * sizeof(double), st));
+        const size_t lds = AttLdsQ(A.nk, tlds ? A.rows : 0, tab == 1 ? A.rows : 0).bytes();
+        int rc = att_pick<0, 1, 2>(tab, [&](auto t) { return att_pick<0, 1>(tlds, [&](auto tl) {
+            constexpr int TAB = F::ROPE ? 0 : decltype(t)::value;
+            constexpr bool TLDS = TAB == 1 || (TAB == 0 && !F::ROPE && decltype(tl)::value);     // (TAB 1 is the table in LDS, TAB 2 is not)
+            return attn_launch(k_attn_bwd_q<TAB, TLDS, F::ROPE, T>, (unsigned)(A.wslots * A.heads), attn_waves(A.nq), lds, st, A);
+        }); });
+        if (!rc && tab) rc = attn_table_tail(A, tab, st);
         if (rc) return rc;
-        if (tab == 1) {
-            hipLaunchKernelGGL(k_attn_table_sum<T>, dim3((unsigned)((a->table_rows * a->heads + 31) / 32)), dim3(256), 0, st, A);
-            HIP_TRY(hipGetLastError());
-        }
-        if (tab == 2) {
-            hipLaunchKernelGGL(k_attn_table_round<T>, dim3((unsigned)((a->table_rows * a->heads + 255) / 256)), dim3(256), 0, st, A);
-            HIP_TRY(hipGetLastError());
-        }
     }
-    if (a->g_k || a->g_v) {
-        const int nqp = (a->nq + 15) / 16 * 16;
-        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp + (tlds ? a->table_rows : 0)) * sizeof(float);
-        const unsigned grid = (unsigned)(a->windows * a->heads);
-        const int waves = attn_waves(a->nk);
-        if (int rc = tlds ? attn_launch(k_attn_bwd_kv<true, false, T>, grid, waves, lds, st, A) : attn_launch(k_attn_bwd_kv<false, false, T>, grid, waves, lds, st, A)) return rc;
+    if (A.g_k || A.g_v) {
+        const size_t lds = AttLdsKV(A.nq, tlds ? A.rows : 0).bytes();
+        if (int rc = att_pick<0, 1>(tlds, [&](auto tl) {
+                constexpr bool TLDS = decltype(tl)::value && !F::ROPE;
+                return attn_launch(k_attn_bwd_kv<TLDS, F::ROPE, T>, (unsigned)(A.windows * A.heads), attn_waves(A.nk), lds, st, A);
+            })) return rc;
     }
-    return GSASR_OK;
-}
-
-template <typename D>
-size_t attn_rope_scratch_bytes(const D *a)
-{
-    if (attn_rope_geometry_check(a)) return 0;
-    // the slices' partial angle gradients of the backward; never 0 for a valid descriptor
-    const int slices = attn_angle_slices(a->windows);
-    const bool part = a->g_angles && slices > 1;
-    return 256 + (part ? align_up((size_t)slices * a->heads * a->angle_rows * (a->head_dim / 2) * sizeof(float), 256) : 0);
-}
-
-template <typename T, typename D>
-int attn_rope_backward(const D *a, void *stream)
-{
-    if (int rc = attn_rope_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->out || !a->stats || !a->grad_out || !a->cossin)
-        return fail(GSASR_ERR_ARG, "null q, k, v, out, stats, grad_out or cossin pointer");
-    if (a->g_angles && (!a->g_q || !a->g_k)) return fail(GSASR_ERR_ARG, "g_angles needs g_q and g_k (it is formed from them)");
-    if (sizeof(T) == 2) {
-        if (attn_bf_misaligned({a->q, a->k, a->v, a->out, a->grad_out, a->g_q, a->g_k, a->g_v}, 4) || attn_misaligned(a->cossin))
-            return fail(GSASR_ERR_ARG, "q, k, v, out, grad_out, g_q, g_k and g_v must be 4-byte aligned and cossin 8-byte aligned");
-    } else if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin) || attn_misaligned(a->g_q) || attn_misaligned(a->g_k))
-        return fail(GSASR_ERR_ARG, "q, k, cossin, g_q and g_k must be 8-byte aligned");
-    const AttnArgsT<T> A = attn_rope_args<T>(a);
-    if (a->g_angles && A.aslices > 1 && !a->scratch)
-        return fail(GSASR_ERR_ARG, "null scratch pointer (the angle gradient needs gsasr_window_attn_rope_scratch_bytes)");
-    hipStream_t st = (hipStream_t)stream;
-    if (a->g_q) {
-        const size_t lds = (size_t)2 * ((a->nk + 15) / 16) * 16 * ATT_LD * sizeof(float);
-        if (int rc = attn_launch(k_attn_bwd_q<0, false, true, T>, (unsigned)(a->windows * a->heads), attn_waves(a->nq), lds, st, A)) return rc;
-    }
-    if (a->g_k || a->g_v) {
-        const int nqp = (a->nq + 15) / 16 * 16;
-        const size_t lds = ((size_t)2 * nqp * ATT_LD + 2 * nqp) * sizeof(float);
-        if (int rc = attn_launch(k_attn_bwd_kv<false, true, T>, (unsigned)(a->windows * a->heads), attn_waves(a->nk), lds, st, A)) return rc;
-    }
-    if (a->g_angles) {
-        const unsigned blocks = (unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256);
-        hipLaunchKernelGGL(k_attn_angle_grad<T>, dim3(blocks, (unsigned)A.aslices), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
-        if (A.aslices > 1) {
-            hipLaunchKernelGGL(k_attn_angle_sum<T>, dim3(blocks), dim3(256), 0, st, A);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return GSASR_OK;
-}
-
-// LDS of the bf16 forward: K rows and V transposed, keys padded to whole paired steps (32), and the head's table column
-inline size_t attn_bf_fwd_lds(int nk, int table_rows_in_lds)
-{
-    const int nkp32 = (nk + 31) / 32 * 32;
-    return ((size_t)nkp32 * ATT_KLD + (size_t)32 * (nkp32 + ATT_VPAD)) * sizeof(att_bf) + (size_t)table_rows_in_lds * sizeof(float);
+    return F::ROPE ? attn_angle_tail(A, st) : GSASR_OK;
 }
 
 }  // namespace
@@ -1021,102 +1098,20 @@ inline size_t attn_bf_fwd_lds(int nk, int table_rows_in_lds)
 extern "C" {
 
 size_t gsasr_window_attn_scratch_bytes(const gsasr_window_attn *a) { return attn_scratch_bytes(a); }
+int gsasr_window_attn_forward(const gsasr_window_attn *a, void *stream) { return attn_forward(a, stream); }
+int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream) { return attn_backward(a, stream); }
 
-int gsasr_window_attn_forward(const gsasr_window_attn *a, void *stream)
-{
-    if (int rc = attn_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out) return fail(GSASR_ERR_ARG, "null q, k, v, table, index or out pointer");
-    const AttnArgs A = attn_args<float>(a);
-    const int nt = (a->nk + 15) / 16;
-    const bool tlds = attn_tlds(a), stats = a->stats != nullptr;
-    const size_t lds = ((size_t)2 * nt * 16 * ATT_LD + (tlds ? a->table_rows : 0)) * sizeof(float);
-    const unsigned grid = (unsigned)(a->windows * a->heads);
-    const int waves = attn_waves(a->nq);
-    hipStream_t st = (hipStream_t)stream;
-#define ATT_FWD(T) (stats ? (tlds ? attn_launch(k_attn_fwd<T, true, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, true, false>, grid, waves, lds, st, A)) \
-                          : (tlds ? attn_launch(k_attn_fwd<T, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, false, false>, grid, waves, lds, st, A)))
-    if (nt <= 3) return ATT_FWD(3);
-    if (nt <= 9) return ATT_FWD(9);
-    return ATT_FWD(16);
-#undef ATT_FWD
-}
+size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_rope *a) { return attn_scratch_bytes(a); }
+int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *a, void *stream) { return attn_forward(a, stream); }
+int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *a, void *stream) { return attn_backward(a, stream); }
 
-int gsasr_window_attn_backward(const gsasr_window_attn *a, void *stream) { return attn_backward<float>(a, stream); }
-
-size_t gsasr_window_attn_rope_scratch_bytes(const gsasr_window_attn_rope *a) { return attn_rope_scratch_bytes(a); }
-
-int gsasr_window_attn_rope_forward(const gsasr_window_attn_rope *a, void *stream)
-{
-    if (int rc = attn_rope_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->angles || !a->out || !a->cossin) return fail(GSASR_ERR_ARG, "null q, k, v, angles, out or cossin pointer");
-    if (attn_misaligned(a->q) || attn_misaligned(a->k) || attn_misaligned(a->cossin)) return fail(GSASR_ERR_ARG, "q, k and cossin must be 8-byte aligned");
-    const AttnArgs A = attn_rope_args<float>(a);
-    const int nt = (a->nk + 15) / 16;
-    const bool stats = a->stats != nullptr;
-    const size_t lds = (size_t)2 * nt * 16 * ATT_LD * sizeof(float);
-    const unsigned grid = (unsigned)(a->windows * a->heads);
-    const int waves = attn_waves(a->nq);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_attn_cossin<float>, dim3((unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-#define ATT_FWD(T) (stats ? attn_launch(k_attn_fwd<T, true, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd<T, false, false, true>, grid, waves, lds, st, A))
-    if (nt <= 3) return ATT_FWD(3);
-    if (nt <= 9) return ATT_FWD(9);
-    return ATT_FWD(16);
-#undef ATT_FWD
-}
-
-int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *a, void *stream) { return attn_rope_backward<float>(a, stream); }
-
-// ---- bf16 activations: the forward on the bf16 matrix instruction, the backward the kernels above on att_bf ----
+// bf16 activations: the forward on the bf16 matrix instruction, the backward the fp32 kernels on att_bf
 size_t gsasr_window_attn_bf16_scratch_bytes(const gsasr_window_attn_bf16 *a) { return attn_scratch_bytes(a); }
+int gsasr_window_attn_bf16_forward(const gsasr_window_attn_bf16 *a, void *stream) { return attn_forward(a, stream); }
+int gsasr_window_attn_bf16_backward(const gsasr_window_attn_bf16 *a, void *stream) { return attn_backward(a, stream); }
 
-int gsasr_window_attn_bf16_forward(const gsasr_window_attn_bf16 *a, void *stream)
-{
-    if (int rc = attn_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->table || !a->index || !a->out) return fail(GSASR_ERR_ARG, "null q, k, v, table, index or out pointer");
-    if (attn_bf_misaligned({a->q, a->k, a->v, a->out}, 2)) return fail(GSASR_ERR_ARG, "q, k, v and out must be 2-byte aligned");
-    const AttnArgsT<att_bf> A = attn_args<att_bf>(a);
-    const int nt = (a->nk + 15) / 16;
-    const bool tlds = attn_tlds(a), stats = a->stats != nullptr;
-    const size_t lds = attn_bf_fwd_lds(a->nk, tlds ? a->table_rows : 0);
-    const unsigned grid = (unsigned)(a->windows * a->heads);
-    const int waves = attn_waves(a->nq);
-    hipStream_t st = (hipStream_t)stream;
-#define ATT_FWD(T) (stats ? (tlds ? attn_launch(k_attn_fwd_bf<T, true, true, false>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd_bf<T, true, false, false>, grid, waves, lds, st, A)) \
-                          : (tlds ? attn_launch(k_attn_fwd_bf<T, false, true, false>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd_bf<T, false, false, false>, grid, waves, lds, st, A)))
-    if (nt <= 3) return ATT_FWD(3);
-    if (nt <= 9) return ATT_FWD(9);
-    return ATT_FWD(16);
-#undef ATT_FWD
-}
-
-int gsasr_window_attn_bf16_backward(const gsasr_window_attn_bf16 *a, void *stream) { return attn_backward<att_bf>(a, stream); }
-
-size_t gsasr_window_attn_rope_bf16_scratch_bytes(const gsasr_window_attn_rope_bf16 *a) { return attn_rope_scratch_bytes(a); }
-
-int gsasr_window_attn_rope_bf16_forward(const gsasr_window_attn_rope_bf16 *a, void *stream)
-{
-    if (int rc = attn_rope_geometry_check(a)) return rc;
-    if (!a->q || !a->k || !a->v || !a->angles || !a->out || !a->cossin) return fail(GSASR_ERR_ARG, "null q, k, v, angles, out or cossin pointer");
-    if (attn_bf_misaligned({a->q, a->k, a->v, a->out}, 4) || attn_misaligned(a->cossin))
-        return fail(GSASR_ERR_ARG, "q, k, v and out must be 4-byte aligned and cossin 8-byte aligned");
-    const AttnArgsT<att_bf> A = attn_rope_args<att_bf>(a);
-    const int nt = (a->nk + 15) / 16;
-    const bool stats = a->stats != nullptr;
-    const size_t lds = attn_bf_fwd_lds(a->nk, 0);
-    const unsigned grid = (unsigned)(a->windows * a->heads);
-    const int waves = attn_waves(a->nq);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_attn_cossin<att_bf>, dim3((unsigned)((a->heads * a->angle_rows * (a->head_dim / 2) + 255) / 256)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-#define ATT_FWD(T) (stats ? attn_launch(k_attn_fwd_bf<T, true, false, true>, grid, waves, lds, st, A) : attn_launch(k_attn_fwd_bf<T, false, false, true>, grid, waves, lds, st, A))
-    if (nt <= 3) return ATT_FWD(3);
-    if (nt <= 9) return ATT_FWD(9);
-    return ATT_FWD(16);
-#undef ATT_FWD
-}
-
-int gsasr_window_attn_rope_bf16_backward(const gsasr_window_attn_rope_bf16 *a, void *stream) { return attn_rope_backward<att_bf>(a, stream); }
+size_t gsasr_window_attn_rope_bf16_scratch_bytes(const gsasr_window_attn_rope_bf16 *a) { return attn_scratch_bytes(a); }
+int gsasr_window_attn_rope_bf16_forward(const gsasr_window_attn_rope_bf16 *a, void *stream) { return attn_forward(a, stream); }
+int gsasr_window_attn_rope_bf16_backward(const gsasr_window_attn_rope_bf16 *a, void *stream) { return attn_backward(a, stream); }
 
 }  // extern "C"
