@@ -12,6 +12,7 @@ ChrisDud0257/GSASR, behind the reference's own autograd/operator surface).
     from gsasr_amd import imresize, imresize_new, imresize_batch                   # MATLAB bicubic degradation, batched, differentiable
     from gsasr_amd import make_batch, draw_batch                                   # the dataset's crop / LR / augment / pad, one call on uint8 images
     from gsasr_amd import window_attention, use_hip_attention                      # the Fea2GS decoder's window attention, fused
+    from gsasr_amd import window_attention_qkv                                     # ... of a Swin layer: packed qkv, a mask per window
     from gsasr_amd import window_attention_rope                                    # ... of the RoPE decoder (Fea2GS_ROPE_AMP)
     from gsasr_amd import window_attention_bf16_torch, window_attention_rope_bf16_torch   # the contracts of their compute="bf16" mode
 
@@ -36,7 +37,7 @@ def __getattr__(name):      # (lazily: importing the package alone does not impo
         from . import data
         return getattr(data, name)
     if name in ("window_attention", "window_attention_rope", "use_hip_attention", "window_attention_bf16_torch",
-                "window_attention_rope_bf16_torch"):
+                "window_attention_rope_bf16_torch", "window_attention_qkv", "window_attention_qkv_torch"):
         from . import attention
         return getattr(attention, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

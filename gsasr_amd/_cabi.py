@@ -125,6 +125,17 @@ class WindowAttnRopeBf16(ctypes.Structure):
     _fields_ = list(WindowAttnRope._fields_)
 
 
+class WindowAttnMasked(ctypes.Structure):
+    """struct gsasr_window_attn_masked: gsasr_window_attn with a mask per window and row pitches for q, k, v and their gradients"""
+    _fields_ = list(WindowAttn._fields_) + [("mask", ctypes.c_void_p), ("mask_windows", ctypes.c_int)] + \
+        [(p, ctypes.c_int) for p in ("pitch_q", "pitch_k", "pitch_v", "pitch_gq", "pitch_gk", "pitch_gv")]
+
+
+class WindowAttnMaskedBf16(ctypes.Structure):
+    """struct gsasr_window_attn_masked_bf16: gsasr_window_attn_masked with bf16 activations (same fields, same layout)"""
+    _fields_ = list(WindowAttnMasked._fields_)
+
+
 RESIZE_NO_ANTIALIAS, RESIZE_ACCUMULATE, RESIZE_SHARED_SCALE = 1, 2, 4     # GSASR_RESIZE_*
 BATCH_HFLIP, BATCH_VFLIP, BATCH_TRANSPOSE = 1, 2, 4     # GSASR_BATCH_* (aug bits)
 BATCH_BGR, BATCH_NO_ANTIALIAS = 1, 2                    # GSASR_BATCH_* (flags)
@@ -137,6 +148,7 @@ _vp, _f, _i, _u, _sz, _dp = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctype
 _vwp, _lp, _ssp, _mp = ctypes.POINTER(View), ctypes.POINTER(Loss), ctypes.POINTER(Ssim), ctypes.POINTER(Metrics)
 _rzp, _btp, _wap = ctypes.POINTER(Resize), ctypes.POINTER(Batch), ctypes.POINTER(WindowAttn)
 _wrp, _wabp, _wrbp = ctypes.POINTER(WindowAttnRope), ctypes.POINTER(WindowAttnBf16), ctypes.POINTER(WindowAttnRopeBf16)
+_wmp, _wmbp = ctypes.POINTER(WindowAttnMasked), ctypes.POINTER(WindowAttnMaskedBf16)
 _step_tail, _sample_tail, _u8_tail = [_dp, _vp, _sz, _vp, _vp], [_dp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp], [_dp, _vp, _sz, _vp, _i, _i, _sz, _u, _vp]
 _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (restype, argtypes)
     "gsasr_abi_version": (_i, []),
@@ -227,6 +239,13 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_window_attn_rope_bf16_scratch_bytes": (_sz, [_wrbp]),
     "gsasr_window_attn_rope_bf16_forward": (_i, [_wrbp, _vp]),
     "gsasr_window_attn_rope_bf16_backward": (_i, [_wrbp, _vp]),
+    # ... the biased one with a mask per window and packed q, k, v (gsasr_window_attn_masked, gsasr_window_attn_masked_bf16)
+    "gsasr_window_attn_masked_scratch_bytes": (_sz, [_wmp]),
+    "gsasr_window_attn_masked_forward": (_i, [_wmp, _vp]),
+    "gsasr_window_attn_masked_backward": (_i, [_wmp, _vp]),
+    "gsasr_window_attn_masked_bf16_scratch_bytes": (_sz, [_wmbp]),
+    "gsasr_window_attn_masked_bf16_forward": (_i, [_wmbp, _vp]),
+    "gsasr_window_attn_masked_bf16_backward": (_i, [_wmbp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1345,6 +1364,78 @@ def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_o
     grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, table), need)]
     _attn_backward(d, fns, q, out, stats, grad_out, **dict(zip(("g_q", "g_k", "g_v", "g_table"), grads)))
     return tuple(grads)
+
+
+# ---- the biased window attention with a mask and packed q, k, v (include/gsasr_splat.h: gsasr_window_attn_masked) ----
+def make_window_attn_masked(windows: int, heads: int, nq: int, nk: int, head_dim: int, table_rows: int, scale: float, bf16: bool = False,
+                            mask_windows: int = 0, pitches=(0, 0, 0), grad_pitches=(0, 0, 0)):
+    """a gsasr_window_attn_masked (`bf16`: gsasr_window_attn_masked_bf16) descriptor without pointers"""
+    d = (WindowAttnMaskedBf16 if bf16 else WindowAttnMasked)(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(table_rows))
+    d.scale, d.flags, d.mask_windows = float(scale), 0, int(mask_windows)
+    d.pitch_q, d.pitch_k, d.pitch_v = (int(p) for p in pitches)
+    d.pitch_gq, d.pitch_gk, d.pitch_gv = (int(p) for p in grad_pitches)
+    return d
+
+
+_MASKED_FNS = {bf16: {what: f"gsasr_window_attn_masked{'_bf16' if bf16 else ''}_{what}" for what in ("forward", "backward", "scratch_bytes")}
+               for bf16 in (False, True)}
+
+
+def _rows_view(t: torch.Tensor, name: str, bf16: bool) -> int:
+    """the row pitch (elements) of an activation `[W,n,C]` that may be a column block of a wider contiguous tensor"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == (torch.bfloat16 if bf16 else torch.float32)):
+        raise RuntimeError(f"{name} must be a {'bfloat16' if bf16 else 'float32'} CUDA tensor")
+    W, n, C = t.shape
+    pitch = t.stride(1) if n > 1 else (t.stride(0) if W > 1 else C)
+    if t.stride(2) != 1 or pitch < C or (W > 1 and t.stride(0) != n * pitch):
+        raise RuntimeError(f"{name} must be [W,n,C] with unit column stride and one row pitch (strides {tuple(t.stride())})")
+    return int(pitch)
+
+
+def _masked_desc(q, k, v, table, index, mask, scale: float):
+    """the gsasr_window_attn_masked descriptor of a call: q, k, v `[W,n,C]` each contiguous or a column block of a packed tensor
+    (their row pitches go into the descriptor), `mask` fp32 `[nW,nq,nk]` contiguous or None"""
+    bf16 = q.dtype == torch.bfloat16
+    pitches = tuple(_rows_view(t, name, bf16) for t, name in ((q, "q"), (k, "k"), (v, "v")))
+    heads = int(table.shape[1])
+    d = make_window_attn_masked(q.shape[0], heads, q.shape[1], k.shape[1], q.shape[2] // heads, table.shape[0], scale, bf16, pitches=pitches)
+    d.table = _chk(table, "bias_table")
+    d.q, d.k, d.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
+    _attn_index(d, index)
+    if mask is not None:
+        d.mask, d.mask_windows = _chk(mask, "mask", (d.nq, d.nk)), int(mask.shape[0])
+    return d, _MASKED_FNS[bf16]
+
+
+def window_attn_masked_forward(q, k, v, table, index, mask, scale: float, want_stats: bool = True):
+    """gsasr_window_attn_masked_forward (bf16 `q`, `k`, `v`: _masked_bf16_forward) -> (out `[W,nq,C]` contiguous, the rows'
+    log-sum-exp or None).  `q`, `k`, `v` may be column blocks of one packed tensor: they are read in place"""
+    d, fns = _masked_desc(q, k, v, table, index, mask, scale)
+    dev = q.device
+    with _on(dev):
+        out = torch.empty(q.shape, dtype=q.dtype, device=dev)
+        stats = torch.empty(d.windows, d.heads, d.nq, dtype=torch.float32, device=dev) if want_stats else None
+        d.out, d.stats = out.data_ptr(), None if stats is None else stats.data_ptr()
+        check(getattr(lib(), fns["forward"])(ctypes.byref(d), _stream(dev)), fns["forward"])
+    return out, stats
+
+
+def window_attn_masked_backward(q, k, v, table, index, mask, scale: float, out, stats, grad_out, need=(True, True, True, True), packed=False):
+    """gsasr_window_attn_masked_backward -> (g_q, g_k, g_v, g_table), None where `need` is False.  `packed`: g_q, g_k, g_v are the
+    column blocks of ONE `[W,n,3C]` tensor, written in place through the gradient pitches (all three are then computed)"""
+    d, fns = _masked_desc(q, k, v, table, index, mask, scale)
+    C = int(q.shape[2])
+    if packed:
+        if k.shape != q.shape:
+            raise RuntimeError("a packed gradient needs nq == nk")
+        whole = torch.empty(q.shape[0], q.shape[1], 3 * C, dtype=q.dtype, device=q.device)
+        grads = [whole[..., :C], whole[..., C:2 * C], whole[..., 2 * C:]]
+        d.pitch_gq = d.pitch_gk = d.pitch_gv = 3 * C
+    else:
+        grads = [torch.empty(t.shape, dtype=t.dtype, device=t.device) if n else None for t, n in zip((q, k, v), need)]
+    g_table = torch.empty_like(table) if need[3] else None
+    _attn_backward(d, fns, out, out, stats, grad_out, g_q=grads[0], g_k=grads[1], g_v=grads[2], g_table=g_table)
+    return (whole, g_table) if packed else (*grads, g_table)
 
 
 # ---- the decoder's window attention with a rotary embedding (include/gsasr_splat.h: gsasr_window_attn_rope) -----

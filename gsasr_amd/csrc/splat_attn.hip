@@ -47,11 +47,18 @@
 // Backward: the kernels above instantiated on the element type T = att_bf (loads widen, stores round to nearest even, the
 // rotated operands are rounded to bf16 where they are formed); the products stay on the exact-fp32 instruction.
 //
-// The host layer is written once for the four descriptor types.  AttnFamily<descriptor> (AttnBiased or AttnRotary on float or
-// att_bf) states what differs: the required pointers, the alignment rule, the head_dim and table_rows / angle_rows rules, the
-// scratch, each with its message, and the family's fields of AttnArgsT.  attn_check, attn_args, attn_forward and attn_backward
-// are templates on the descriptor and the twelve extern "C" functions one call each; a new variant is a family and its three
-// entry points.  att_pick turns the runtime (key tiles -> MAXT 3 / 9 / 16, stats, table in LDS, TAB) into template arguments;
+// The masked family (gsasr_window_attn_masked / _masked_bf16: the attention of a Swin layer, utils/swinir.py:226-257) is the
+// biased kernels with MK = true: S = (scale q k^T + B) + mask[w % mask_windows] in that order, the row's mask values loaded with
+// its biases (k_attn_fwd: the whole row up front; the backward kernels: one tile ahead, in k_attn_bwd_kv down the lane's key
+// column), and q, k, v, g_q, g_k, g_v each at its own row pitch, so that a packed [windows, n, 3 C] tensor is read and its
+// gradient written in place.  MK kernels take AttnArgsMT (AttnArgsT plus the mask and the pitches); with MK = false every
+// expression is the one it was, and the other families' kernels keep their instruction streams.
+//
+// The host layer is written once for the six descriptor types.  AttnFamily<descriptor> (AttnBiased, AttnRotary or AttnMasked on
+// float or att_bf) states what differs: the required pointers, the alignment rule, the head_dim and table_rows / angle_rows
+// rules, the scratch, each with its message, the kernels' argument type and the family's fields of it.  attn_check, attn_args,
+// attn_forward and attn_backward are templates on the descriptor and the eighteen extern "C" functions one call each; a new
+// variant is a family and its three entry points.  att_pick turns the runtime (key tiles -> MAXT 3 / 9 / 16, the masked family 3 / 4 / 9 / 16; stats, table in LDS, TAB) into template arguments;
 // the dynamic LDS of a kernel is one struct (AttLdsQ, AttLdsKV, AttLdsFwdBf) that the kernel walks to its pointers and the
 // host asks for the byte count.  The four kernels that touch no activation take AttnAux and exist once.
 #include "splat_common.h"
@@ -96,6 +103,24 @@ struct AttnArgsT {
     int ldvec;      // bf16 forward: elements per global load of q, k, v (8, 2 or 1: the head's slice is 16-, 4- or 2-byte aligned)
 };
 typedef AttnArgsT<float> AttnArgs;
+
+// the arguments of the masked family's kernels (MK): the other families' kernels keep AttnArgsT, and with it their code
+template <typename T>
+struct AttnArgsMT : AttnArgsT<T> {
+    const float *mask;      // [mwin, nq, nk], window w reads mask[w % mwin]; null: no mask
+    int mwin;               // (at least 1, so that w % mwin is defined without a mask)
+    bool mvec;              // mask rows can be read 16 bytes at a time
+    int pq, pk, pv, pgq, pgk, pgv;      // elements between consecutive rows of q, k, v and of g_q, g_k, g_v
+};
+template <typename T, bool MK> using AttArgs = std::conditional_t<MK, AttnArgsMT<T>, AttnArgsT<T>>;
+
+// what a kernel reads of them (the plain arguments: the contiguous pitch C everywhere and no mask)
+struct AttPitch { int q, k, v, gq, gk, gv; };
+struct AttMask { const float *p; int win; bool vec; };
+#define ATT_MASKED_ARGS(A, C) \
+    AttPitch P = {C, C, C, C, C, C}; \
+    AttMask M = {nullptr, 1, false}; \
+    if constexpr (MK) { P = {A.pq, A.pk, A.pv, A.pgq, A.pgk, A.pgv}; M = {A.mask, A.mwin, A.mvec}; }
 
 // what the kernels that touch no activation read (k_attn_table_sum, k_attn_table_round, k_attn_cossin, k_attn_angle_sum)
 // (no two integers that one of them reads lie side by side unless they did in AttnArgsT: each kernel keeps its scalar loads)
@@ -184,6 +209,16 @@ __device__ __forceinline__ void att_load_index(int (&ix)[4], const int *__restri
     } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) ix[r] = irow[min(j0 + r, nk - 1)];
+    }
+}
+
+// mask[row][j0 .. j0 + 3] as att_load_index reads the index: entries past nk repeat a valid one, `vec` is one 16-byte load
+__device__ __forceinline__ void att_load_mask(att_f4 &m, const float *__restrict__ mrow, int j0, int nk, bool vec)
+{
+    if (vec) m = *reinterpret_cast<const att_f4 *>(mrow + min(j0, nk - 4));
+    else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[r] = mrow[min(j0 + r, nk - 1)];
     }
 }
 
@@ -280,32 +315,46 @@ __device__ __forceinline__ AttLane att_lane() { return {(int)(threadIdx.x >> 6),
 __device__ __forceinline__ void att_shift(int &ix, int &ix1, int ixn) { ix = ix1; ix1 = ixn; }
 
 // ROPE: q and k rotated (K as it is staged, the query row in registers; rotate, then scale), no table / index / bias
-template <int MAXT, bool STATS, bool TLDS, bool ROPE = false>
-__global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
+// MK (the masked family): S = (scale q k^T + B) + mask[w % mwin], the row's mask values loaded with its biases (a uniform branch
+// around the loads when the call has no mask: + 0 then), and q, k, v read at their own row pitches
+template <int MAXT, bool STATS, bool TLDS, bool ROPE = false, bool MK = false>
+__global__ __launch_bounds__(256) void k_attn_fwd(AttArgs<float, MK> A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    ATT_MASKED_ARGS(A, C)
+    const int Cq = P.q, Ck = P.k, Cv = P.v;
     const int nt = (nk + 15) >> 4, nkp = nt << 4;
     const AttLdsQ L(nk, TLDS ? A.rows : 0);
     float *s_k = s_mem, *s_v = s_k + L.kv, *s_tb = s_v + L.kv;
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
-    if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * C + h * d, cs, nk, nkp, d, C, 1.f);
-    else att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
-    att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+    if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * Ck + h * d, cs, nk, nkp, d, Ck, 1.f);
+    else att_stage(s_k, A.k + (size_t)w * nk * Ck + h * d, nk, nkp, d, Ck, 1.f);
+    att_stage(s_v, A.v + (size_t)w * nk * Cv + h * d, nk, nkp, d, Cv, 1.f);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
     const auto [wave, nwaves, c16, g] = att_lane();
     const int nqt = (nq + 15) >> 4;
+    const float *mwin = MK && M.p ? M.p + (size_t)(w % M.win) * nq * nk : nullptr;
     for (int qt = wave; qt < nqt; qt += nwaves) {
         const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
         float qr[8];
-        if (ROPE) att_load_row_rot(qr, A.q + ((size_t)w * nq + ic) * C + h * d, cs + ic * (d >> 1), g, d, true, A.scale);
-        else att_load_row(qr, A.q + ((size_t)w * nq + ic) * C + h * d, g, d, true, A.scale);
+        if (ROPE) att_load_row_rot(qr, A.q + ((size_t)w * nq + ic) * Cq + h * d, cs + ic * (d >> 1), g, d, true, A.scale);
+        else att_load_row(qr, A.q + ((size_t)w * nq + ic) * Cq + h * d, g, d, true, A.scale);
         att_f4 sc[MAXT];
         const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
         float m = -INFINITY;
         att_f4 bs[ROPE ? 1 : MAXT];         // (the whole row's biases first)
+        att_f4 ms[MK ? MAXT : 1];           // (and its mask values)
+        if (MK) {
+#pragma unroll
+            for (int t = 0; t < (MK ? MAXT : 0); ++t) ms[t] = att_f4{0.f, 0.f, 0.f, 0.f};
+            if (mwin) {
+#pragma unroll
+                for (int t = 0; t < (MK ? MAXT : 0); ++t) att_load_mask(ms[t], mwin + (size_t)ic * nk, 16 * t + 4 * g, nk, M.vec);
+            }
+        }
 #pragma unroll
         for (int t = 0; t < (ROPE ? 0 : MAXT); ++t) {
             int ix[4];
@@ -319,7 +368,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs A)
                 sc[t] = att_tile(s_k, 16 * t, c16, g, qr);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    sc[t][r] = 16 * t + 4 * g + r < nk ? (ROPE ? sc[t][r] : sc[t][r] + bs[ROPE ? 0 : t][r]) : -INFINITY;
+                    sc[t][r] = 16 * t + 4 * g + r < nk ? (ROPE ? sc[t][r] : MK ? (sc[t][r] + bs[ROPE ? 0 : t][r]) + ms[MK ? t : 0][r] : sc[t][r] + bs[ROPE ? 0 : t][r]) : -INFINITY;
                     m = fmaxf(m, sc[t][r]);
                 }
             }
@@ -399,9 +448,9 @@ __device__ __forceinline__ unsigned att_rot_pair(unsigned w, float2 t)
 
 // the head's slices of K (rotated when ROPE) and V, rows [0, nk) x columns [0, d), into s_k[nkp32][ATT_KLD] and s_vt[32][vld],
 // zero elsewhere.  U loads of K and of V in flight per thread before the first LDS store
-template <int VEC, bool ROPE>
+template <int VEC, bool ROPE, bool MK = false>
 __device__ __forceinline__ void att_stage_kv_bf(att_bf *s_k, att_bf *s_vt, const att_bf *__restrict__ ksrc, const att_bf *__restrict__ vsrc,
-                                                const float2 *__restrict__ cs, int nk, int nkp32, int vld, int d, int C)
+                                                const float2 *__restrict__ cs, int nk, int nkp32, int vld, int d, int Ck, int Cv)
 {
     constexpr int CPR = 32 / VEC, NW = (VEC + 1) / 2, U = VEC == 8 ? 2 : 4;
     const int nthr = blockDim.x, total = nkp32 * CPR, hd = d >> 1;
@@ -411,8 +460,8 @@ __device__ __forceinline__ void att_stage_kv_bf(att_bf *s_k, att_bf *s_vt, const
         for (int u = 0; u < U; ++u) {
             const int e = e0 + nthr * u, j = e / CPR, cc = (e % CPR) * VEC;
             const bool ok = e < total && j < nk && cc < d;
-            att_ld_raw<VEC>(kw[u], ksrc + (size_t)j * C + cc, ok);
-            att_ld_raw<VEC>(vw[u], vsrc + (size_t)j * C + cc, ok);
+            att_ld_raw<VEC>(kw[u], ksrc + (size_t)j * Ck + cc, ok);
+            att_ld_raw<VEC>(vw[u], vsrc + (size_t)j * (MK ? Cv : Ck) + cc, ok);
             if constexpr (ROPE && VEC > 1) {
 #pragma unroll
                 for (int i = 0; i < NW; ++i) kw[u][i] = att_rot_pair(kw[u][i], ok ? cs[j * hd + (cc >> 1) + i] : make_float2(0.f, 0.f));
@@ -467,29 +516,32 @@ struct AttLdsFwdBf {
 // The geometry of k_attn_fwd (one workgroup per (window, head), a wave takes 16 queries, the lane holds its query's whole score
 // row in fp32: one maximum, one sum of the unrounded p).  scale multiplies the fp32 score sum; p is rounded to bf16 only as the
 // operand of P V; out is rounded once at the store.  include/gsasr_splat.h has the contract.
-template <int MAXT, bool STATS, bool TLDS, bool ROPE>
-__global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
+template <int MAXT, bool STATS, bool TLDS, bool ROPE, bool MK = false>
+__global__ __launch_bounds__(256) void k_attn_fwd_bf(AttArgs<att_bf, MK> A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    ATT_MASKED_ARGS(A, C)
+    const int Cq = P.q, Ck = P.k, Cv = P.v;
     const int nt = (nk + 15) >> 4;
     const AttLdsFwdBf L(nk, TLDS ? A.rows : 0);
     const int nkp32 = L.nkp32, vld = L.vld;
     att_bf *s_k = reinterpret_cast<att_bf *>(s_mem), *s_vt = s_k + L.k;
     float *s_tb = reinterpret_cast<float *>(s_vt + L.vt);
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
-    const att_bf *ksrc = A.k + (size_t)w * nk * C + h * d, *vsrc = A.v + (size_t)w * nk * C + h * d;
-    if (A.ldvec == 8) att_stage_kv_bf<8, ROPE>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
-    else if (A.ldvec == 2) att_stage_kv_bf<2, ROPE>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
-    else if (!ROPE) att_stage_kv_bf<1, false>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, C);
+    const att_bf *ksrc = A.k + (size_t)w * nk * Ck + h * d, *vsrc = A.v + (size_t)w * nk * Cv + h * d;
+    if (A.ldvec == 8) att_stage_kv_bf<8, ROPE, MK>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, Ck, Cv);
+    else if (A.ldvec == 2) att_stage_kv_bf<2, ROPE, MK>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, Ck, Cv);
+    else if (!ROPE) att_stage_kv_bf<1, false, MK>(s_k, s_vt, ksrc, vsrc, cs, nk, nkp32, vld, d, Ck, Cv);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
     const auto [wave, nwaves, c16, g] = att_lane();
     const int nqt = (nq + 15) >> 4;
+    const float *mwin = MK && M.p ? M.p + (size_t)(w % M.win) * nq * nk : nullptr;
     for (int qt = wave; qt < nqt; qt += nwaves) {
         const int i = qt * 16 + c16, ic = min(i, nq - 1);       // (rows past nq repeat the last query and are not stored)
-        const att_bf *qrow = A.q + ((size_t)w * nq + ic) * C + h * d;
+        const att_bf *qrow = A.q + ((size_t)w * nq + ic) * Cq + h * d;
         const float2 *qcs = ROPE ? cs + ic * (d >> 1) : nullptr;
         att_bf8 qf;
         if (A.ldvec == 8) qf = att_load_q_bf<8, ROPE>(qrow, qcs, g, d);
@@ -499,6 +551,15 @@ __global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
         const int *irow = ROPE ? nullptr : A.index + (size_t)ic * nk;
         float m = -INFINITY;
         att_f4 bs[ROPE ? 1 : MAXT];         // (the whole row's biases first)
+        att_f4 ms[MK ? MAXT : 1];           // (and its mask values)
+        if (MK) {
+#pragma unroll
+            for (int t = 0; t < (MK ? MAXT : 0); ++t) ms[t] = att_f4{0.f, 0.f, 0.f, 0.f};
+            if (mwin) {
+#pragma unroll
+                for (int t = 0; t < (MK ? MAXT : 0); ++t) att_load_mask(ms[t], mwin + (size_t)ic * nk, 16 * t + 4 * g, nk, M.vec);
+            }
+        }
 #pragma unroll
         for (int t = 0; t < (ROPE ? 0 : MAXT); ++t) {
             int ix[4];
@@ -515,7 +576,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float s = sc[t][r] * A.scale;         // (the fp32 sum times scale, then the fp32 bias)
-                    sc[t][r] = 16 * t + 4 * g + r < nk ? (ROPE ? s : s + bs[ROPE ? 0 : t][r]) : -INFINITY;
+                    sc[t][r] = 16 * t + 4 * g + r < nk ? (ROPE ? s : MK ? (s + bs[ROPE ? 0 : t][r]) + ms[MK ? t : 0][r] : s + bs[ROPE ? 0 : t][r]) : -INFINITY;
                     m = fmaxf(m, sc[t][r]);
                 }
             }
@@ -562,12 +623,15 @@ __global__ __launch_bounds__(256) void k_attn_fwd_bf(AttnArgsT<att_bf> A)
 // TAB: 0 no table gradient, 1 binned in LDS -> a partial column, 2 global double atomics on the scratch's [rows, heads]
 // ROPE (TAB 0, no table): K staged rotated, the query row rotated in registers, dq times the conjugate at the store
 // T: the activations' element type (bf16: loads widen as they stage, delta is of the bf16 out that was stored, dq is rounded at the store)
-template <int TAB, bool TLDS, bool ROPE = false, typename T = float>
-__global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
+// MK: the mask of the window being walked (w, not the slot) joins S after the bias, one tile ahead; own pitches for q, k, v, g_q
+template <int TAB, bool TLDS, bool ROPE = false, typename T = float, bool MK = false>
+__global__ __launch_bounds__(256) void k_attn_bwd_q(AttArgs<T, MK> A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int slot = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    ATT_MASKED_ARGS(A, C)
+    const int Cq = P.q, Ck = P.k, Cv = P.v, Cgq = P.gq;
     const int nt = (nk + 15) >> 4, nkp = nt << 4, nqt = (nq + 15) >> 4;
     const AttLdsQ L(nk, TLDS ? A.rows : 0, TAB == 1 ? A.rows : 0);
     float *s_k = s_mem, *s_v = s_k + L.kv, *s_tb = s_v + L.kv, *s_tab = s_tb + L.tb;
@@ -577,17 +641,19 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
     if (TLDS) att_stage_table(s_tb, A, h);
     for (int w = slot; w < A.windows; w += A.wslots) {
         __syncthreads();        // (the previous window's reads of s_k / s_v are done; s_tab is zeroed)
-        if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * C + h * d, cs, nk, nkp, d, C, 1.f);
-        else att_stage(s_k, A.k + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
-        att_stage(s_v, A.v + (size_t)w * nk * C + h * d, nk, nkp, d, C, 1.f);
+        if (ROPE) att_stage_rot(s_k, A.k + (size_t)w * nk * Ck + h * d, cs, nk, nkp, d, Ck, 1.f);
+        else att_stage(s_k, A.k + (size_t)w * nk * Ck + h * d, nk, nkp, d, Ck, 1.f);
+        att_stage(s_v, A.v + (size_t)w * nk * Cv + h * d, nk, nkp, d, Cv, 1.f);
         __syncthreads();
+        const float *mwin = MK && M.p ? M.p + (size_t)(w % M.win) * nq * nk : nullptr;
         for (int qt = wave; qt < nqt; qt += nwaves) {
             const int i = qt * 16 + c16, ic = min(i, nq - 1);
             const bool iv = i < nq;
             const size_t qoff = ((size_t)w * nq + ic) * C + h * d;
             float qr[8], gr[8], orow[8];
-            if (ROPE) att_load_row_rot(qr, A.q + qoff, cs + ic * (d >> 1), g, d, true, A.scale);
-            else att_load_row(qr, A.q + qoff, g, d, true, A.scale);
+            const size_t qrow = MK ? ((size_t)w * nq + ic) * Cq + h * d : qoff;
+            if (ROPE) att_load_row_rot(qr, A.q + qrow, cs + ic * (d >> 1), g, d, true, A.scale);
+            else att_load_row(qr, A.q + qrow, g, d, true, A.scale);
             att_load_row(gr, A.grad_out + qoff, g, d, iv, 1.f);
             att_load_row(orow, A.out + qoff, g, d, iv, 1.f);
             float delta = 0.f;
@@ -604,9 +670,13 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
                 att_load_index(ix, irow, 4 * g, nk, A.vec);
                 att_load_index(ix1, irow, 16 + 4 * g, nk, A.vec);
             }
+            att_f4 mk = {0.f, 0.f, 0.f, 0.f};       // (MK: this tile's mask values, the next tile's loaded under this one's products)
+            if (MK && mwin) att_load_mask(mk, mwin + (size_t)ic * nk, 4 * g, nk, M.vec);
             for (int t = 0; t < nt; ++t) {
                 float b[4];
                 int ixn[4];     // (two tiles ahead: one tile's products are shorter than a round trip to L2)
+                att_f4 mkn = {0.f, 0.f, 0.f, 0.f};
+                if (MK && mwin) att_load_mask(mkn, mwin + (size_t)ic * nk, 16 * t + 16 + 4 * g, nk, M.vec);
                 if (!ROPE) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) b[r] = att_bias<TLDS>(s_tb, A.table, A.heads, h, ix[r]);
@@ -627,12 +697,13 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
                 for (int r = 0; r < 4; ++r) {
                     const int j = 16 * t + 4 * g + r;
                     const bool valid = iv && j < nk;
-                    const float p = valid ? att_exp((ROPE ? sc[r] : sc[r] + b[r]) - lse) : 0.f;
+                    const float p = valid ? att_exp((ROPE ? sc[r] : MK ? (sc[r] + b[r]) + mk[r] : sc[r] + b[r]) - lse) : 0.f;
                     ds[r] = p * (dp[r] - delta);
                     if (TAB == 1 && valid) atomicAdd(&s_tab[ix[r]], ds[r]);
                     if (TAB == 2 && valid) atomicAdd(reinterpret_cast<double *>(A.part) + (size_t)ix[r] * A.heads + h, (double)ds[r]);
                     att_shift(ix[r], ix1[r], ixn[r]);
                 }
+                if (MK) mk = mkn;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     dq0 = att_mfma(ds[r], k0[r], dq0);
@@ -649,7 +720,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_q(AttnArgsT<T> A)
                         u1 = att_unrot(dq1[r] * A.scale, cs, min(io, nq - 1), d >> 1, c16 + 16, d);
                     }
                     if (io < nq) {
-                        T *po = A.g_q + ((size_t)w * nq + io) * C + h * d;
+                        T *po = A.g_q + ((size_t)w * nq + io) * Cgq + h * d;
                         if (c16 < d) att_st(po + c16, ROPE ? u0 : dq0[r] * A.scale);
                         if (c16 + 16 < d) att_st(po + c16 + 16, ROPE ? u1 : dq1[r] * A.scale);
                     }
@@ -690,19 +761,23 @@ __global__ __launch_bounds__(256) void k_attn_table_round(AttnAux A)
 }
 
 // ROPE: scale Q staged rotated, the key row rotated in registers, dk times the conjugate at the store
-template <bool TLDS, bool ROPE = false, typename T = float>
-__global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
+// MK: the mask column of the lane's key (mask[w % mwin][query][key]: the key is on the lane here), one tile ahead; own pitches
+template <bool TLDS, bool ROPE = false, typename T = float, bool MK = false>
+__global__ __launch_bounds__(256) void k_attn_bwd_kv(AttArgs<T, MK> A)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int w = blockIdx.x / A.heads, h = blockIdx.x % A.heads;
     const int nq = A.nq, nk = A.nk, d = A.d, C = A.heads * A.d;
+    ATT_MASKED_ARGS(A, C)
+    const int Cq = P.q, Ck = P.k, Cv = P.v, Cgk = P.gk, Cgv = P.gv;
     const int nqt = (nq + 15) >> 4, nqp = nqt << 4, nkt = (nk + 15) >> 4;
     const AttLdsKV L(nq, TLDS ? A.rows : 0);
     float *s_q = s_mem, *s_g = s_q + L.qg, *s_lse = s_g + L.qg, *s_delta = s_lse + L.nqp, *s_tb = s_delta + L.nqp;
     const size_t qbase = (size_t)w * nq * C + h * d;
     const float2 *cs = ROPE ? reinterpret_cast<const float2 *>(A.cossin) + (size_t)h * A.arows * (d >> 1) : nullptr;
-    if (ROPE) att_stage_rot(s_q, A.q + qbase, cs, nq, nqp, d, C, A.scale);
-    else att_stage(s_q, A.q + qbase, nq, nqp, d, C, A.scale);
+    const size_t qsrc = MK ? (size_t)w * nq * Cq + h * d : qbase;
+    if (ROPE) att_stage_rot(s_q, A.q + qsrc, cs, nq, nqp, d, Cq, A.scale);
+    else att_stage(s_q, A.q + qsrc, nq, nqp, d, Cq, A.scale);
     att_stage(s_g, A.grad_out + qbase, nq, nqp, d, C, 1.f);
     if (TLDS) att_stage_table(s_tb, A, h);
     __syncthreads();
@@ -717,14 +792,15 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
     }
     __syncthreads();
     const auto [wave, nwaves, c16, g] = att_lane();
+    const float *mwin = MK && M.p ? M.p + (size_t)(w % M.win) * nq * nk : nullptr;
     for (int kt = wave; kt < nkt; kt += nwaves) {
         const int j = kt * 16 + c16, jc = min(j, nk - 1);
         const bool jv = j < nk;
-        const size_t koff = ((size_t)w * nk + jc) * C + h * d;
+        const size_t koff = ((size_t)w * nk + jc) * Ck + h * d, voff = MK ? ((size_t)w * nk + jc) * Cv + h * d : koff;
         float kr[8], vr[8];
         if (ROPE) att_load_row_rot(kr, A.k + koff, cs + jc * (d >> 1), g, d, jv, 1.f);
         else att_load_row(kr, A.k + koff, g, d, jv, 1.f);
-        att_load_row(vr, A.v + koff, g, d, jv, 1.f);
+        att_load_row(vr, A.v + voff, g, d, jv, 1.f);
         att_f4 dk0 = {0.f, 0.f, 0.f, 0.f}, dk1 = dk0, dv0 = dk0, dv1 = dk0;
         int ix[4], ix1[4];      // (loaded two tiles ahead, unconditionally: as in k_attn_bwd_q)
         if (!ROPE) {
@@ -734,9 +810,19 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
                 ix1[r] = A.index[(size_t)min(16 + 4 * g + r, nq - 1) * nk + jc];
             }
         }
+        float mk[4] = {0.f, 0.f, 0.f, 0.f};     // (MK: as in k_attn_bwd_q, the queries 4 g + r of the tile at the lane's key)
+        if (MK && mwin) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mk[r] = mwin[(size_t)min(4 * g + r, nq - 1) * nk + jc];
+        }
         for (int t = 0; t < nqt; ++t) {
             float b[4];
             int ixn[4];
+            float mkn[4] = {0.f, 0.f, 0.f, 0.f};
+            if (MK && mwin) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mkn[r] = mwin[(size_t)min(16 * t + 16 + 4 * g + r, nq - 1) * nk + jc];
+            }
             if (!ROPE) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -758,9 +844,10 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int i = 16 * t + 4 * g + r;
-                p[r] = (jv && i < nq) ? att_exp((ROPE ? sc[r] : sc[r] + b[r]) - lse[r]) : 0.f;
+                p[r] = (jv && i < nq) ? att_exp((ROPE ? sc[r] : MK ? (sc[r] + b[r]) + mk[r] : sc[r] + b[r]) - lse[r]) : 0.f;
                 ds[r] = p[r] * (dp[r] - dl[r]);
                 att_shift(ix[r], ix1[r], ixn[r]);
+                if (MK) mk[r] = mkn[r];
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -779,14 +866,14 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnArgsT<T> A)
                 u1 = att_unrot(dk1[r], cs, min(jo, nk - 1), d >> 1, c16 + 16, d);
             }
             if (jo < nk) {
-                const size_t off = ((size_t)w * nk + jo) * C + h * d;
+                const size_t off = ((size_t)w * nk + jo) * Cgk + h * d, offv = MK ? ((size_t)w * nk + jo) * Cgv + h * d : off;
                 if (A.g_k) {
                     if (c16 < d) att_st(A.g_k + off + c16, ROPE ? u0 : dk0[r]);
                     if (c16 + 16 < d) att_st(A.g_k + off + c16 + 16, ROPE ? u1 : dk1[r]);
                 }
                 if (A.g_v) {
-                    if (c16 < d) att_st(A.g_v + off + c16, dv0[r]);
-                    if (c16 + 16 < d) att_st(A.g_v + off + c16 + 16, dv1[r]);
+                    if (c16 < d) att_st(A.g_v + offv + c16, dv0[r]);
+                    if (c16 + 16 < d) att_st(A.g_v + offv + c16 + 16, dv1[r]);
                 }
             }
         }
@@ -865,7 +952,8 @@ inline bool attn_misaligned(uintptr_t to, std::initializer_list<const void *> ps
 template <typename D, typename ELEM>
 struct AttnBiased {
     typedef ELEM T;
-    static constexpr bool ROPE = false;
+    static constexpr bool ROPE = false, MASKED = false;
+    typedef AttnArgsT<ELEM> ARGS;
     static constexpr const char *NULL_DESC = "null window-attention descriptor", *TOO_MANY = "windows * heads or table_rows * heads exceeds 2^31 - 1";
     static const char *bad_size(const D *a)
     {
@@ -908,7 +996,8 @@ struct AttnBiased {
 template <typename D, typename ELEM>
 struct AttnRotary {
     typedef ELEM T;
-    static constexpr bool ROPE = true;
+    static constexpr bool ROPE = true, MASKED = false;
+    typedef AttnArgsT<ELEM> ARGS;
     static constexpr const char *NULL_DESC = "null rotary window-attention descriptor", *TOO_MANY = "windows * heads or heads * angle_rows * head_dim / 2 exceeds 2^31 - 1";
     static const char *bad_size(const D *a)
     {
@@ -953,7 +1042,46 @@ struct AttnRotary {
     }
 };
 
+// the masked family (gsasr_window_attn_masked, gsasr_window_attn_masked_bf16): the biased family's rules and fields, a mask
+// per window modulo mask_windows and a row pitch for each of q, k, v, g_q, g_k, g_v (0: heads * head_dim)
+template <typename D, typename ELEM>
+struct AttnMasked : AttnBiased<D, ELEM> {
+    typedef AttnBiased<D, ELEM> B;
+    typedef ELEM T;
+    static constexpr bool MASKED = true;
+    typedef AttnArgsMT<ELEM> ARGS;
+    static const char *bad_size(const D *a)
+    {
+        if (const char *msg = B::bad_size(a)) return msg;
+        if (a->mask_windows < 0) return "mask_windows must not be negative";
+        if (a->mask_windows && a->windows % a->mask_windows) return "windows must be a multiple of mask_windows";
+        const long long c = (long long)a->heads * a->head_dim;
+        for (long long p : {a->pitch_q, a->pitch_k, a->pitch_v, a->pitch_gq, a->pitch_gk, a->pitch_gv})
+            if (p && p < c) return "a non-zero pitch must be at least heads * head_dim";
+        return nullptr;
+    }
+    static const char *missing(const D *a, bool bwd)
+    {
+        if (const char *msg = B::missing(a, bwd)) return msg;
+        return (a->mask != nullptr) != (a->mask_windows != 0) ? "mask and mask_windows must be set together (NULL and 0: no mask)" : nullptr;
+    }
+    static void fill(AttnArgsMT<T> &A, const D *a)
+    {
+        B::fill(A, a);
+        const long long c = (long long)a->heads * a->head_dim;
+        auto pitch = [c](long long p) { return p ? p : c; };
+        A.mask = a->mask; A.mwin = a->mask_windows > 0 ? a->mask_windows : 1;
+        A.mvec = a->nk % 4 == 0 && ((uintptr_t)a->mask & 15) == 0;
+        A.pq = pitch(a->pitch_q); A.pk = pitch(a->pitch_k); A.pv = pitch(a->pitch_v);
+        A.pgq = pitch(a->pitch_gq); A.pgk = pitch(a->pitch_gk); A.pgv = pitch(a->pitch_gv);
+        // the bf16 forward's load width: every row of q, k, v must keep the alignment of the first (attn_args has the bases)
+        if (sizeof(T) == 2 && A.ldvec > 1 && ((A.pq | A.pk | A.pv) & (A.ldvec - 1))) A.ldvec = (A.pq | A.pk | A.pv) & 1 ? 1 : 2;
+    }
+};
+
 template <typename D> struct AttnFamily;
+template <> struct AttnFamily<gsasr_window_attn_masked> : AttnMasked<gsasr_window_attn_masked, float> {};
+template <> struct AttnFamily<gsasr_window_attn_masked_bf16> : AttnMasked<gsasr_window_attn_masked_bf16, att_bf> {};
 template <> struct AttnFamily<gsasr_window_attn> : AttnBiased<gsasr_window_attn, float> {};
 template <> struct AttnFamily<gsasr_window_attn_bf16> : AttnBiased<gsasr_window_attn_bf16, att_bf> {};
 template <> struct AttnFamily<gsasr_window_attn_rope> : AttnRotary<gsasr_window_attn_rope, float> {};
@@ -982,9 +1110,9 @@ template <typename D>
 size_t attn_scratch_bytes(const D *a) { return attn_check(a) ? 0 : 256 + AttnFamily<D>::scratch(a); }
 
 template <typename D>
-AttnArgsT<typename AttnFamily<D>::T> attn_args(const D *a)
+typename AttnFamily<D>::ARGS attn_args(const D *a)
 {
-    AttnArgsT<typename AttnFamily<D>::T> A = {};
+    typename AttnFamily<D>::ARGS A = {};
     A.q = a->q; A.k = a->k; A.v = a->v; A.out = a->out; A.o = a->out; A.stats = a->stats;
     A.grad_out = a->grad_out; A.g_q = a->g_q; A.g_k = a->g_k; A.g_v = a->g_v; A.part = (float *)a->scratch;
     A.windows = a->windows; A.heads = a->heads; A.nq = a->nq; A.nk = a->nk; A.d = a->head_dim; A.scale = a->scale;
@@ -1029,18 +1157,23 @@ int attn_forward(const D *a, void *stream)
     typedef AttnFamily<D> F;
     typedef typename F::T T;
     if (int rc = attn_check(a, 1)) return rc;
-    const AttnArgsT<T> A = attn_args(a);
+    const typename F::ARGS A = attn_args(a);
     hipStream_t st = (hipStream_t)stream;
     if (F::ROPE) if (int rc = attn_launch(k_attn_cossin, (unsigned)((A.heads * A.arows * (A.d / 2) + 255) / 256), 4, 0, st, attn_aux(A))) return rc;
     const unsigned grid = (unsigned)(A.windows * A.heads);
     const int waves = attn_waves(A.nq);
     const bool tlds = !F::ROPE && A.rows <= ATT_TAB_LDS;
-    return att_pick<3, 9, 16>((A.nk + 15) / 16, [&](auto maxt) { return att_pick<0, 1>(A.stats != nullptr, [&](auto stats) { return att_pick<0, 1>(tlds, [&](auto tl) {
+    // MAXT by the key tiles.  The masked family has one for exactly four: SwinIR's 64 keys, where it is a third shorter than MAXT 9
+    // (DESIGN.md 3.2i); the other families' shipped shapes have 9 and 16 tiles and keep their three
+    auto launch = [&](auto maxt) {
+        return att_pick<0, 1>(A.stats != nullptr, [&](auto stats) { return att_pick<0, 1>(tlds, [&](auto tl) {
         constexpr int MAXT = decltype(maxt)::value;
         constexpr bool STATS = decltype(stats)::value, TLDS = decltype(tl)::value && !F::ROPE;
-        if constexpr (sizeof(T) == 2) return attn_launch(k_attn_fwd_bf<MAXT, STATS, TLDS, F::ROPE>, grid, waves, AttLdsFwdBf(A.nk, TLDS ? A.rows : 0).bytes(), st, A);
-        else return attn_launch(k_attn_fwd<MAXT, STATS, TLDS, F::ROPE>, grid, waves, AttLdsQ(A.nk, TLDS ? A.rows : 0).bytes(), st, A);
-    }); }); });
+        if constexpr (sizeof(T) == 2) return attn_launch(k_attn_fwd_bf<MAXT, STATS, TLDS, F::ROPE, F::MASKED>, grid, waves, AttLdsFwdBf(A.nk, TLDS ? A.rows : 0).bytes(), st, A);
+        else return attn_launch(k_attn_fwd<MAXT, STATS, TLDS, F::ROPE, F::MASKED>, grid, waves, AttLdsQ(A.nk, TLDS ? A.rows : 0).bytes(), st, A);
+    }); }); };
+    if constexpr (F::MASKED) return att_pick<3, 4, 9, 16>((A.nk + 15) / 16, launch);
+    else return att_pick<3, 9, 16>((A.nk + 15) / 16, launch);
 }
 
 // d table after k_attn_bwd_q: the partial columns added in a fixed order (TAB 1), or the double sums rounded (TAB 2)
@@ -1068,7 +1201,7 @@ int attn_backward(const D *a, void *stream)
     typedef AttnFamily<D> F;
     typedef typename F::T T;
     if (int rc = attn_check(a, 2)) return rc;
-    const AttnArgsT<T> A = attn_args(a);
+    const typename F::ARGS A = attn_args(a);
     hipStream_t st = (hipStream_t)stream;
     const int tab = F::tab(a);
     const bool tlds = !F::ROPE && A.rows <= ATT_TAB_LDS;
@@ -1078,7 +1211,7 @@ int attn_backward(const D *a, void *stream)
         int rc = att_pick<0, 1, 2>(tab, [&](auto t) { return att_pick<0, 1>(tlds, [&](auto tl) {
             constexpr int TAB = F::ROPE ? 0 : decltype(t)::value;
             constexpr bool TLDS = TAB == 1 || (TAB == 0 && !F::ROPE && decltype(tl)::value);     // (TAB 1 is the table in LDS, TAB 2 is not)
-            return attn_launch(k_attn_bwd_q<TAB, TLDS, F::ROPE, T>, (unsigned)(A.wslots * A.heads), attn_waves(A.nq), lds, st, A);
+            return attn_launch(k_attn_bwd_q<TAB, TLDS, F::ROPE, T, F::MASKED>, (unsigned)(A.wslots * A.heads), attn_waves(A.nq), lds, st, A);
         }); });
         if (!rc && tab) rc = attn_table_tail(A, tab, st);
         if (rc) return rc;
@@ -1087,7 +1220,7 @@ int attn_backward(const D *a, void *stream)
         const size_t lds = AttLdsKV(A.nq, tlds ? A.rows : 0).bytes();
         if (int rc = att_pick<0, 1>(tlds, [&](auto tl) {
                 constexpr bool TLDS = decltype(tl)::value && !F::ROPE;
-                return attn_launch(k_attn_bwd_kv<TLDS, F::ROPE, T>, (unsigned)(A.windows * A.heads), attn_waves(A.nk), lds, st, A);
+                return attn_launch(k_attn_bwd_kv<TLDS, F::ROPE, T, F::MASKED>, (unsigned)(A.windows * A.heads), attn_waves(A.nk), lds, st, A);
             })) return rc;
     }
     return F::ROPE ? attn_angle_tail(A, st) : GSASR_OK;
@@ -1109,6 +1242,15 @@ int gsasr_window_attn_rope_backward(const gsasr_window_attn_rope *a, void *strea
 size_t gsasr_window_attn_bf16_scratch_bytes(const gsasr_window_attn_bf16 *a) { return attn_scratch_bytes(a); }
 int gsasr_window_attn_bf16_forward(const gsasr_window_attn_bf16 *a, void *stream) { return attn_forward(a, stream); }
 int gsasr_window_attn_bf16_backward(const gsasr_window_attn_bf16 *a, void *stream) { return attn_backward(a, stream); }
+
+// the masked family: a mask per window (modulo mask_windows) after the bias, q, k, v and their gradients at their own row pitches
+size_t gsasr_window_attn_masked_scratch_bytes(const gsasr_window_attn_masked *a) { return attn_scratch_bytes(a); }
+int gsasr_window_attn_masked_forward(const gsasr_window_attn_masked *a, void *stream) { return attn_forward(a, stream); }
+int gsasr_window_attn_masked_backward(const gsasr_window_attn_masked *a, void *stream) { return attn_backward(a, stream); }
+
+size_t gsasr_window_attn_masked_bf16_scratch_bytes(const gsasr_window_attn_masked_bf16 *a) { return attn_scratch_bytes(a); }
+int gsasr_window_attn_masked_bf16_forward(const gsasr_window_attn_masked_bf16 *a, void *stream) { return attn_forward(a, stream); }
+int gsasr_window_attn_masked_bf16_backward(const gsasr_window_attn_masked_bf16 *a, void *stream) { return attn_backward(a, stream); }
 
 size_t gsasr_window_attn_rope_bf16_scratch_bytes(const gsasr_window_attn_rope_bf16 *a) { return attn_scratch_bytes(a); }
 int gsasr_window_attn_rope_bf16_forward(const gsasr_window_attn_rope_bf16 *a, void *stream) { return attn_forward(a, stream); }

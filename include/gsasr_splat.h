@@ -784,6 +784,72 @@ GSASR_API size_t gsasr_window_attn_rope_bf16_scratch_bytes(const gsasr_window_at
 GSASR_API int gsasr_window_attn_rope_bf16_forward(const gsasr_window_attn_rope_bf16 *attn, void *stream);
 GSASR_API int gsasr_window_attn_rope_bf16_backward(const gsasr_window_attn_rope_bf16 *attn, void *stream);
 
+/* The biased window attention with an additive mask per window and q, k, v read in place from a packed tensor: the attention
+ * of a Swin layer (SwinIR's WindowAttention, utils/swinir.py:226-257 -- one Linear writes [windows, n, 3 heads head_dim], every
+ * second layer adds its shifted-window mask).  gsasr_window_attn's formulas, layouts, limits and guarantees, word for word
+ * (exact softmax over the whole row, the log-sum-exp statistic, one owner per output row and no atomics for out, g_q, g_k, g_v,
+ * the table gradient's two paths), with
+ *
+ *   S = (scale q[w, :, h] k[w, :, h]^T + B_h) + M_(w mod mask_windows)      in this order of fp32 additions (torch's)
+ *
+ *   mask           const float [mask_windows, nq, nk], fp32 for both element types; window w reads mask[w % mask_windows];
+ *                  windows % mask_windows == 0.  mask == NULL with mask_windows == 0: no mask.  The entries must be finite --
+ *                  NOT checked here, like the index (a row of -inf has no softmax).  The mask gets no gradient.
+ *   pitch_q, pitch_k, pitch_v   elements between consecutive rows of q / k / v: row (w, i) of q starts at
+ *                  q + (w nq + i) pitch_q, of k and v at k + (w nk + j) pitch_k and v + (w nk + j) pitch_v.  0 = heads * head_dim
+ *                  (contiguous).  A packed qkv tensor [windows, n, 3 C], C = heads * head_dim: q = qkv, k = qkv + C,
+ *                  v = qkv + 2 C, all three pitches 3 C.
+ *   pitch_gq, pitch_gk, pitch_gv   the same for g_q, g_k, g_v (one [windows, n, 3 C] gradient is written in place).
+ *                  out, grad_out and stats stay contiguous.
+ *
+ * The forward and both backward kernels form S by the same chain, mask included: the statistic is of the forward's bits.
+ * gsasr_window_attn_masked_bf16 follows the bf16 contract above; the mask is added to the fp32 score sum after `scale` and the
+ * bias.  Its forward chooses the load width from the base pointers AND the pitches (16 bytes: head_dim % 8 == 0, 16-byte aligned
+ * q, k, v and pitches that are multiples of 8; 4 bytes: an even head_dim, 4-byte aligned q, k, v, even pitches; else 2 bytes;
+ * a pitch counts elements, so every pitch keeps the 2-byte rule).  Mask rows are read 16 bytes at a time when nk % 4 == 0 and
+ * mask is 16-byte aligned.
+ * GSASR_ERR_ARG before anything is enqueued: what gsasr_window_attn (or _bf16) refuses; mask_windows < 0; windows not a
+ * multiple of mask_windows; mask without mask_windows or mask_windows without mask; a non-zero pitch below heads * head_dim. */
+typedef struct gsasr_window_attn_masked {
+    int windows, heads, nq, nk, head_dim, table_rows;
+    float scale;
+    unsigned flags;       /* 0 (none defined) */
+    const float *q, *k, *v, *table;
+    const int *index;
+    float *out;           /* written by the forward, read by the backward */
+    float *stats;
+    const float *grad_out;
+    float *g_q, *g_k, *g_v, *g_table;
+    void *scratch;
+    const float *mask;
+    int mask_windows;
+    int pitch_q, pitch_k, pitch_v, pitch_gq, pitch_gk, pitch_gv;
+} gsasr_window_attn_masked;
+GSASR_API size_t gsasr_window_attn_masked_scratch_bytes(const gsasr_window_attn_masked *attn);   /* as gsasr_window_attn_scratch_bytes */
+GSASR_API int gsasr_window_attn_masked_forward(const gsasr_window_attn_masked *attn, void *stream);
+GSASR_API int gsasr_window_attn_masked_backward(const gsasr_window_attn_masked *attn, void *stream);
+
+typedef struct gsasr_window_attn_masked_bf16 {
+    int windows, heads, nq, nk, head_dim, table_rows;
+    float scale;
+    unsigned flags;       /* 0 (none defined) */
+    const gsasr_bf16 *q, *k, *v;
+    const float *table;
+    const int *index;
+    gsasr_bf16 *out;      /* written by the forward, read by the backward */
+    float *stats;
+    const gsasr_bf16 *grad_out;
+    gsasr_bf16 *g_q, *g_k, *g_v;
+    float *g_table;
+    void *scratch;
+    const float *mask;    /* fp32 */
+    int mask_windows;
+    int pitch_q, pitch_k, pitch_v, pitch_gq, pitch_gk, pitch_gv;
+} gsasr_window_attn_masked_bf16;
+GSASR_API size_t gsasr_window_attn_masked_bf16_scratch_bytes(const gsasr_window_attn_masked_bf16 *attn);   /* as gsasr_window_attn_scratch_bytes */
+GSASR_API int gsasr_window_attn_masked_bf16_forward(const gsasr_window_attn_masked_bf16 *attn, void *stream);
+GSASR_API int gsasr_window_attn_masked_bf16_backward(const gsasr_window_attn_masked_bf16 *attn, void *stream);
+
 /* Sampled pixels.  With `sample_coords` the reference renders the whole [3,H,W] image and
  * then picks the S requested pixels out of it, one indexing op per point (utils/gaussian_splatting.py:214-216;
  * the points come from basicsr/data/continuous_bicubic_downsample_dataset.py:86-88).  These entry points evaluate

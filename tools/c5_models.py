@@ -316,3 +316,74 @@ def training_step(encoder, decoder, optimizer, lq, gt, gt_sizes, scales, batched
     loss.backward()
     optimizer.step()
     return loss.detach(), params
+
+
+class _SwinShapedLayer(nn.Module):
+    """one Swin layer in this harness's own code: pre-norm window attention (packed qkv Linear, learned relative-position bias,
+    the shifted-window mask on odd layers) and a pre-norm MLP of ratio 2, residual around both; roll / partition / reverse in torch"""
+
+    def __init__(self, dim, heads, window, shift, attention):
+        super().__init__()
+        self.heads, self.window, self.shift, self.attention = heads, window, shift, attention
+        self.norm1, self.norm2 = nn.LayerNorm(dim), nn.LayerNorm(dim)
+        self.qkv, self.proj = nn.Linear(dim, 3 * dim), nn.Linear(dim, dim)
+        self.mlp = nn.Sequential(nn.Linear(dim, 2 * dim), nn.GELU(), nn.Linear(2 * dim, dim))
+        yy, xx = torch.meshgrid(torch.arange(window), torch.arange(window), indexing="ij")
+        cy, cx = yy.flatten(), xx.flatten()
+        self.register_buffer("index", (cy[:, None] - cy[None, :] + window - 1) * (2 * window - 1) + cx[:, None] - cx[None, :] + window - 1, persistent=False)
+        self.bias = nn.Parameter(nn.init.trunc_normal_(torch.zeros((2 * window - 1) ** 2, heads), std=0.02))
+
+    def region_mask(self, h, w, device):
+        """[windows per image, n, n] of 0 / -100 between the regions the shift brings together"""
+        s, sh = self.window, self.shift
+        label = torch.zeros(h, w, device=device)
+        cuts = (slice(0, -s), slice(-s, -sh), slice(-sh, None))
+        for a, ys in enumerate(cuts):
+            for b, xs in enumerate(cuts):
+                label[ys, xs] = 3 * a + b
+        win = label.view(h // s, s, w // s, s).permute(0, 2, 1, 3).reshape(-1, s * s)
+        return torch.where(win[:, None, :] != win[:, :, None], -100.0, 0.0)
+
+    def attend(self, qkv, mask):
+        if self.attention != "torch":
+            from gsasr_amd.attention import window_attention_qkv
+            y = window_attention_qkv(qkv, self.bias, self.index, compute="bf16" if self.attention == "hip_bf16" else "fp32", mask=mask)
+            return y.to(qkv.dtype) if self.attention == "hip_bf16" else y
+        W, n, C3 = qkv.shape
+        H, d = self.heads, C3 // (3 * self.heads)
+        q, k, v = qkv.reshape(W, n, 3, H, d).permute(2, 0, 3, 1, 4).unbind(0)
+        attn = (q * d ** -0.5) @ k.transpose(-2, -1) + self.bias[self.index].permute(2, 0, 1).unsqueeze(0)
+        if mask is not None:
+            attn = (attn.view(W // mask.shape[0], mask.shape[0], H, n, n) + mask.unsqueeze(1).unsqueeze(0)).view(W, H, n, n)
+        return (torch.softmax(attn, dim=-1) @ v).transpose(1, 2).reshape(W, n, C3 // 3)
+
+    def forward(self, x):
+        b, h, w, c = x.shape
+        s = self.window
+        y = self.norm1(x)
+        if self.shift:
+            y = torch.roll(y, (-self.shift, -self.shift), (1, 2))
+        y = y.view(b, h // s, s, w // s, s, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, s * s, c)
+        y = self.proj(self.attend(self.qkv(y), self.region_mask(h, w, x.device) if self.shift else None))
+        y = y.view(b, h // s, w // s, s, s, c).permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, c)
+        if self.shift:
+            y = torch.roll(y, (self.shift, self.shift), (1, 2))
+        x = x + y
+        return x + self.mlp(self.norm2(x))
+
+
+class SwinShapedStack(nn.Module):
+    """the SHAPE of the SwinIR encoder the reference ships with its AMP configurations (SwinIRNOUP: 36 layers, embed_dim 180,
+    6 heads, window 8, every second layer shifted by half a window) on tokens [B, h, w, 180] -- for measurement only: what the
+    36 window attentions cost in torch and through gsasr_amd.window_attention_qkv (`attention` "torch", "hip", "hip_bf16")"""
+
+    def __init__(self, dim=180, heads=6, window=8, layers=36, attention="torch"):
+        super().__init__()
+        if attention not in ("torch", "hip", "hip_bf16"):
+            raise ValueError(f"attention must be 'torch', 'hip' or 'hip_bf16' (got {attention!r})")
+        self.layers = nn.ModuleList([_SwinShapedLayer(dim, heads, window, window // 2 if i % 2 else 0, attention) for i in range(layers)])
+
+    def forward(self, x):
+        for layer in self.layers:
+            x = layer(x)
+        return x

@@ -13,7 +13,14 @@ and torch's reference expression, interleaved; then the decoder step under autoc
 Protocol: one process; every variant warmed up first; then `reps` rounds in which the variants take turns (interleaved, so a
 drift of the clock hits all of them), each turn `iters` back-to-back calls between two events on the current stream; the
 median of the rounds with their min and max, in milliseconds per call.  One JSON line per measurement.
-`--only-hip` runs the op alone (for a counter-collecting profiler run of its kernels)."""
+`--only-hip` runs the op alone (for a counter-collecting profiler run of its kernels).
+
+    python tools/window_attention_bench.py --masked [--only-hip] [--skip-decoder]      # profiles/window_attention_masked.txt
+
+`--masked`: gsasr_amd.window_attention_qkv on a packed qkv with a shifted-window mask (SwinIR's WindowAttention) against the
+reference's explicit expression and against F.scaled_dot_product_attention with bias + mask as `attn_mask`, in fp32 and on bf16
+inputs under bf16 autocast (compute="bf16"), forward and forward + backward; then the SwinIR-shaped stack of tools/c5_models.py
+(36 layers) with torch and hip attention, one forward + backward line each."""
 import argparse
 import json
 import os
@@ -25,8 +32,10 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
-from gsasr_amd.attention import window_attention, window_attention_rope, window_attention_rope_torch, window_attention_torch      # noqa: E402
+from gsasr_amd.attention import (window_attention, window_attention_qkv, window_attention_rope, window_attention_rope_torch,      # noqa: E402
+                                 window_attention_torch)
 
+MASKED_SHAPES = [(576, 64, 6, 30, 36), (64, 256, 6, 32, 4)]     # (W, n, H, d, nW): config 5's batch in SwinIR (16 samples of 48 x 48 LR in 8 x 8 windows); 16 x 16 windows
 OP_SHAPES = [(256, 144, 6, 30), (64, 256, 6, 32)]      # (W, n, H, d): config 5's batch (16 samples x 16 windows); the 16 x 16 configs
 ROPE_SHAPES = [(256, 144, 6, 32), (64, 256, 6, 32)]    # the RoPE decoder's: 192 channels; EDSR / RDN / SwinIR 144 tokens, HATL 256
 
@@ -180,6 +189,100 @@ def bf16_op_level(args, dev):
                                       form=name, **{k: round(x, 4) for k, x in r.items()})), flush=True)
 
 
+def swin_explicit_form(qkv, table, index, mask, scale=None):
+    """the expression of SwinIR's WindowAttention.forward (utils/swinir.py:233-254) between its two Linears"""
+    W, n, C3 = qkv.shape
+    H = table.shape[1]
+    d = C3 // (3 * H)
+    q, k, v = qkv.reshape(W, n, 3, H, d).permute(2, 0, 3, 1, 4).unbind(0)
+    attn = (q * d ** -0.5) @ k.transpose(-2, -1)
+    attn = attn + table[index.view(-1)].view(n, n, -1).permute(2, 0, 1).contiguous().unsqueeze(0)
+    nW = mask.shape[0]
+    attn = (attn.view(W // nW, nW, H, n, n) + mask.unsqueeze(1).unsqueeze(0)).view(-1, H, n, n)
+    return (torch.softmax(attn, dim=-1) @ v).transpose(1, 2).reshape(W, n, C3 // 3)
+
+
+def swin_sdpa_form(qkv, table, index, mask, scale=None):
+    """F.scaled_dot_product_attention with bias + mask as attn_mask ([nW, H, n, n], broadcast over the samples)"""
+    W, n, C3 = qkv.shape
+    H = table.shape[1]
+    d = C3 // (3 * H)
+    nW = mask.shape[0]
+    q, k, v = qkv.reshape(W // nW, nW, n, 3, H, d).permute(3, 0, 1, 4, 2, 5).unbind(0)
+    both = (table[index].permute(2, 0, 1).unsqueeze(0) + mask.unsqueeze(1)).to(q.dtype)
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=both).permute(0, 1, 3, 2, 4).reshape(W, n, C3 // 3)
+
+
+def shifted_window_mask(side, nW, dev):
+    """[nW, side^2, side^2] of 0 / -100: the regions of a half-window shift, as SwinIR's calculate_mask labels them, on an image of
+    sqrt(nW) x sqrt(nW) windows"""
+    per = int(round(nW ** 0.5))
+    size, shift = per * side, side // 2
+    label = torch.zeros(size, size)
+    cuts = (slice(0, -side), slice(-side, -shift), slice(-shift, None))
+    for a, ys in enumerate(cuts):
+        for b, xs in enumerate(cuts):
+            label[ys, xs] = 3 * a + b
+    win = label.view(per, side, per, side).permute(0, 2, 1, 3).reshape(nW, side * side)
+    diff = win[:, None, :] - win[:, :, None]
+    return torch.where(diff != 0, -100.0, 0.0).to(dev)
+
+
+def masked_op_level(args, dev):
+    for (W, n, H, d, nW) in MASKED_SHAPES:
+        g = torch.Generator().manual_seed(0)
+        C, side = H * d, int(round(n ** 0.5))
+        qkv32, wgt32 = torch.randn(W, n, 3 * C, generator=g).to(dev), torch.randn(W, n, C, generator=g).to(dev)
+        table = (0.5 * torch.randn((2 * side - 1) ** 2, H, generator=g)).to(dev)
+        yy, xx = torch.meshgrid(torch.arange(side), torch.arange(side), indexing="ij")
+        cy, cx = yy.flatten(), xx.flatten()
+        index = ((cy[:, None] - cy[None, :] + side - 1) * (2 * side - 1) + cx[:, None] - cx[None, :] + side - 1).to(dev)
+        mask = shifted_window_mask(side, nW, dev)
+        for amp in (False, True):
+            qkv, wgt = (qkv32.bfloat16(), wgt32.bfloat16()) if amp else (qkv32, wgt32)
+            hip = (lambda a, t, i, m: window_attention_qkv(a, t, i, compute="bf16", mask=m)) if amp else (lambda a, t, i, m: window_attention_qkv(a, t, i, mask=m))
+            forms = {"hip": hip} if args.only_hip else {"hip": hip, "torch_explicit": swin_explicit_form, "torch_sdpa": swin_sdpa_form}
+            leaves = [qkv.clone().requires_grad_(True), table.clone().requires_grad_(True)]
+
+            def fwd(fn):
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    return fn(qkv, table, index, mask)
+
+            def fwd_bwd(fn):
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                    out = fn(*leaves, index, mask)
+                torch.autograd.grad(out, leaves, wgt.to(out.dtype))
+
+            for what, run in (("forward", fwd), ("forward+backward", fwd_bwd)):
+                res = interleaved({name: (lambda f=fn: run(f)) for name, fn in forms.items()}, args.reps, args.iters)
+                for name, r in res.items():
+                    print(json.dumps(dict(level="op", position="bias+mask, packed qkv", precision="bf16 inputs, bf16 autocast" if amp else "fp32",
+                                          shape=dict(W=W, n=n, H=H, d=d, nW=nW), what=what, form=name, **{k: round(x, 4) for k, x in r.items()})), flush=True)
+
+
+def swin_stack_level(args, dev):
+    """the SwinIR-shaped stack (36 layers, dim 180, window 8, alternating shift) on config 5's batch, fp32 and bf16 autocast"""
+    import c5_models
+    torch.manual_seed(0)
+    nets = {}
+    for name in ("torch", "hip", "hip_bf16"):
+        nets[name] = c5_models.SwinShapedStack(attention=name).to(dev)
+        nets[name].load_state_dict(nets["torch"].state_dict())
+    x = torch.randn(16, 48, 48, 180, device=dev)
+    for amp in (False, True):
+        def step(net):
+            for p in net.parameters():
+                p.grad = None
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                loss = net(x).float().square().mean()
+            loss.backward()
+
+        run = {name: (lambda m=net: step(m)) for name, net in nets.items() if amp or name != "hip_bf16"}
+        for name, r in interleaved(run, max(3, args.reps // 2), 2, warmup=2).items():
+            print(json.dumps(dict(level="swin stack", layers=36, precision="bf16 autocast" if amp else "fp32", x=[16, 48, 48, 180], what="forward+backward",
+                                  mode=f"attention={name}", **{k: round(v, 3) for k, v in r.items()})), flush=True)
+
+
 def bf16_decoder_level(args, dev, position):
     """the decoder step under bf16 autocast: attention "torch", "hip" (fp32 kernels behind the cast) and "hip_bf16" """
     import c5_models
@@ -239,8 +342,15 @@ def main():
     ap.add_argument("--skip-bias", action="store_true", help="leave out the biased op and its decoder")
     ap.add_argument("--skip-rope", action="store_true", help="leave out the rotary op and its decoder")
     ap.add_argument("--bf16", action="store_true", help="the bf16 mode alone: both ops and the decoder step under bf16 autocast")
+    ap.add_argument("--masked", action="store_true", help="the masked op on a packed qkv and the SwinIR-shaped stack alone")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.masked:
+        if not args.skip_op:
+            masked_op_level(args, dev)
+        if not args.skip_decoder and not args.only_hip:
+            swin_stack_level(args, dev)
+        return
     if args.bf16:
         if not args.skip_op:
             bf16_op_level(args, dev)
