@@ -1420,12 +1420,29 @@ def window_attn_masked_forward(q, k, v, table, index, mask, scale: float, want_s
     return out, stats
 
 
-def window_attn_masked_backward(q, k, v, table, index, mask, scale: float, out, stats, grad_out, need=(True, True, True, True), packed=False):
+def window_attn_masked_backward(q, k, v, table, index, mask, scale: float, out, stats, grad_out, need=(True, True, True, True), packed=False,
+                                grads=None):
     """gsasr_window_attn_masked_backward -> (g_q, g_k, g_v, g_table), None where `need` is False.  `packed`: g_q, g_k, g_v are the
-    column blocks of ONE `[W,n,3C]` tensor, written in place through the gradient pitches (all three are then computed)"""
+    column blocks of ONE `[W,n,3C]` tensor, written in place through the gradient pitches (all three are then computed).
+    `grads`: the caller's own (g_q, g_k, g_v), each of its input's shape and dtype, contiguous or a view with unit column stride
+    and one row pitch (which goes into the descriptor), or None where none is wanted: written in place and returned; only
+    `need[3]` is then looked at"""
     d, fns = _masked_desc(q, k, v, table, index, mask, scale)
     C = int(q.shape[2])
-    if packed:
+    if grads is not None:
+        if packed:
+            raise RuntimeError("`grads` and `packed` exclude each other")
+        grads = list(grads)
+        if len(grads) != 3:
+            raise RuntimeError("`grads` must be (g_q, g_k, g_v), None where none is wanted")
+        for field, g, t in zip(("gq", "gk", "gv"), grads, (q, k, v)):
+            if g is None:
+                continue
+            pitch = _rows_view(g, "g_" + field[1], q.dtype == torch.bfloat16)
+            if g.shape != t.shape or g.device != t.device:
+                raise RuntimeError(f"g_{field[1]} must have {field[1]}'s shape {tuple(t.shape)} on its device (got {tuple(g.shape)})")
+            setattr(d, "pitch_" + field, pitch)
+    elif packed:
         if k.shape != q.shape:
             raise RuntimeError("a packed gradient needs nq == nk")
         whole = torch.empty(q.shape[0], q.shape[1], 3 * C, dtype=q.dtype, device=q.device)

@@ -5,8 +5,9 @@ prints its ratio.
 
 Shapes are (W, nq, nk, H, d, nW).  The shipped one carries the real mask of a shifted Swin block (the golden's); the tails of
 every tile, one mask broadcast over all windows, nW = W, the limits 255 / 256, both sides of every key-tile threshold between two
-forward instantiations, and 280 windows with a table gradient: more than 256
-windows per head, so one workgroup of k_attn_bwd_q serves windows slot, slot + 256 whose masks differ.  Every shape runs with a
+forward instantiations, and more than 256 windows per head with a table gradient, so that one workgroup of k_attn_bwd_q serves the
+windows slot, slot + 256: 280 windows with nW = 4 (256 % 4 == 0: the two windows of a slot read the SAME mask) and 258 with nW = 3
+(their masks differ; tests/test_window_attention_masked_dispatch_gpu.py row A has the rest of the walk).  Every shape runs with a
 random ASYMMETRIC mask (3 randn): Swin's own masks are symmetric in (i, j) and cannot show a transposed read in k_attn_bwd_kv,
 where the key is on the lane.  The index is relative over nq + nk - 1 rows of a table that has three more: unused rows must come
 back exactly 0.
@@ -29,7 +30,7 @@ NAMES = ("out", "g_q", "g_k", "g_v", "g_table")
 SHIPPED = [(8, 64, 64, 6, 30, 4)]
 TAILS = [(2, 9, 9, 2, 5, 2), (6, 17, 33, 3, 30, 3), (2, 33, 17, 1, 32, 1), (2, 2, 2, 1, 1, 2)]
 LIMITS = [(2, 255, 256, 2, 31, 2), (2, 256, 255, 2, 1, 1)]
-SLOTS = [(280, 9, 9, 6, 30, 4)]
+SLOTS = [(280, 9, 9, 6, 30, 4), (258, 9, 9, 2, 5, 3)]
 # the forward's instantiations by key tiles (3 | 4 | up to 9 | up to 16), both sides of every threshold; d = 8 and 32 with a packed
 # pitch that is a multiple of 8 take the bf16 forward's 16-byte loads, d = 30 its 4-byte ones, an odd d (TAILS) the 2-byte ones
 DISPATCH = [(2, 48, 48, 2, 8, 2), (2, 49, 49, 2, 32, 2), (2, 65, 65, 3, 30, 1), (2, 144, 144, 2, 32, 2), (2, 145, 145, 1, 30, 2)]
