@@ -154,6 +154,7 @@ _SIGNATURES = {     # every symbol include/gsasr_splat.h declares: name -> (rest
     "gsasr_abi_version": (_i, []),
     "gsasr_last_error": (ctypes.c_char_p, []),
     "gsasr_splat_workspace_bytes": (_sz, [_dp]),
+    "gsasr_splat_counter_bytes": (_sz, [_dp]),
     "gsasr_splat_plan": (_i, [_vp, _vp, _vp, _dp, _vp, _sz, _vp]),
     "gsasr_splat_forward": (_i, [_dp, _vp, _sz, _vp, _vp]),
     "gsasr_splat_forward_u8": (_i, _u8_tail),
@@ -1088,7 +1089,14 @@ def _loss_scratch(d: Dims, dev) -> torch.Tensor:
     n = int(lib().gsasr_loss_scratch_bytes(ctypes.byref(d)))
     if n == 0:
         check(-1, "gsasr_loss_scratch_bytes")
-    return torch.empty(n // 4, dtype=torch.float32, device=dev)
+    return _loss_scratch_of(n, dev)
+
+
+def _loss_scratch_of(nbytes: int, dev) -> torch.Tensor:
+    """the partial sums of a fused loss: fp32, `nbytes` = gsasr_loss_scratch_bytes() of the call's dims.  The one place where
+    that scratch is allocated: tests/test_workspace_bounds_gpu.py replaces this function to put the scratch between guards (keep
+    it a function of its own)"""
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
 
 
 def _loss_grad(d0: Dims, shape, dev) -> torch.Tensor:
@@ -1167,7 +1175,7 @@ def _step_loss(shape, pp: int, src, target: torch.Tensor, kind: int, norm: int, 
             hwc = (B, d.slot, d.w, 3) if d.batch > 1 else (d.h, d.w, 3)
             grad = _loss_grad(d0, planar if d.flags & FLAG_CHW_GRAD else hwc, dev)
         loss = torch.empty(1 + B, dtype=torch.float32, device=dev)
-        scratch = torch.empty(nscratch // 4, dtype=torch.float32, device=dev)
+        scratch = _loss_scratch_of(nscratch, dev)
         img = torch.empty(planar, dtype=torch.float32, device=dev) if want_image else None
         desc = Loss(int(kind), int(norm), float(weight), float(eps), target.data_ptr(), trows, None if grad is None else grad.data_ptr(),
                     loss.data_ptr(), None if img is None else img.data_ptr(), scratch.data_ptr())
@@ -1279,6 +1287,19 @@ def _chk_act(t: torch.Tensor, name: str, bf16: bool) -> int:
     return t.data_ptr()
 
 
+def _own_scratch(scratch: torch.Tensor, n: int, dev, sizer: str) -> int:
+    """a caller's scratch for a call that needs `n` bytes (the export `sizer`): a contiguous uint8 CUDA tensor of at least `n`
+    bytes on `dev`, 256-byte aligned -> its address"""
+    if not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
+            and scratch.device == dev):
+        raise RuntimeError("scratch must be a contiguous uint8 CUDA tensor on the call's device")
+    if scratch.numel() < n:
+        raise RuntimeError(f"scratch is smaller than {sizer}()")
+    if scratch.data_ptr() % 256:
+        raise RuntimeError("scratch must be 256-byte aligned")
+    return scratch.data_ptr()
+
+
 def make_window_attn_rope(windows: int, heads: int, nq: int, nk: int, head_dim: int, angle_rows: int, scale: float, bf16: bool = False):
     """a gsasr_window_attn_rope (`bf16`: gsasr_window_attn_rope_bf16) descriptor without pointers"""
     d = (WindowAttnRopeBf16 if bf16 else WindowAttnRope)(int(windows), int(heads), int(nq), int(nk), int(head_dim), int(angle_rows))
@@ -1320,9 +1341,9 @@ def _attn_forward(d, fns, q, want_stats: bool):
     return out, stats
 
 
-def _attn_backward(d, fns, q, out, stats, grad_out, **grads):
+def _attn_backward(d, fns, q, out, stats, grad_out, scratch=None, **grads):
     """out, stats and grad_out checked, the gradient pointers set (`grads`: field -> tensor or None), the scratch asked for
-    (0: the descriptor's error is raised) and allocated, the backward called"""
+    (0: the descriptor's error is raised) and allocated (or the caller's `scratch`, a uint8 tensor, taken), the backward called"""
     bf16 = q.dtype == torch.bfloat16
     _chk_act(out, "out", bf16), _chk(stats, "stats"), _chk_act(grad_out, "grad_out", bf16)
     if out.shape != q.shape or grad_out.shape != q.shape or tuple(stats.shape) != (d.windows, d.heads, d.nq):
@@ -1335,8 +1356,11 @@ def _attn_backward(d, fns, q, out, stats, grad_out, **grads):
         n = int(getattr(lib(), fns["scratch_bytes"])(ctypes.byref(d)))
         if n == 0:
             check(-1, fns["scratch_bytes"])
-        scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
-        d.scratch = scratch.data_ptr()
+        if scratch is None:
+            scratch = torch.empty(n // 4, dtype=torch.float32, device=dev)
+            d.scratch = scratch.data_ptr()
+        else:
+            d.scratch = _own_scratch(scratch, n, dev, fns["scratch_bytes"])
         check(getattr(lib(), fns["backward"])(ctypes.byref(d), _stream(dev)), fns["backward"])
 
 
@@ -1356,13 +1380,13 @@ def window_attn_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table
     return _attn_forward(d, fns, q, want_stats)
 
 
-def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_out, need=(True, True, True, True)):
+def window_attn_backward(q, k, v, table, index, scale: float, out, stats, grad_out, need=(True, True, True, True), scratch=None):
     """gsasr_window_attn_backward (bf16 activations: gsasr_window_attn_bf16_backward) -> (g_q, g_k, g_v, g_table), None where
-    `need` is False"""
+    `need` is False.  `scratch`: the caller's uint8 tensor of gsasr_window_attn[_bf16]_scratch_bytes()"""
     d, fns = _attn_desc(q, k, v, table, False, scale)
     _attn_index(d, index)
     grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, table), need)]
-    _attn_backward(d, fns, q, out, stats, grad_out, **dict(zip(("g_q", "g_k", "g_v", "g_table"), grads)))
+    _attn_backward(d, fns, q, out, stats, grad_out, scratch, **dict(zip(("g_q", "g_k", "g_v", "g_table"), grads)))
     return tuple(grads)
 
 
@@ -1421,12 +1445,12 @@ def window_attn_masked_forward(q, k, v, table, index, mask, scale: float, want_s
 
 
 def window_attn_masked_backward(q, k, v, table, index, mask, scale: float, out, stats, grad_out, need=(True, True, True, True), packed=False,
-                                grads=None):
+                                grads=None, scratch=None):
     """gsasr_window_attn_masked_backward -> (g_q, g_k, g_v, g_table), None where `need` is False.  `packed`: g_q, g_k, g_v are the
     column blocks of ONE `[W,n,3C]` tensor, written in place through the gradient pitches (all three are then computed).
     `grads`: the caller's own (g_q, g_k, g_v), each of its input's shape and dtype, contiguous or a view with unit column stride
     and one row pitch (which goes into the descriptor), or None where none is wanted: written in place and returned; only
-    `need[3]` is then looked at"""
+    `need[3]` is then looked at.  `scratch`: the caller's uint8 tensor of gsasr_window_attn_masked[_bf16]_scratch_bytes()"""
     d, fns = _masked_desc(q, k, v, table, index, mask, scale)
     C = int(q.shape[2])
     if grads is not None:
@@ -1451,7 +1475,7 @@ def window_attn_masked_backward(q, k, v, table, index, mask, scale: float, out, 
     else:
         grads = [torch.empty(t.shape, dtype=t.dtype, device=t.device) if n else None for t, n in zip((q, k, v), need)]
     g_table = torch.empty_like(table) if need[3] else None
-    _attn_backward(d, fns, out, out, stats, grad_out, g_q=grads[0], g_k=grads[1], g_v=grads[2], g_table=g_table)
+    _attn_backward(d, fns, out, out, stats, grad_out, scratch, g_q=grads[0], g_k=grads[1], g_v=grads[2], g_table=g_table)
     return (whole, g_table) if packed else (*grads, g_table)
 
 
@@ -1466,16 +1490,17 @@ def window_attn_rope_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     return (*_attn_forward(d, fns, q, want_stats), cossin)
 
 
-def window_attn_rope_backward(q, k, v, angles, scale: float, out, stats, cossin, grad_out, need=(True, True, True, True)):
+def window_attn_rope_backward(q, k, v, angles, scale: float, out, stats, cossin, grad_out, need=(True, True, True, True), scratch=None):
     """gsasr_window_attn_rope_backward -> (g_q, g_k, g_v, g_angles), None where `need` is False (the angle gradient is formed
-    from g_q and g_k: both are computed for it, and dropped here when not needed themselves)"""
+    from g_q and g_k: both are computed for it, and dropped here when not needed themselves).  `scratch`: the caller's uint8
+    tensor of gsasr_window_attn_rope[_bf16]_scratch_bytes()"""
     d, fns = _attn_desc(q, k, v, angles, True, scale)
     d.cossin = _chk(cossin, "cossin")
     if tuple(cossin.shape) != (*angles.shape, 2):
         raise RuntimeError("out / grad_out must have q's shape, stats [W,H,nq] and cossin angles' shape + [2]")
     make = (need[0] or need[3], need[1] or need[3], need[2], need[3])
     grads = [torch.empty_like(t) if n else None for t, n in zip((q, k, v, angles), make)]
-    _attn_backward(d, fns, q, out, stats, grad_out, **dict(zip(("g_q", "g_k", "g_v", "g_angles"), grads)))
+    _attn_backward(d, fns, q, out, stats, grad_out, scratch, **dict(zip(("g_q", "g_k", "g_v", "g_angles"), grads)))
     return tuple(g if n else None for g, n in zip(grads, need))
 
 
@@ -1515,10 +1540,12 @@ def _u8_picture(t: torch.Tensor, name: str):
 
 
 def image_metrics(img: torch.Tensor, ref: torch.Tensor, sizes=None, crop_border: int = 0, y_channel: bool = False, bgr: bool = False,
-                  psnr: bool = True, ssim: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  psnr: bool = True, ssim: bool = True, out: Optional[torch.Tensor] = None,
+                  scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gsasr_image_metrics: `img`, `ref` uint8 `[h,w,3]` or `[B,H,W,3]` (windows of larger tensors are taken through their
     strides), `sizes` the samples' own (h_b, w_b) -> float64 `[B,2]` = {psnr, ssim} per sample on the device, no
-    synchronisation.  A metric that is not asked for leaves its column as it is (`out`: the caller's tensor; else zeros)."""
+    synchronisation.  A metric that is not asked for leaves its column as it is (`out`: the caller's tensor; else zeros).
+    `scratch`: the caller's uint8 tensor of gsasr_metrics_scratch_bytes()."""
     pi, ip, istr = _u8_picture(img, "img")
     pr, rp, rstr = _u8_picture(ref, "ref")
     if img.shape != ref.shape or img.device != ref.device:
@@ -1535,8 +1562,12 @@ def image_metrics(img: torch.Tensor, ref: torch.Tensor, sizes=None, crop_border:
             out = torch.empty(B, 2, dtype=torch.float64, device=dev) if psnr and ssim else torch.zeros(B, 2, dtype=torch.float64, device=dev)
         elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, 2) and out.device == dev):
             raise RuntimeError(f"out must be a contiguous float64 [{B}, 2] tensor on the pictures' device")
-        scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
-        d.img, d.ref, d.out, d.scratch = pi, pr, out.data_ptr(), scratch.data_ptr()
+        if scratch is None:
+            scratch = torch.empty(n // 8, dtype=torch.float64, device=dev)
+            ps = scratch.data_ptr()
+        else:
+            ps = _own_scratch(scratch, n, dev, "gsasr_metrics_scratch_bytes")
+        d.img, d.ref, d.out, d.scratch = pi, pr, out.data_ptr(), ps
         check(lib().gsasr_image_metrics(ctypes.byref(d), _stream(dev)), "gsasr_image_metrics")
     return out
 
@@ -1716,6 +1747,12 @@ def _query_points(points: torch.Tensor, batch: int, device) -> Tuple[torch.Tenso
     return points.detach().to(device=device, dtype=torch.float32).contiguous(), int(points.shape[-2])
 
 
+def _fresh_ws(nbytes: int, dev) -> torch.Tensor:
+    """a plan workspace that is not pooled (the sampled and query step forms).  The one place where it is allocated:
+    tests/test_workspace_bounds_gpu.py replaces this function to put the workspace between guards (keep it a function of its own)"""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 def _sample_ws(d: Dims, n_points: int, dev) -> torch.Tensor:
     nbytes = lib().gsasr_sample_workspace_bytes(ctypes.byref(d), n_points)
     if nbytes == 0:
@@ -1723,13 +1760,21 @@ def _sample_ws(d: Dims, n_points: int, dev) -> torch.Tensor:
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
 
-def sample_forward(p: Plan, points: torch.Tensor, _query: bool = False):
-    """values of the splat at `points` only: `[3,S]` (`[B,3,S]` on a batched canvas) + the state for `sample_backward`."""
+def sample_forward(p: Plan, points: torch.Tensor, _query: bool = False, sample_ws: Optional[torch.Tensor] = None):
+    """values of the splat at `points` only: `[3,S]` (`[B,3,S]` on a batched canvas) + the state for `sample_backward`.
+    `sample_ws`: the caller's uint8 tensor of gsasr_sample_workspace_bytes(), which the state then carries to the backward."""
     B = max(int(p.dims.batch), 1)
     pts, n = (_query_points if _query else _points)(points, B, p.device)
     name = "gsasr_splat_query_forward" if _query else "gsasr_splat_sample_forward"
     with _on(p.device):
-        sws = _sample_ws(p.dims, n, p.device)
+        if sample_ws is None:
+            sws = _sample_ws(p.dims, n, p.device)
+        else:
+            sws = sample_ws
+            need = int(lib().gsasr_sample_workspace_bytes(ctypes.byref(p.dims), n))
+            if need == 0:
+                check(-1, "gsasr_sample_workspace_bytes")
+            _own_scratch(sws, need, p.device, "gsasr_sample_workspace_bytes")
         out = torch.empty((B, 3, n) if B > 1 else (3, n), dtype=torch.float32, device=p.device)
         check(getattr(lib(), name)(ctypes.byref(p.dims), p.workspace.data_ptr(), p.workspace.numel(),
                                    pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(),
@@ -1737,10 +1782,10 @@ def sample_forward(p: Plan, points: torch.Tensor, _query: bool = False):
     return out, (pts, n, sws)
 
 
-def query_forward(p: Plan, points: torch.Tensor):
+def query_forward(p: Plan, points: torch.Tensor, sample_ws: Optional[torch.Tensor] = None):
     """values of the splat at fractional pixel positions: `points` float `[S,2]` (r, c) on the image's own grid (`[B,S,2]` on a
     batched canvas) -> `[3,S]` (`[B,3,S]`) + the state for `query_backward`.  `p`: a plan made with `flags=FLAG_CONTINUOUS`."""
-    return sample_forward(p, points, _query=True)
+    return sample_forward(p, points, _query=True, sample_ws=sample_ws)
 
 
 def query_backward(p: Plan, state, sigmas, coords, colors, grad_out, g_sigmas, g_coords, g_colors,
@@ -1805,7 +1850,7 @@ def _step_sampled(shape, pp: int, src, points: torch.Tensor, dev, names=None):
     names = names or _STEP_SAMPLE
     pts, n = (_query_points if names is _STEP_QUERY else _points)(points, B, dev)
     with _on(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _fresh_ws(nbytes, dev)
         sws = _sample_ws(d, n, dev)
         out = torch.empty((B, 3, n) if B > 1 else (3, n), dtype=torch.float32, device=dev)
         _step_call(names, pp, src, d, ws, nbytes, pts.data_ptr(), n, out.data_ptr(), sws.data_ptr(), sws.numel(), _stream(dev))

@@ -317,6 +317,15 @@ size_t gsasr_splat_workspace_bytes(const gsasr_dims *dims)
     return make_layout(dims).total;
 }
 
+size_t gsasr_splat_counter_bytes(const gsasr_dims *dims)
+{
+    if (!dims_ok(dims)) {
+        fail(GSASR_ERR_ARG, "bad dims");
+        return 0;
+    }
+    return make_layout(dims).count_bytes;
+}
+
 size_t gsasr_splat_workspace_bytes_view(const gsasr_dims *dims, const gsasr_view *view)
 {
     if (!view_ok(dims, view)) {

@@ -209,6 +209,12 @@ GSASR_API const char *gsasr_last_error(void);
 /* Bytes of scratch the plan needs for these dims (0 on bad dims). 256-byte aligned base required. */
 GSASR_API size_t gsasr_splat_workspace_bytes(const gsasr_dims *dims);
 
+/* Bytes of ONE of the workspace's two counter arrays for these dims (0 on bad dims): the per-cell counters, the extent groups
+ * and the dead-class counter lines that GSASR_FLAG_COUNTERS_CLEAN speaks of.  The plan header (256 bytes) is followed by the
+ * array of parity 0 and then by that of GSASR_FLAG_PARITY.  Read-only; for callers that keep workspaces between plans and want
+ * to check, or clear, the array the next plan will count in. */
+GSASR_API size_t gsasr_splat_counter_bytes(const gsasr_dims *dims);
+
 /* Bin the Gaussians for [row0,row1) into `workspace` (classify -> scan -> scatter -> pack). */
 GSASR_API int gsasr_splat_plan(const float *sigmas /*[s,3]*/, const float *coords /*[s,2]*/,
                      const float *colors /*[s,3]*/, const gsasr_dims *dims, void *workspace,
@@ -362,7 +368,9 @@ GSASR_API int gsasr_step_backward_view(const float *gs_parameters, const float *
  * (L1Loss / MSELoss / CharbonnierLoss, basicsr/losses/basic_loss.py:14-25), summed over the samples and divided by b).  The
  * forward kernels hold the finished pixel in registers: they load the target pixel, form d = v - t and write dL/dimg and one
  * partial sum of phi(d) per sub-tile; a small kernel adds the partials of each sample in a fixed order, in double.  No image is
- * written or read back, no float atomics, no memset; two calls on one plan give the same bits.
+ * written or read back, no float atomics, no memset; two calls on one plan give the same bits wherever the forward gives the
+ * same pixels (the search kernels add a pixel's terms in an order that follows wave timing: where Gaussians overlap, the pixels'
+ * last bits, and then the loss's and the gradient's, may differ between two calls).
  *
  *   kind                    phi(d)             phi'(d)
  *   GSASR_LOSS_L1           |d|                (d > 0) - (d < 0): 0 at d == 0, torch's convention

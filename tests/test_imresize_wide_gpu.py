@@ -25,6 +25,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from test_imresize import adjoint_f64, resize_f64      # noqa: E402
+import wsguard      # noqa: E402
 from test_imresize_gpu import padded_batch      # noqa: E402
 from test_imresize_wide import (ALL_OK, AXIS_CASES, SMALL_BAD, case_id, check_entries, matrices,      # noqa: E402
                                 taps_per_output)
@@ -176,6 +177,10 @@ def test_scratch_between_nan_guards(dev, name):
         after = buf.view(torch.int32)
         assert torch.equal(after[:GUARD], before[:GUARD]) and torch.equal(after[GUARD + words:], before[GUARD + words:]), (name, backward)
         assert bool((before == before[0]).all()) and bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + words:]).all())
+        for fill in ("zero", "seeded"):         # the scratch from the other kinds of garbage (tests/wsguard.py), the guards as they are
+            mid.copy_(torch.from_numpy(wsguard.fill_bytes(fill, 4 * words, seed=7)).view(torch.float32))
+            assert torch.equal(run(mid).view(torch.int32), want.view(torch.int32)), (name, backward, fill)
+            assert torch.equal(after[:GUARD], before[:GUARD]) and torch.equal(after[GUARD + words:], before[GUARD + words:]), (name, backward, fill)
         with pytest.raises(RuntimeError, match="smaller than gsasr_resize_scratch_bytes"):
             run(buf[GUARD:GUARD + words - 1])
 

@@ -18,6 +18,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import wsguard      # noqa: E402
 from test_make_batch import ALL8, CASES, fixture, run_case      # noqa: E402
 
 from gsasr_amd import _cabi      # noqa: E402
@@ -186,13 +187,15 @@ def test_guards_and_repeatability(dev):
     n_scratch = int(_cabi.lib().gsasr_batch_scratch_bytes(ctypes.byref(d)))
     assert n_scratch > 0 and n_scratch % 256 == 0
     outs = []
-    for _ in range(2):
+    for fill in (None, None, "zero", "seeded"):      # the scratch as allocated (0xA5), twice, then from the fills of tests/wsguard.py
         fl = torch.full((G + n_gt + G + n_lq + G,), float("nan"), device=dev)
         by = torch.full((256 + n_scratch + 256,), 0xA5, dtype=torch.uint8, device=dev)
         gt = fl[G:G + n_gt].view(3, 3, Gh, Gw)
         lq = fl[G + n_gt + G:G + n_gt + G + n_lq].view(3, 3, lr, lr)
         scratch = by[256:256 + n_scratch]
         assert scratch.data_ptr() % 256 == 0
+        if fill:
+            scratch.copy_(torch.from_numpy(wsguard.fill_bytes(fill, n_scratch, seed=7)))
         _cabi.batch_make(srcs, crops, aug, gt, lq, scratch=scratch)
         torch.cuda.synchronize()
         assert bool(torch.isfinite(gt).all()) and bool(torch.isfinite(lq).all())
@@ -200,6 +203,7 @@ def test_guards_and_repeatability(dev):
         assert bool((by[:256] == 0xA5).all()) and bool((by[-256:] == 0xA5).all())
         outs.append((gt.clone(), lq.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    assert all(torch.equal(o[0], outs[0][0]) and torch.equal(o[1], outs[0][1]) for o in outs[2:])
     f = [[bool(a & m) for a in aug] for m in (1, 2, 4)]
     cpu = D.make_batch([t.cpu() for t in srcs], crops, lr, *f, gt_pad=(Gh, Gw))
     assert torch.equal(outs[0][0].cpu(), cpu["gt"])
